@@ -2,7 +2,7 @@
 """Headline benchmark: FastSLAM filter steps on synthetic 360-degree bearing+colour scans.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P] [--landmarks L]
-                    [--assoc ml|known] [--no-cpu-baseline] [--no-secondary]
+                    [--assoc ml|known] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary] ...]
 
 One "step" = one whole cam_cb (prkt_core_v2.py:59-137): weight reset, motion sample,
 maximum-likelihood data association, per particle x landmark EKF update + weight,
@@ -17,10 +17,19 @@ the environment; started bare (`python bench.py --gpus N`) the script launches t
 itself as child processes BEFORE it touches the GPU and relays rank 0's line.  `n_gpus` is
 the world size RCCL actually formed, and it must equal --gpus.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with two extra
-objects: "roofline" for the dominant kernel of the timed route (timed with hipEvents on
-the library's own stream inside the timed region) and "cpu_baseline" (the NumPy oracle of
-the same step on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up,
+warms up, times the K steps and reports them, with "roofline" for the dominant kernel of the
+timed route (timed with hipEvents on the library's own stream inside the timed region).
+Everything that takes work of its own moves behind --full: the untimed probes behind the
+timed region, configs[1] and the configs[4] shard, the facade at the reference's scene
+sizes, the measured copy bandwidth and "cpu_baseline" (the NumPy oracle of the same step on
+a bounded sample of the same workload); the --no-* options switch parts of it off.
+
+--dump-outputs DIR writes what the timed path computed in its last step, before anything
+else touches the filter: poses.npy (P x 4: x, y, heading, weight; a seeded sample of rows,
+pose_particles.npy, when P is in the millions), summary.npy, and the landmarks of a fixed,
+seeded sample of particles (sample_particles.npy, landmark_means.npy, landmark_covs.npy,
+landmark_counts.npy), all float64 and at most 64 MB together.
 """
 from __future__ import annotations
 
@@ -518,6 +527,42 @@ def per_step_replay(filt, lib, P, L, means, covs, scans, ws, us, ids, first, las
             "kernel_ms_min_max_timed_window": [float(kw.min()), float(kw.max())] if kw.size else None}
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # (under 64 MB, .npy headers included)
+
+
+def dump_outputs(filt, P, L, out_dir, write=True):
+    """What a caller of the timed path receives after its last step, as float64 .npy files under out_dir: the particles' poses
+    and weights (all of them, or a seeded sample of rows when they alone would take half the limit: pose_particles.npy), the
+    filter's summary, and the landmarks (means, covariances, update counts) of a fixed, seeded sample of particles, as many as
+    fit the limit beside the poses.  Called on every rank (the downloads complete a sharded filter's pending exchange); only
+    `write` ranks write."""
+    poses = np.asarray(filt.download_poses(), dtype=np.float64)
+    pose_rows = None
+    if poses.nbytes > DUMP_LIMIT_BYTES // 2:
+        pose_rows = np.sort(np.random.RandomState(2023).choice(P, DUMP_LIMIT_BYTES // 2 // poses[0].nbytes, replace=False))
+        poses = poses[pose_rows]
+    summary = np.asarray(filt.summary(), dtype=np.float64)
+    per_particle = L * (5 + 25 + 1) * 8
+    spent = poses.nbytes + (0 if pose_rows is None else pose_rows.size * 8) + (1 << 20)
+    n = int(max(1, min(P, (DUMP_LIMIT_BYTES - spent) // per_particle)))
+    sample = np.sort(np.random.RandomState(2024).choice(P, n, replace=False)) if n < P else np.arange(P)
+    means = np.empty((n, L, 5))
+    covs = np.empty((n, L, 5, 5))
+    counts = np.empty((n, L))
+    for j, p in enumerate(sample):
+        m, c, k = filt.download_landmarks(int(p), int(p) + 1)
+        means[j], covs[j], counts[j] = m[0], c[0], k[0]
+    if not write:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [("poses", poses), ("summary", summary), ("sample_particles", sample.astype(np.float64)),
+              ("landmark_means", means), ("landmark_covs", covs), ("landmark_counts", counts)]
+    if pose_rows is not None:
+        arrays.append(("pose_particles", pose_rows.astype(np.float64)))
+    for name, a in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def roofline_object(P, L, route, obs_ms, obs_n, stride, K, copy_gbs):
     obs_avg_s = (obs_ms / max(obs_n, 1)) * 1e-3
     alg_bytes = float(P) * L * BYTES_PER_UPDATE
@@ -582,6 +627,11 @@ def main():
     ap.add_argument("--particles", type=int, default=DEFAULT_P, help="particles per GPU")
     ap.add_argument("--landmarks", type=int, default=DEFAULT_L)
     ap.add_argument("--assoc", choices=["ml", "known"], default="ml")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: probes, configs[1], the configs[4] shard, the facade objects, the copy "
+                         "bandwidth and the CPU baseline (the --no-* options below switch parts of it off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] object")
     ap.add_argument("--no-probes", action="store_true", help="skip the untimed probes behind the timed region")
@@ -597,6 +647,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the outputs, the line -- nothing else
+        args.no_cpu_baseline = args.no_secondary = args.no_probes = args.no_configs4 = args.no_refscene = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])  # never returns
 
@@ -654,7 +706,7 @@ def main():
     P, L = args.particles, args.landmarks
     K, W = args.steps, args.warmup
     EXTRA = 32  # untimed steps after the timed region (association share, unique sources, supplied-ids route)
-    NSC = max(K + W + EXTRA, 64)  # (the per-step replay runs through trajectory step 62)
+    NSC = max(K + W + EXTRA, 64) if args.full else K + W  # (the per-step replay runs through trajectory step 62)
     means, covs, scans = synthetic_inputs(L, NSC)
     ws = synthetic_controls(NSC)
     ids = np.arange(1, L + 1, dtype=np.int32) if args.assoc == "known" else None
@@ -717,6 +769,8 @@ def main():
     flagged = filt.observe_flagged() if hasattr(filt, "observe_flagged") else None
     if route in ("ml_regs", "ml_fused") and hasattr(filt, "observe_published") and filt.observe_published():
         route += "_pub"  # which instance of the one-pass route worked on the scans is decided on the device
+    if args.dump_outputs:  # the filter as the last timed step left it, before any probe touches it
+        dump_outputs(filt, P, L, args.dump_outputs, write=rank == 0)
     # validity probe (untimed): share of the blobs of the last timed scan that the particles, as they
     # stand now, still associate with some landmark (the workload degenerates when this collapses)
     matched = None
@@ -734,15 +788,16 @@ def main():
     # (after a resample several particles descend from one ancestor and read the same slot, so part of
     # the 224 B/update stream is served by L2 / Infinity Cache, not HBM), from a few extra untimed steps
     uniq = []
-    filt.enable_timing(0b0000010)
-    filt.reset_timings()
-    for s in range(W + K, W + K + (0 if args.no_probes else 8)):
-        one_step(s)
-        if not sharded and hasattr(filt, "download_sources"):
-            uniq.append(int(np.unique(filt.download_sources()).size))
-    barrier()
-    tm["assoc"] = filt.timings()["assoc"]
-    filt.enable_timing(0)
+    if args.full:
+        filt.enable_timing(0b0000010)
+        filt.reset_timings()
+        for s in range(W + K, W + K + (0 if args.no_probes else 8)):
+            one_step(s)
+            if not sharded and hasattr(filt, "download_sources"):
+                uniq.append(int(np.unique(filt.download_sources()).size))
+        barrier()
+        tm["assoc"] = filt.timings()["assoc"]
+        filt.enable_timing(0)
 
     # the streaming figure without duplicates: the same observe launches back to back WITHOUT resamples,
     # every particle reading its own slot (all particles then sit at one pose: the bytes are the same)
@@ -957,7 +1012,7 @@ def main():
     # what a plain device-to-device copy reaches on THIS box (read + write bytes / time), outside the
     # timed region: the practical ceiling next to the 8 TB/s vendor figure
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         n = 1 << 27  # 2 x 1 GiB of float64
         a = torch.empty(n, dtype=torch.float64, device="cuda").normal_()
         b = torch.empty_like(a)
@@ -1019,7 +1074,8 @@ def main():
             roof["no_resample_probe"] = no_dup
         if known is not None:
             roof["ekf_stage"] = known
-        roof["assoc_kernel_ms"] = assoc_ms / max(assoc_n, 1)
+        if args.full:  # (the association kernel is timed in the untimed steps behind the timed region)
+            roof["assoc_kernel_ms"] = assoc_ms / max(assoc_n, 1)
         if flagged is not None:
             roof["particles_sent_to_general_kernels_last_step"] = flagged[0]
             roof["candidate_list_overflows_last_step"] = flagged[1]
@@ -1052,7 +1108,8 @@ def main():
                 else "single GPU",
             },
             "roofline": roof,
-            "kernel_ms_per_step": {"observe": obs_ms / max(obs_n, 1), "assoc": assoc_ms / max(assoc_n, 1)},
+            "kernel_ms_per_step": {"observe": obs_ms / max(obs_n, 1), "assoc": assoc_ms / max(assoc_n, 1)} if args.full
+            else {"observe": obs_ms / max(obs_n, 1)},
             "summary": list(summary),
             "matched_fraction_last_timed_scan": matched,  # validity: the scans stayed matchable to the end
         }

@@ -19,6 +19,10 @@ produced do).  Each fixture stores inputs and the reference's outputs:
                      ancestors, summaries, strided landmark sample)
   motion.npz         motion_update sequences incl. heading wrap
   resample.npz       low_variance_resample ancestor lists for crafted weights
+  reference_live.npz the reference's answers on the random inputs of
+                     tests/test_oracle_vs_reference_live.py (triples, resample
+                     ancestors, new-landmark geometry and bookkeeping); written
+                     alone by ``python oracle/make_golden.py --only-reference-live``
   step_potential.npz the potential-feature branch of cam_cb (:109-118, :366-367): reference particles whose
                      `potential_features` are populated by hand (negative ids, update_count 0..6, one immutable),
                      P=12, 5 full + 4 potential landmarks per particle, 3 steps: ids (negative for potential
@@ -565,9 +569,121 @@ def gen_resample():
     return out
 
 
+def _reading_row(st, b):
+    """(x, y, quaternion x, y, z, w, bearing, r, g, b) of an (Odometry, Blob) reading."""
+    p, q = st.pose.pose.position, st.pose.pose.orientation
+    return [p.x, p.y, q.x, q.y, q.z, q.w, b.bearing, b.color.r, b.color.g, b.color.b]
+
+
+def gen_reference_live():
+    """The reference's answers on the random inputs of tests/test_oracle_vs_reference_live.py (the same seeds, the same order of
+    draws): per (pose, landmark, blob) probability of match, Kalman gain and importance factor; low_variance_resample ancestors;
+    and the new-landmark geometry and bookkeeping of prkt_core_v2.py:546-746 on random readings."""
+    from nav_msgs.msg import Odometry
+
+    out = {}
+    # (1) triples
+    rs = np.random.RandomState(4242)
+    cols = {k: [] for k in ("pose", "mean", "cov", "blob", "heading", "prob", "K", "w")}
+    for i in range(40):
+        pose = (rs.uniform(-3, 3), rs.uniform(-3, 3), rs.uniform(-3, 3))
+        mean = np.array([rs.uniform(-25, 25), rs.uniform(-25, 25), *rs.uniform(0, 255, 3)])
+        a = rs.normal(size=(5, 5))
+        cov = a @ a.T / 5 + 0.2 * np.identity(5)
+        tb = math.atan2(mean[1] - pose[1], mean[0] - pose[0]) - pose[2]
+        blob = (tb + rs.uniform(-0.6, 0.6), *(mean[2:] + rs.uniform(-12, 12, 3)))
+        p = core.FilterParticle()
+        p.state.pose.pose.position.x, p.state.pose.pose.position.y = pose[0], pose[1]
+        p.state.pose.pose.orientation = heading_to_quaternion(pose[2])
+        f = core.Feature(mean=mean.copy(), covar=cov.copy())
+        p.feature_set[1] = f
+        H = p.measurement_jacobian(1)
+        Q = p.measurement_covariance(H, 1, 0.1 * np.identity(4))
+        K = p.kalman_gain(1, H, core.inverse(Q))
+        for k, v in (("pose", pose), ("mean", mean), ("cov", cov), ("blob", blob),
+                     ("heading", quaternion_to_heading(p.state.pose.pose.orientation)),
+                     ("prob", p.probability_of_match(p.state, Blob(*blob), f)), ("K", K),
+                     ("w", p.importance_factor(Q, Blob(*blob), p.generate_measurement(1)))):
+            cols[k].append(np.asarray(v, dtype=np.float64))
+    for k, v in cols.items():
+        out["tri_" + k] = np.array(v)
+    # (2) low_variance_resample
+    rs = np.random.RandomState(77)
+    sizes, ws, ancs = [], [], []
+    for trial in range(30):
+        P = int(rs.randint(2, 400))
+        w = np.exp(rs.normal(0, rs.uniform(0.1, 8), P))
+        fs = core.FastSLAM([])
+        fs.particles = [core.FilterParticle() for _ in range(P)]
+        for i, (p, wi) in enumerate(zip(fs.particles, w)):
+            p.weight = float(wi)
+            p._idx = i
+        pyrandom.seed(trial)
+        fs.low_variance_resample()
+        sizes.append(P)
+        ws.append(w)
+        ancs.append([p._idx for p in fs.particles])
+    out["res_sizes"] = np.array(sizes, dtype=np.int64)
+    out["res_w"] = np.concatenate(ws)
+    out["res_anc"] = np.concatenate(ancs).astype(np.int64)
+    # (3) the new-landmark geometry: reading_distance_function, color_distance, cross_readings, ray_intersect on random readings
+    rs = np.random.RandomState(1)
+    rp = core.FilterParticle()
+    rp.potential_features = IterDict()
+
+    def reading():
+        st = Odometry()
+        st.pose.pose.position.x, st.pose.pose.position.y = rs.uniform(-5, 5, 2)
+        st.pose.pose.orientation = heading_to_quaternion(rs.uniform(-3, 3))
+        b = Blob()
+        b.bearing = rs.uniform(-3, 3)
+        b.color.r, b.color.g, b.color.b = rs.uniform(0, 255, 3)
+        return st, b
+
+    g = {k: [] for k in ("a", "b", "args", "dist", "colour", "cross", "ray", "ha", "hb")}
+    for i in range(1500):
+        a, b = reading(), reading()
+        x = rp.cross_readings(a, b)
+        args = (rs.uniform(-3, 3), rs.uniform(-3, 3), a[1].bearing, rs.uniform(-3, 3), rs.uniform(-3, 3), b[1].bearing)
+        for k, v in (("a", _reading_row(*a)), ("b", _reading_row(*b)), ("args", args),
+                     ("dist", rp.reading_distance_function(a[0], a[1], b[0], b[1])), ("colour", rp.color_distance(a[1], b[1])),
+                     ("cross", (float("nan"), float("nan")) if x is None else x), ("ray", float(rp.ray_intersect(*args))),
+                     ("ha", quaternion_to_heading(a[0].pose.pose.orientation)), ("hb", quaternion_to_heading(b[0].pose.pose.orientation))):
+            g[k].append(np.asarray(v, dtype=np.float64))
+    for k, v in g.items():
+        out["geo_" + k] = np.array(v)
+    # ... the bookkeeping: two orphans, then a promotion into potential_features
+    r1, r2, r3 = reading(), reading(), reading()
+    rp.add_hypothesis(*r1)
+    rp.add_hypothesis(*r2)
+    out["book_readings"] = np.array([_reading_row(*r) for r in (r1, r2, r3)])
+    out["book_hypotheses"] = np.array(sorted(rp.hypothesis_set), dtype=np.int64)
+    out["book_next_id"] = np.int64(rp.next_id)
+    rp.add_new_feature(1, *r3)
+    out["book_potential_keys"] = np.array(list(rp.potential_features), dtype=np.int64)
+    out["book_potential_covar"] = np.asarray(rp.potential_features[-3].covar, dtype=np.float64)
+    out["book_potential_mean"] = np.asarray(rp.potential_features[-3].mean, dtype=np.float64)
+    # ... find_nearest_reading over the stored readings of the reference's own unit test (test_prkt_ros2.py:228-274)
+    rp.potential_features.clear()
+    rp.potential_features[-1] = r1
+    rp.potential_features[-2] = r2
+    qs, found = [], []
+    for k in range(50):
+        q = reading()
+        qs.append(_reading_row(*q))
+        found.append(rp.find_nearest_reading(*q))
+    out["near_queries"] = np.array(qs)
+    out["near_found"] = np.array(found, dtype=np.int64)
+    return out
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     t0 = time.time()
+    np.savez_compressed(os.path.join(OUT, "reference_live.npz"), **gen_reference_live())
+    print("reference_live done", time.time() - t0)
+    if "--only-reference-live" in sys.argv:
+        return
     np.savez_compressed(os.path.join(OUT, "ka_triples.npz"), **gen_triples())
     print("ka_triples done", time.time() - t0)
     np.savez_compressed(os.path.join(OUT, "motion.npz"), **gen_motion())
