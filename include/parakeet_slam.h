@@ -415,6 +415,19 @@ int pk_timings(pk_filter* f, double ms[PK_T_COUNT], int64_t launches[PK_T_COUNT]
 /* Algorithmic HBM bytes of one observe launch (14 scalars read + 14 written per
  * particle.landmark) and the bytes the layout actually moves (adds update_count, ids). */
 int pk_observe_bytes(const pk_filter* f, int32_t num_blobs, int64_t* algorithmic, int64_t* moved);
+/* The colour table (options "colour_table": -1 auto (default), 0 off, 1 as auto; "colour_table_depth": levels, default 1024, read at the
+ * first scan in the mode behind a pk_upload_map; "colour_table_margin": levels short of the table's end at which the host leaves the
+ * mode, -1 (default) min(16, depth / 2), 0 never -- levels beyond the table are then worked out by the kernels themselves, exact and slow).
+ * While every map of the filter descends from one pk_upload_map, the colour covariance of a landmark is a function of (landmark,
+ * number of updates); the 512-lane publish / subscribe kernel of the 512 < L <= 2048 route then reads it from a shared table
+ * instead of streaming six rows per landmark in and out of every map slot (136 instead of 232 bytes per particle.landmark; `moved`
+ * of pk_observe_bytes says which).  The slots' colour rows are written back from the table whenever anything else reads them --
+ * every download (of the particles asked for), association and exchange sees what it always saw.  The mode ends (until the next pk_upload_map) with
+ * pk_upload_landmarks, pk_set_measurement_noise behind an update, pk_grow_enable, any shard / pack / adopt call, an observe on
+ * another route, or a landmark updated nearly as often as the table is deep.
+ * out[0] the last observe ran in the mode and nothing has ended it since, [1] the table's depth, [2] scans taken in the mode,
+ * [3] whole-buffer write-backs of the colour rows -- both since pk_create. */
+int pk_colour_table_stats(pk_filter* f, int64_t out[4]);
 /* Which kernels the last pk_observe / pk_step used for association + EKF update (instrumentation):
  * PK_ROUTE_NONE before the first call. */
 enum {

@@ -105,6 +105,7 @@ SIGNATURES = {
     "pk_reset_timings": (C.c_int, [_h]),
     "pk_timings": (C.c_int, [_h, _dp, _lp]),
     "pk_observe_bytes": (C.c_int, [_h, C.c_int32, _lp, _lp]),
+    "pk_colour_table_stats": (C.c_int, [_h, _lp]),
     "pk_observe_route": (C.c_int, [_h]),
     "pk_download_sources": (C.c_int, [_h, _ip]),
     "pk_observe_flagged": (C.c_int, [_h, _lp, _lp]),
@@ -465,6 +466,13 @@ class DeviceFilter(object):
         a = np.zeros(6, dtype=np.int64)
         check(self._lib.pk_observe_pub_stats(self._h, lptr(a)))
         return dict(zip(("entries", "contested_blobs", "multi_landmarks", "longest_list", "entry_capacity", "instance"), (int(v) for v in a)))
+
+    def colour_table_stats(self):
+        """The colour table (pk_colour_table_stats): dict of engaged (the last observe ran in the mode and nothing has ended it),
+        depth, scans (taken in the mode), materialisations (whole-buffer write-backs of the slots' colour rows)."""
+        a = np.zeros(4, dtype=np.int64)
+        check(self._lib.pk_colour_table_stats(self._h, lptr(a)))
+        return dict(zip(("engaged", "depth", "scans", "materialisations"), (int(v) for v in a)))
 
     # ---- new landmarks on the device (SURVEY 8 row f4; pk_grow_enable) ----
     def grow_enable(self, preset_landmarks, reading_capacity=64, pair_threshold=30.0):

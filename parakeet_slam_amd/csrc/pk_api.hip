@@ -16,6 +16,7 @@
 
 #include "../../include/parakeet_slam.h"
 #include "pk_kernels.hpp"
+#include "pk_pub_layout.hpp"
 
 using namespace pk;
 
@@ -176,6 +177,27 @@ struct pk_filter {
     int B = 0;
     bool reset = false;
   } split;
+  // The colour table (pk_colour.hpp): while every map descends from one pk_upload_map the colour block of a landmark is
+  // a function of (landmark, update count), and k_step_pub's 512-lane instances take it from ct_tab instead of streaming six rows per
+  // landmark in and out of every slot.  The slots' colour rows go stale then (colour_rows_valid) and are written back from the table
+  // whenever anything else wants them (ensure_colour_rows).
+  int colour_table = -1;          // option: -1 auto, 0 off, 1 as auto
+  int colour_table_depth = 1024;  // option: levels of the table
+  int colour_table_margin = -1;   // option: the host leaves the mode this many levels short of the table's end; -1: min(16, depth / 2); 0: never
+  bool ct_eligible = false;       // the maps came from pk_upload_map and nothing has ended the mode since
+  bool ct_updated = false;        // some observe has run since that upload
+  bool ct_sharded = false;        // a shard / pack / adopt call was made on this filter: never
+  bool ct_built = false;          // ct_tab holds the levels of ct_base under ct_qt
+  bool ct_scan = false;           // the observe in progress takes the table-mode kernel
+  bool ct_engaged = false;        // the last observe did, and nothing has ended the mode since
+  bool colour_rows_valid = true;
+  double* ct_base = nullptr;      // [6][Lp] the uploaded colour rows
+  double* ct_tab = nullptr;       // [ct_depth][6][Lp]
+  int ct_depth = 0;
+  NoiseD ct_qt{};
+  unsigned* ct_max_dev = nullptr; // the highest level a table-mode kernel has read since the upload
+  unsigned* ct_seen = nullptr;    // pinned host word: that figure, copied behind every table-mode scan (the last finished scan's, or the one before)
+  int64_t ct_scans = 0, ct_whole = 0;  // scans taken in the mode, whole-buffer materialisations
   bool adopt_local_done = false;  // pk_shard_adopt_local_dev made the new generation current; pk_shard_adopt_remote_dev may fill it
   int pub_ecap = 0;       // k_step_pub was prepared for the current scan with this many publish entries (0: not prepared)
   int split_reserve_cus = 16;  // CUs the first part of a split step leaves free for the all-to-all's kernels
@@ -393,6 +415,105 @@ int materialise(pk_filter* f) {
   f->d.alt = nullptr;  // every slot now lives in the shard's own buffer
   return PK_OK;
 }
+
+// ---- the colour table's host side
+ColourTable ct_view(const pk_filter* f) { return ColourTable{f->ct_tab, f->ct_depth}; }
+// The slots of the live buffer get their colour rows back (no-op while they are valid).  Called at the top of every entry point that
+// reads colour rows of slots or hands them out.
+int ensure_colour_rows(pk_filter* f) {
+  if (f->colour_rows_valid) return PK_OK;
+  {
+    Span t(f, PK_T_MATERIALISE);
+    launch_colour_rows(f->stream, f->d, ct_view(f), f->ct_qt);
+  }
+  PK_LAUNCH_CHECK("ensure_colour_rows");
+  f->colour_rows_valid = true;
+  f->ct_whole += 1;
+  return PK_OK;
+}
+// A download of some particles' maps: only their slots get their rows (behind materialise: slot p is particle p's), and the rest of
+// the buffer stays as stale as it was -- a caller that looks at one particle every step does not pay for all of them.
+int colour_rows_for_download(pk_filter* f, int64_t p0, int64_t p1) {
+  if (f->colour_rows_valid || p0 >= p1) return PK_OK;
+  if (p0 == 0 && p1 == f->d.P) return ensure_colour_rows(f);
+  {
+    Span t(f, PK_T_MATERIALISE);
+    launch_colour_rows(f->stream, f->d, ct_view(f), f->ct_qt, nullptr, nullptr, p0, p1);
+  }
+  PK_LAUNCH_CHECK("colour_rows_for_download");
+  return PK_OK;
+}
+// ... and the mode stays off until the next pk_upload_map
+int ct_end(pk_filter* f) {
+  f->ct_eligible = false;
+  f->ct_scan = false;
+  f->ct_engaged = false;
+  return ensure_colour_rows(f);
+}
+// Does this observe take the table-mode kernel?  (The conditions under which onepass_prepare / onepass_launch hand the scan to
+// k_step_pub's 512-lane instances, with pruned lists: a scan that kernel stands back from then goes to the general kernels as a
+// whole, behind k_colour_rows, and never to k_step_regs.)
+bool ct_scan_ok(const pk_filter* f, const AssocLaunch& al, int B) {
+  if (f->colour_table == 0 || !f->ct_eligible || f->ct_sharded || f->grow_on || f->dense || !f->ct_base) return false;
+  if (!al.regs || al.fused || al.big) return false;
+  if (!f->cand_lists || !f->pub_step || !f->far_prune) return false;
+  if (f->d.lay.Lp <= 2 * kPubSmallThreads || f->d.lay.L > kRegsMaxL) return false;
+  if (regs_cand_lds_bytes(f->d.lay.Lp, B) > kMaxDynLds || step_pub_entry_capacity(B) <= 0) return false;
+  // beyond the table's end the kernel runs the recurrence itself, lane by lane (exact, slow): the host leaves the mode before the
+  // levels it knows of get there (colour_table_margin = 0: never -- the kernel's own handling carries every scan)
+  const int margin = f->colour_table_margin >= 0 ? f->colour_table_margin : std::min(16, f->ct_depth > 0 ? f->ct_depth / 2 : 16);
+  if (margin > 0 && f->ct_built && f->ct_seen && (int64_t)*reinterpret_cast<volatile unsigned*>(f->ct_seen) + margin >= f->ct_depth) return false;
+  return true;
+}
+// The table is allocated and built when the mode first engages on a map (built again if Qt changed before any update); the depth is
+// the option's value at that first scan, and holds until the next pk_upload_map
+int ct_engage(pk_filter* f) {
+  int rc;
+  const int Lp = f->d.lay.Lp;
+  const int depth = f->ct_built ? f->ct_depth : f->colour_table_depth;
+  if (!f->ct_seen) {
+    PK_HIP(hipHostMalloc((void**)&f->ct_seen, 64, hipHostMallocDefault));
+    *f->ct_seen = 0u;
+  }
+  if (!f->ct_max_dev && (rc = dev_alloc(f, &f->ct_max_dev, 16))) return rc;
+  const bool same_qt = memcmp(&f->ct_qt, &f->qt, sizeof(NoiseD)) == 0;
+  if (f->ct_built && same_qt && f->ct_depth == depth) return PK_OK;
+  if (!f->ct_tab || f->ct_depth != depth) {
+    PK_HIP(hipStreamSynchronize(f->stream));
+    if (f->ct_tab) {
+      (void)hipFree(f->ct_tab);
+      f->device_bytes -= (int64_t)((size_t)f->ct_depth * 6 * Lp * sizeof(double));
+      f->ct_tab = nullptr;
+    }
+    if ((rc = dev_alloc(f, &f->ct_tab, (size_t)depth * 6 * Lp))) return rc;
+    f->ct_depth = depth;
+  }
+  f->ct_qt = f->qt;
+  launch_colour_table(f->stream, f->ct_base, f->ct_tab, depth, Lp, f->ct_qt);
+  PK_HIP(hipMemsetAsync(f->ct_max_dev, 0, 16, f->stream));
+  *f->ct_seen = 0u;
+  PK_LAUNCH_CHECK("colour table");
+  f->ct_built = true;
+  return PK_OK;
+}
+
+// shard / pack / adopt entry points: the slots get their rows back, and the mode is never taken on this filter again
+int ct_shard_call(pk_filter* f) {
+  f->ct_sharded = true;
+  if (f->colour_rows_valid) {
+    f->ct_eligible = false;
+    f->ct_engaged = false;
+    return PK_OK;
+  }
+  int rc;
+  if ((rc = use_device(f))) return rc;
+  return ct_end(f);
+}
+#define PK_CT_SHARD_CALL(f_)                      \
+  if (f_) {                                       \
+    const int rcc_ = ct_shard_call(f_);           \
+    if (rcc_) return rcc_;                        \
+  }
 
 // Pack one landmark (dense 5x5 host form) into the compact fields of a host slot image.
 void pack_landmark(const MapLayout& lay, unsigned char* slot, int l, const double* mean, const double* cov) {
@@ -766,6 +887,7 @@ int enqueue_association(pk_filter* f, const double* blobs, int B, bool finalize,
       fh = f->fh;
       fh.n_flagged = ctl_n_flagged(f);
     }
+    if ((rc = ct_end(f))) return rc;  // (the general association reads the slots' colour rows)
     Span t(f, PK_T_ASSOC);
     CandTable cand;
     if (fh.lmpass && f->cand_lists && f->d.lay.L < 65535) {
@@ -794,6 +916,7 @@ int enqueue_association(pk_filter* f, const double* blobs, int B, bool finalize,
     return fail(PK_ERR_UNSUPPORTED,
                 "maximum-likelihood association of %d blobs: neither the colour-grid tables nor the brute-force kernel's "
                 "%zu bytes of per-blob state fit the workgroup's %zu bytes of LDS", B, assoc_brute_lds_bytes(B), (size_t)kMaxDynLds);
+  if ((rc = ct_end(f))) return rc;
   Span t(f, PK_T_ASSOC);
   launch_assoc_brute(f->stream, f->d, blobs_dev, dir_dev, B, f->ids_dev);
   return PK_OK;
@@ -866,6 +989,7 @@ int relayout(pk_filter* f, bool dense, bool keep) {
     }
     if ((rc = pk_download_landmarks(f, 0, P, means.data(), covs.data(), counts.data()))) return rc;
   }
+  if ((rc = ct_end(f))) return rc;  // (the buffers go: nothing left to write rows into)
   PK_HIP(hipStreamSynchronize(f->stream));
   for (int i = 0; i < 2; ++i) {
     if (d.map[i]) (void)hipFree(d.map[i]);
@@ -1032,6 +1156,9 @@ int pk_destroy(pk_filter* f) {
     if (f->stage_done[i]) (void)hipEventDestroy(f->stage_done[i]);
   }
   if (f->retry_seen) (void)hipHostFree(f->retry_seen);
+  for (void* q : {(void*)f->ct_base, (void*)f->ct_tab, (void*)f->ct_max_dev})
+    if (q) (void)hipFree(q);
+  if (f->ct_seen) (void)hipHostFree(f->ct_seen);
   if (f->own_stream) (void)hipStreamDestroy(f->own_stream);
   delete f;
   return PK_OK;
@@ -1075,6 +1202,8 @@ int pk_set_measurement_noise(pk_filter* f, const double Qt[16]) {
       if (fabs(Qt[i * 4 + j] - Qt[j * 4 + i]) > 1e-9 * (scale > 0 ? scale : 1.0)) coupled = true;
   int rc;
   if ((rc = use_device(f))) return rc;
+  // (the table's levels were made under the old Qt: once an update has used them the mode ends; before that the table is built afresh)
+  if (f->ct_updated && (rc = ct_end(f))) return rc;
   if (coupled && !f->dense && (rc = relayout(f, true, f->map_loaded))) return rc;
   for (int i = 0; i < 16; ++i) f->qt16[i] = Qt[i];
   f->qt_dense = coupled;
@@ -1107,6 +1236,19 @@ int pk_upload_map(pk_filter* f, const double* means, const double* covs, const u
   PK_HIP(hipMemcpyAsync(f->slot_tmp, slot.data(), lay.slot_bytes, hipMemcpyHostToDevice, f->stream));
   PK_HIP(hipMemcpyAsync(f->d.immutable, imm.data(), imm.size(), hipMemcpyHostToDevice, f->stream));
   launch_broadcast_slot(f->stream, f->d, f->slot_tmp);
+  // every particle holds this map with update counts 0: the colour table's level 0 (the 512-lane publish / subscribe route only)
+  f->colour_rows_valid = true;  // (every slot of the live buffer was just rewritten)
+  f->ct_scan = false;
+  f->ct_engaged = false;
+  f->ct_built = false;
+  f->ct_updated = false;
+  f->ct_eligible = false;
+  if (!f->dense && lay.Lp > 2 * kPubSmallThreads && L <= kRegsMaxL) {
+    if (!f->ct_base && (rc = dev_alloc(f, &f->ct_base, (size_t)6 * lay.Lp))) return rc;
+    PK_HIP(hipMemcpyAsync(f->ct_base, slot.data() + (size_t)F_CRR * lay.Lp * sizeof(double), (size_t)6 * lay.Lp * sizeof(double),
+                          hipMemcpyHostToDevice, f->stream));
+    f->ct_eligible = true;
+  }
   PK_HIP(hipStreamSynchronize(f->stream));  // host staging buffers die here
   f->src_identity = true;
   f->map_loaded = true;
@@ -1197,6 +1339,7 @@ int pk_download_landmarks(pk_filter* f, int64_t p0, int64_t p1, double* means, d
   int rc;
   if ((rc = use_device(f))) return rc;
   if ((rc = materialise(f))) return rc;
+  if ((rc = colour_rows_for_download(f, p0, p1))) return rc;  // (the colour table's mode goes on)
   const MapLayout& lay = f->d.lay;
   const int L = lay.L;
   const int64_t chunk = std::max<int64_t>(1, (int64_t)(64u << 20) / (int64_t)lay.slot_bytes);
@@ -1226,6 +1369,7 @@ int pk_upload_landmarks(pk_filter* f, int64_t p0, int64_t p1, const double* mean
   if (!f->map_loaded) return fail(PK_ERR_STATE, "pk_upload_landmarks: no map uploaded");
   int rc;
   if ((rc = use_device(f))) return rc;
+  if ((rc = ct_end(f))) return rc;  // (a particle's map edited by hand: its colour blocks are no longer the table's)
   if ((rc = materialise(f))) return rc;
   const int L = f->d.lay.L;
   // finite means and covariances whatever the layout (as pk_upload_map checks them); the layout decision only while compact
@@ -1490,7 +1634,7 @@ static int onepass_prepare(pk_filter* f, const AssocLaunch& al, int B, CandTable
     if (ecap > 0) {  // candidate lists both ways, and the publish table's layout
       uint4* far = f->far_prune ? f->far_dev : nullptr;
       launch_candidates(f->stream, f->d, B, al.exact, ref, f->cand_dev, ctl_cand_over(f), f->bcnt_dev, f->brec_dev, ctl_n_stray(f),
-                        kCandSlots, f->out4, f->npass_dev, far, part);
+                        kCandSlots, f->out4, f->npass_dev, far, part, f->ct_scan ? ct_view(f) : ColourTable(), &f->ct_qt);
       // (the flags are folded where no stand-by kernel takes a scan k_step_pub leaves: pruned lists, growing maps, maps of at most 512 landmarks)
       const bool fold = whole && (far != nullptr || f->grow_on || al.fused);
       launch_cand_entries(f->stream, f->d, B, f->cand_dev, f->erec_dev, f->bcnt_dev, f->brec_dev, f->binfo_dev, f->glist_dev, ctl_cand_over(f),
@@ -1527,6 +1671,11 @@ static int onepass_launch(pk_filter* f, const AssocLaunch& al, int B, const Obse
     // a scan the kernel stood back from (a list overflowed, the table did not fit): every particle to the fall-back kernels
     if (!f->flag_folded) launch_flag_range_if(f->stream, ctl_skip_pub(f), fh.pflag, fh.n_flagged, p0, p1);
   } else if (al.regs) {
+    if (f->ct_scan) {
+      e1.ctab = f->ct_tab;
+      e1.ctab_depth = f->ct_depth;
+      e1.ctab_max = f->ct_max_dev;
+    }
     if (f->pub_ecap > 0 && cand.rec)
       launch_step_pub(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev, f->glist_dev, ctl_skip_pub(f), f->pub_ecap,
                       p0, p1, reserve_cus);
@@ -1626,10 +1775,12 @@ static int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int3
   if (grow && f->dense)
     return fail(PK_ERR_STATE, "pk_observe: the new-landmark bookkeeping (pk_grow_enable) writes the compact landmark layout; this filter "
                               "is on the dense one (a covariance or Qt that couples position and colour)");
+  f->ct_updated = true;
   if (f->dense) return dense_observe(f, blobs, B, ids, ids_out, reset, true);
   ObserveExtras ex;
   ex.reset = reset;
   if (ids) {
+    if ((rc = ct_end(f))) return rc;  // (another route: k_observe streams whole slots)
     f->staged.valid = false;  // a staged ML scan does not survive another observe
     // block: ctl | blobs (4B doubles) | first (Lp int32) | next (B int32)
     const size_t o_blobs = kCtlBytes;
@@ -1686,6 +1837,9 @@ static int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int3
   AssocLaunch al;
   // (ids wanted: the association kernel + k_observe; growing maps: a publish / subscribe kernel, or that)
   if ((rc = enqueue_association(f, blobs, B, false, ids_out == nullptr, &al, grow))) return rc;
+  // the colour table's mode: this scan takes the table-mode kernel, or the mode ends here (the slots get their colour rows first)
+  f->ct_scan = ct_scan_ok(f, al, B);
+  if (f->ct_scan ? (rc = ct_engage(f)) : (rc = ct_end(f))) return rc;
   f->grow_bits = false;
   if (grow && (al.fused || al.regs || al.big)) {
     // round 6: the one-pass kernel leaves every particle's unmatched blobs as a bit row (scan order); no second chance -- what it
@@ -1715,8 +1869,22 @@ static int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int3
   if (al.fused || al.regs || al.big) {
     CandTable cand;
     if ((rc = onepass_prepare(f, al, B, &cand, 0, true))) return rc;
+    // (ct_scan_ok restates what sends the scan to k_step_pub; should the two ever part, the scan simply leaves the mode)
+    if (f->ct_scan && !(f->pub_ecap > 0 && cand.rec && cand.far) && (rc = ct_end(f))) return rc;
     if ((rc = onepass_launch(f, al, B, ex, cand, 0, f->d.P))) return rc;
+    if (f->ct_scan) {
+      // what the kernel handed on (or the whole scan, where it stood back) goes to kernels that read whole slots: the SOURCE slots of
+      // those particles get their colour rows from the table first -- a launch that returns in its first wave on the usual scan
+      Span t(f, PK_T_ASSOC);
+      launch_colour_rows(f->stream, f->d, ct_view(f), f->ct_qt, f->fh.pflag, ctl_n_flagged(f));
+      (void)hipMemcpyAsync(f->ct_seen, f->ct_max_dev, sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
+      (void)hipGetLastError();
+      f->colour_rows_valid = false;
+      f->ct_engaged = true;
+      f->ct_scans += 1;
+    }
     if ((rc = onepass_finish(f, al, B, ex, cand))) return rc;
+    f->ct_scan = false;
   } else {
     Span t(f, PK_T_OBSERVE);
     if (al.fast) {
@@ -1809,6 +1977,8 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
   if (f->grow_on) return fail(PK_ERR_STATE, "pk_observe_staged_range: the new-landmark bookkeeping (pk_grow_enable) runs behind whole observes (pk_observe / pk_observe_staged)");
   int rc;
   if ((rc = use_device(f))) return rc;
+  if ((rc = ct_end(f))) return rc;  // (ranged observes: another route)
+  f->ct_updated = true;
   pk_filter::Split& sp = f->split;
   if (first) {
     if (sp.active) return fail(PK_ERR_STATE, "pk_observe_staged_range: the previous split observe was not finished (last = 1)");
@@ -1869,7 +2039,14 @@ int pk_associate(pk_filter* f, const double* blobs, int32_t B, int32_t* ids_out)
   for (int i = 0; i < 4 * B; ++i)
     if (!std::isfinite(blobs[i])) return fail(PK_ERR_INVALID, "pk_associate: blob %d is not finite", i / 4);
   if (f->dense) return dense_observe(f, blobs, B, nullptr, ids_out, false, false);
-  if ((rc = enqueue_association(f, blobs, B, true, false, nullptr))) return rc;
+  if ((rc = ensure_colour_rows(f))) return rc;  // (the colour table's mode goes on: nothing is updated)
+  {
+    const bool keep = f->ct_eligible, engaged = f->ct_engaged;  // (enqueue_association ends the mode where it launches the general association)
+    rc = enqueue_association(f, blobs, B, true, false, nullptr);
+    f->ct_eligible = keep;
+    f->ct_engaged = engaged;
+  }
+  if (rc) return rc;
   PK_LAUNCH_CHECK("pk_associate");
   PK_HIP(hipMemcpyAsync(ids_out, f->ids_dev, (size_t)f->d.P * B * 4, hipMemcpyDeviceToHost, f->stream));
   PK_HIP(hipStreamSynchronize(f->stream));
@@ -1963,6 +2140,25 @@ int pk_set_option(pk_filter* f, const char* name, int64_t value) {
   if (!strcmp(name, "regs_warm")) {
     if (value < 0 || value > 2) return fail(PK_ERR_INVALID, "regs_warm: 0 (off), 1 (mean rows) or 2 (whole slot)");
     f->regs_warm = (int)value;
+    return PK_OK;
+  }
+  if (!strcmp(name, "colour_table")) {
+    if (value < -1 || value > 1) return fail(PK_ERR_INVALID, "colour_table: -1 (auto), 0 (off) or 1 (as auto)");
+    f->colour_table = (int)value;
+    if (value == 0 && !f->colour_rows_valid) {  // (switched off in mid-run: the slots get their rows back)
+      int rc;
+      if ((rc = use_device(f)) || (rc = ct_end(f))) return rc;
+    }
+    return PK_OK;
+  }
+  if (!strcmp(name, "colour_table_depth")) {
+    if (value < 8 || value > 32768) return fail(PK_ERR_INVALID, "colour_table_depth: 8 .. 32768 levels (the table stays below 4 GB: 32-bit offsets)");
+    f->colour_table_depth = (int)value;  // (takes effect when the table is next built: at the first table-mode scan behind a pk_upload_map)
+    return PK_OK;
+  }
+  if (!strcmp(name, "colour_table_margin")) {
+    if (value < -1 || value > 32768) return fail(PK_ERR_INVALID, "colour_table_margin: -1 (auto), 0 (the host never leaves the mode for the table's end) or levels");
+    f->colour_table_margin = (int)value;
     return PK_OK;
   }
   if (!strcmp(name, "assoc_dup")) {
@@ -2098,6 +2294,7 @@ int pk_grow_enable(pk_filter* f, int32_t preset_landmarks, int32_t reading_capac
                               "(a covariance or Qt that couples position and colour)");
   int rc;
   if ((rc = use_device(f))) return rc;
+  if ((rc = ct_end(f))) return rc;  // (growing maps: spare slots get colour blocks of their own)
   GrowState& g = f->grow;
   g.L0 = preset_landmarks;
   g.S = L - preset_landmarks;
@@ -2189,6 +2386,7 @@ int pk_shard_block_totals(pk_filter* f, double gmax, int32_t weight_domain, doub
 }
 
 int pk_set_shard(pk_filter* f, int64_t global_offset) {
+  PK_CT_SHARD_CALL(f);
   if (!f || global_offset < 0) return fail(PK_ERR_INVALID, "pk_set_shard: bad argument");
   f->d.global_offset = global_offset;
   return PK_OK;
@@ -2232,6 +2430,7 @@ static size_t record_stride(const pk_filter* f) { return kPoseRecordBytes + f->d
 int64_t pk_particle_bytes(const pk_filter* f) { return f ? (int64_t)record_stride(f) : -1; }
 
 int pk_pack_particles(pk_filter* f, const int64_t* local_idx, int64_t n, void* dev_buf) {
+  PK_CT_SHARD_CALL(f);
   if (!f || n < 0 || (n > 0 && (!local_idx || !dev_buf))) return fail(PK_ERR_INVALID, "pk_pack_particles: bad argument");
   // (pk_particle_bytes() counts the bookkeeping's tail, k_pack writes records without one -- and pk_adopt_particles
   // would leave readings and id counters on the wrong particles)
@@ -2253,6 +2452,7 @@ int pk_pack_particles(pk_filter* f, const int64_t* local_idx, int64_t n, void* d
 }
 
 int pk_adopt_particles(pk_filter* f, const int64_t* src, const void* dev_buf, int64_t n_received) {
+  PK_CT_SHARD_CALL(f);
   if (f) f->pose_part_ok = false;  // (the poses change: the motion launch's pose sums are no longer theirs)
   if (!f || !src || n_received < 0 || (n_received > 0 && !dev_buf)) return fail(PK_ERR_INVALID, "pk_adopt_particles: bad argument");
   if (f->grow_on) return fail(PK_ERR_STATE, "pk_adopt_particles: the new-landmark bookkeeping (pk_grow_enable) travels with the balanced placement only (pk_shard_*_balanced_dev)");
@@ -2399,6 +2599,7 @@ int pk_shard_download_offspring(pk_filter* f, int64_t* slot_hi) {
 }
 
 int pk_shard_pack_dev(pk_filter* f, const int64_t* ranges, int32_t world, int32_t rank, void* dev_buf) {
+  PK_CT_SHARD_CALL(f);
   if (f && f->grow_on) return fail(PK_ERR_STATE, "pk_shard_pack_dev: the new-landmark bookkeeping (pk_grow_enable) travels with the balanced placement only (pk_shard_*_balanced_dev)");
   if (!f || !ranges || world < 1 || rank < 0 || rank >= world) return fail(PK_ERR_INVALID, "pk_shard_pack_dev: bad argument");
   if (!f->hi_dev) return fail(PK_ERR_STATE, "pk_shard_pack_dev: call pk_shard_plan_dev first");
@@ -2421,6 +2622,7 @@ int pk_shard_pack_dev(pk_filter* f, const int64_t* ranges, int32_t world, int32_
 }
 
 int pk_shard_pack_slots_dev(pk_filter* f, int64_t j0, int64_t j1, int64_t slot_lo, int64_t slot_hi, void* dev_buf) {
+  PK_CT_SHARD_CALL(f);
   if (f && f->grow_on) return fail(PK_ERR_STATE, "pk_shard_pack_slots_dev: the new-landmark bookkeeping (pk_grow_enable) travels with the balanced placement only (pk_shard_*_balanced_dev)");
   if (!f || j0 < 0 || j1 < j0 || j1 > f->d.P || slot_hi < slot_lo) return fail(PK_ERR_INVALID, "pk_shard_pack_slots_dev: bad argument");
   if (!f->hi_dev) return fail(PK_ERR_STATE, "pk_shard_pack_slots_dev: call pk_shard_plan_dev first");
@@ -2434,6 +2636,7 @@ int pk_shard_pack_slots_dev(pk_filter* f, int64_t j0, int64_t j1, int64_t slot_l
 }
 
 int pk_shard_adopt_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t n_received) {
+  PK_CT_SHARD_CALL(f);
   if (f && f->grow_on) return fail(PK_ERR_STATE, "pk_shard_adopt_dev: the new-landmark bookkeeping (pk_grow_enable) travels with the balanced placement only (pk_shard_*_balanced_dev)");
   if (f) f->pose_part_ok = false;  // (the poses change: the motion launch's pose sums are no longer theirs)
   if (!f || rank < 0 || n_received < 0 || (n_received > 0 && !dev_recv)) return fail(PK_ERR_INVALID, "pk_shard_adopt_dev: bad argument");
@@ -2462,6 +2665,7 @@ int pk_shard_adopt_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t
 }
 
 int pk_shard_adopt_local_dev(pk_filter* f, int32_t rank) {
+  PK_CT_SHARD_CALL(f);
   if (f && f->grow_on) return fail(PK_ERR_STATE, "pk_shard_adopt_local_dev: the new-landmark bookkeeping (pk_grow_enable) travels with the balanced placement only (pk_shard_*_balanced_dev)");
   if (f) f->pose_part_ok = false;  // (the poses change: the motion launch's pose sums are no longer theirs)
   if (!f || rank < 0) return fail(PK_ERR_INVALID, "pk_shard_adopt_local_dev: bad argument");
@@ -2484,6 +2688,7 @@ int pk_shard_adopt_local_dev(pk_filter* f, int32_t rank) {
 }
 
 int pk_shard_adopt_remote_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t n_received) {
+  PK_CT_SHARD_CALL(f);
   if (f && f->grow_on) return fail(PK_ERR_STATE, "pk_shard_adopt_remote_dev: the new-landmark bookkeeping (pk_grow_enable) travels with the balanced placement only (pk_shard_*_balanced_dev)");
   if (f) f->pose_part_ok = false;  // (the poses change: the motion launch's pose sums are no longer theirs)
   if (!f || rank < 0 || n_received < 0 || (n_received > 0 && !dev_recv)) return fail(PK_ERR_INVALID, "pk_shard_adopt_remote_dev: bad argument");
@@ -2683,6 +2888,7 @@ static int balanced_row_check(const int64_t* table, int world, int64_t P, const 
 }
 
 int pk_shard_pack_balanced_dev(pk_filter* f, const int64_t* table, int32_t world, int32_t rank, void* dev_buf) {
+  PK_CT_SHARD_CALL(f);
   if (!f || !table || world < 1 || world > 64 || rank < 0 || rank >= world) return fail(PK_ERR_INVALID, "pk_shard_pack_balanced_dev: bad argument");
   if (!f->bal.rel || !f->d.logical[0]) return fail(PK_ERR_STATE, "pk_shard_pack_balanced_dev: call pk_shard_plan_balanced_dev first");
   int rc;
@@ -2712,6 +2918,7 @@ int pk_shard_pack_balanced_dev(pk_filter* f, const int64_t* table, int32_t world
  * ITSELF -- the children from position `keep` on, destined for its own slots [keep, P): what k_bal_pack writes for another rank whose
  * free slots are [keep, P), with the 64-byte balanced header (and the new-landmark bookkeeping behind the map while that is on). */
 int pk_shard_pack_balanced_loop_dev(pk_filter* f, int64_t keep, int64_t a0, int64_t a1, void* dev_buf) {
+  PK_CT_SHARD_CALL(f);
   if (!f || keep < 0 || keep > f->d.P || a0 < 0 || a1 < a0 || a1 > f->d.P || (a1 > a0 && !dev_buf))
     return fail(PK_ERR_INVALID, "pk_shard_pack_balanced_loop_dev: bad argument");
   if (!f->bal.rel || !f->d.logical[0]) return fail(PK_ERR_STATE, "pk_shard_pack_balanced_loop_dev: call pk_shard_plan_balanced_dev first");
@@ -2728,6 +2935,7 @@ int pk_shard_pack_balanced_loop_dev(pk_filter* f, int64_t keep, int64_t a0, int6
 
 int pk_shard_adopt_balanced_dev(pk_filter* f, const int64_t* table, int32_t world, int32_t rank, const void* dev_recv,
                                 int64_t n_received, int32_t mode) {
+  PK_CT_SHARD_CALL(f);
   if (f) f->pose_part_ok = false;
   if (!f || !table || world < 1 || world > 64 || rank < 0 || rank >= world || n_received < 0 || mode < 0 || mode > 2 ||
       (n_received > 0 && !dev_recv))
@@ -2965,7 +3173,18 @@ int pk_observe_bytes(const pk_filter* f, int32_t B, int64_t* algorithmic, int64_
   if (!f) return fail(PK_ERR_INVALID, "pk_observe_bytes: NULL handle");
   const int64_t P = f->d.P, L = f->d.lay.L;
   if (algorithmic) *algorithmic = P * L * 28 * (int64_t)sizeof(double);  // 14 read + 14 written
-  if (moved) *moved = P * (L * (28 * (int64_t)sizeof(double) + 8) + (int64_t)B * 32);
+  // (the colour table's mode: eight rows and the count each way, 136 B per particle.landmark instead of 232)
+  const int64_t rows = f->ct_engaged ? 16 : 28;
+  if (moved) *moved = P * (L * (rows * (int64_t)sizeof(double) + 8) + (int64_t)B * 32);
+  return PK_OK;
+}
+
+int pk_colour_table_stats(pk_filter* f, int64_t out[4]) {
+  if (!f || !out) return fail(PK_ERR_INVALID, "pk_colour_table_stats: NULL argument");
+  out[0] = f->ct_engaged ? 1 : 0;
+  out[1] = f->ct_built ? f->ct_depth : f->colour_table_depth;
+  out[2] = f->ct_scans;
+  out[3] = f->ct_whole;
   return PK_OK;
 }
 

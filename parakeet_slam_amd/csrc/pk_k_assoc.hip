@@ -2,6 +2,7 @@
 //
 // Hand-written gfx950 (CDNA4, wave64) kernels of the FastSLAM particle update; see DESIGN.md
 // section 4.  No MFMA: the algebra is 2x2 / 3x3 and register resident (pk_math.hpp).
+#include "pk_colour.hpp"
 #include "pk_device.hpp"
 #include "pk_pub_math.hpp"
 
@@ -723,6 +724,7 @@ void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& gri
 struct CandArgs {
   SlotSource ss;
   const int32_t* src;
+  size_t count_off;
   const double *x, *y, *h;
   const double* exact;  // [B][6] in cell order: bearing, r, g, b, ux, uy
   uint4* rec;           // [Lp][2] (SLOTS = kCandSlots) or [Lp][3] (twice as many)
@@ -741,6 +743,9 @@ struct CandArgs {
   uint4* far;            // [Lp + kCandSpare][1 + SLOTS / 8] out, or NULL: (Kb, Ib as float, entries of the far list, 0) | the FAR list --
                          // look-alikes whose key is certainly beyond the underflow edge for every particle whose own bound is at
                          // least (Kb, Ib) leave the landmark's list (pk_pub_math.hpp); NULL: nothing is taken off
+  const double* ctab;    // table mode (pk_colour.hpp): the reference's colour blocks come from the table -- its slot's rows may be stale --, or NULL
+  int ctab_depth;
+  Noise<double> qt;
 };
 
 constexpr int kCandThreads = 1024;  // 64 landmarks x 16 waves that share the scan's blobs
@@ -792,6 +797,15 @@ __global__ void __launch_bounds__(kCandThreads) k_candidates(CandArgs a) {
   float kbf = -3.0e38f, ibf = 0.f;
   if (has && a.far) {
     Landmark<double> lm = load_landmark_nocount(f, a.Lp, l);
+    if (a.ctab) {  // (kernel-uniform)
+      const Sym3<double> C = colour_block_at(a.ctab, a.ctab_depth, a.Lp, l, colour_level(reinterpret_cast<const int*>(slot + a.count_off)[l]), a.qt);
+      lm.crr = C.a;
+      lm.crg = C.b;
+      lm.crb = C.c;
+      lm.cgg = C.d;
+      lm.cgb = C.e;
+      lm.cbb = C.f;
+    }
     double fk, fi;
     pub_far_bound(lm, fk, fi);
     if (fi > 0.0 && fk == fk && fabs(fk) < 1e30) {  // (fi > 0: sane determinants, a positive definite colour block)
@@ -897,7 +911,8 @@ __global__ void __launch_bounds__(kCandThreads) k_candidates(CandArgs a) {
 
 void launch_candidates(hipStream_t s, DeviceState& d, int B, const double* exact_dev, int64_t ref_particle, uint4* rec_dev,
                        unsigned* over_dev, unsigned* bcnt_dev, uint4* brec_dev, unsigned* stray_dev, int slots,
-                       const double* pose_sums4_dev, unsigned char* npass_dev, uint4* far_dev, const double* pose_part_dev) {
+                       const double* pose_sums4_dev, unsigned char* npass_dev, uint4* far_dev, const double* pose_part_dev,
+                       const ColourTable& ct, const NoiseD* qt) {
   if (d.P == 0 || d.lay.Lp == 0) return;
   // (inverse lists as wide as the lists themselves: brec_dev holds B x slots u16.  bcnt_dev is all 0 and brec_dev all 0xFF when
   // this is called: cleared at their allocation, and again by k_cand_entries behind its last read of them -- two memset
@@ -921,6 +936,10 @@ void launch_candidates(hipStream_t s, DeviceState& d, int B, const double* exact
   a.n_part = motion_pose_blocks(d.P);
   a.npass = npass_dev;
   a.far = far_dev;
+  a.count_off = d.lay.count_off;
+  a.ctab = qt ? ct.tab : nullptr;
+  a.ctab_depth = ct.depth;
+  a.qt = qt ? make_noise(qt->q00, qt->rr, qt->rg, qt->rb, qt->gg, qt->gb, qt->bb) : Noise<double>{};
   a.P = d.P;
   a.L = d.lay.L;
   a.Lp = d.lay.Lp;

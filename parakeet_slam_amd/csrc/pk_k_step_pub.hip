@@ -44,6 +44,7 @@
 // copy of a candidate's bearing and colour, look-alikes beyond the underflow edge take no slot, the publish table is rank-major.
 #include <type_traits>
 
+#include "pk_colour.hpp"
 #include "pk_device.hpp"
 #include "pk_pub_math.hpp"
 #include "pk_pub_layout.hpp"
@@ -98,6 +99,9 @@ struct PubArgs {
   const unsigned* stats;        // [4] k_cand_entries' figures of this scan: [0] the entries of its publish table, [3] its longest list
   int tbytes;                   // bytes of LDS the publish table and the overflow area share
   const uint4* prim;            // the two-pass kernels: every landmark's primary blob in landmark order (prim_table_uint4), or null
+  const double* ctab = nullptr; // table mode (k_step_pub<NP, 512, true>; pk_colour.hpp): the colour table [depth][6][Lp], else null
+  unsigned* ctab_max = nullptr; //   out: the highest level a lane read (one atomic per workgroup)
+  int ctab_depth = 0;
   unsigned* unm;                // growing maps (section 8(f4)): out [P][unm_words], bit b of a particle's row = blob b (SCAN order) is matched by
   int unm_words;                //   none of its landmarks (:92-95: k_new_landmarks takes those through add_hypothesis), or null
 };
@@ -875,6 +879,9 @@ __device__ __forceinline__ void pub_fold_norms(double& acc, double& prod, bool l
 #endif
 }
 // The blobs taken, applied in scan order (:88): regs_apply with the take bits.
+// TAB (the colour table stands for the slots' colour rows): a landmark's ONLY update of the scan leaves its colour block alone -- the
+// kernel does not store it; a landmark that takes several blobs carries the block from update to update in registers as ever
+template <bool TAB = false>
 __device__ __forceinline__ double pub_apply(const PubSlots& q, const double* ex, const unsigned short* order, const Noise<double>& qt,
                                             Landmark<double>& lm, bool imm, double sx, double sy, double pse, double* prod = nullptr) {
   double acc = 0.0;
@@ -888,7 +895,7 @@ __device__ __forceinline__ double pub_apply(const PubSlots& q, const double* ex,
       const double2 z01 = *reinterpret_cast<const double2*>(rec);
       const double2 z23 = *reinterpret_cast<const double2*>(rec + 2);
       BlobT<double> z{z01.x, z01.y, z23.x, z23.y};
-      acc = ekf_update(lm, sx, sy, z, qt, imm, (EkfAux<double>*)nullptr, &pse, prod);
+      acc = ekf_update<double, !TAB>(lm, sx, sy, z, qt, imm, (EkfAux<double>*)nullptr, &pse, prod);
     }
     return acc;
   }
@@ -1061,8 +1068,13 @@ __device__ __forceinline__ int64_t pub_walk_limit(int64_t p_begin, int64_t p_end
   return e < p_end ? e : p_end;
 }
 #endif
-template <int NP, int THREADS>
-__global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(PubArgs a_unused) {
+// TAB (512 lanes only; DESIGN.md section 4, "colour table"): the six colour-covariance rows of a slot are neither read nor written.
+// They are a function of (landmark, number of updates) for as long as every map came from one pk_upload_map, and come from the
+// table ctab[level][6][Lp] (pk_colour.hpp; L2 hits: a level is 96 KB and the particles sit on a few levels) at the level the
+// landmark's count names; k_colour_rows writes them back into slots whenever somebody else wants them.
+template <int NP, int THREADS, bool TAB>
+__device__ __forceinline__ void step_pub_body() {
+  static_assert(!TAB || THREADS == 512, "table mode: the 512-lane instances");
   constexpr int kPubThreads = THREADS, kPubWaves = THREADS / kWave;
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ double red[2][kPubWaves];
@@ -1077,6 +1089,7 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
   // blobs (the 256-lane instance shares a CU with two others: 704 bytes more of static LDS and only two fit -- 0.296 against 0.222 ms)
   constexpr int kUnmWords = THREADS == kPubSmallThreads ? 32 : 96;
   __shared__ unsigned s_ubits[kUnmWords];
+  __shared__ unsigned s_kmax;  // TAB: the highest level read so far
   // (the two octet numbers of a lane ride above its index in one register; in a register of their own, or below the index: no
   // better -- profiles/r04/ab_perm_mechanisms.log)
 #define PK_PUB_L0(q_, t_) (!kPerm ? 2 * kPubThreads * (q_) + 2 * (t_) : (int)(((lw >> (16 + 8 * (q_))) & 0xFFu) << 4) + 2 * ((t_)&7))
@@ -1139,6 +1152,7 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
     if (tid == 0) {
       wg_flag[0] = 0;
       wg_flag[1] = 0;
+      s_kmax = 0u;
     }
   }
   __syncthreads();
@@ -1174,30 +1188,92 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
     PK_PUB_ROW(q_, mb, F_MB)                                                                      \
     asm volatile("" ::: "memory");                                                                \
   }
+  // TAB: the pair's counts (asked for ahead of the rows that need them: the level is the table rows' address) ...
+#define PK_PUB_LOAD_COUNT(q_, sslot_, coff_, lb_)                                                 \
+  {                                                                                               \
+    const int* sc_ = reinterpret_cast<const int*>((sslot_) + (coff_));                            \
+    const Int2 c_ = *reinterpret_cast<const Int2*>(sc_ + (lb_));                                  \
+    S[2 * (q_)].count = c_.x;                                                                     \
+    S[2 * (q_) + 1].count = c_.y;                                                                 \
+  }
+  // ... and its colour blocks from the table, at the levels the counts name.  A level beyond the table (the host leaves the mode
+  // before landmarks get there, but runs scans ahead of what it knows: correctness does not rest on it) is reached from the table's
+  // last level by the recurrence itself, in a wave-uniform branch -- slow, exact and rare.  The read stays inside the table
+  // whatever the count says.
+#define PK_PUB_TAB_ROWS(q_, lb_)                                                                  \
+  {                                                                                               \
+    PubArgsPtr Rt_ = pub_args_now(rp);                                                            \
+    const double* tb_ = Rt_->ctab;                                                                \
+    const unsigned D_ = (unsigned)Rt_->ctab_depth;                                                \
+    const int lbt_ = (lb_);                                                                       \
+    bool beyond_ = false;                                                                         \
+    _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_) {                                            \
+      const unsigned k_ = min(colour_level(S[2 * (q_) + j_].count), D_ + kColourBeyondMax);       \
+      beyond_ |= k_ >= D_;                                                                        \
+      if (k_ > s_kmax) atomicMax(&s_kmax, k_);                                                    \
+      /* (a uniform row base and ONE 32-bit byte offset per landmark: the table is below 4 GB -- ct_engage) */ \
+      const unsigned bo_ = (min(k_, D_ - 1u) * 6u * (unsigned)Lp + (unsigned)(lbt_ + j_)) * 8u;   \
+      const char* tc_ = reinterpret_cast<const char*>(tb_);                                       \
+      const size_t rs_ = (size_t)Lp * 8;                                                          \
+      S[2 * (q_) + j_].crr = *reinterpret_cast<const double*>(tc_ + bo_);                         \
+      S[2 * (q_) + j_].crg = *reinterpret_cast<const double*>(tc_ + rs_ + bo_);                   \
+      S[2 * (q_) + j_].crb = *reinterpret_cast<const double*>(tc_ + 2 * rs_ + bo_);               \
+      S[2 * (q_) + j_].cgg = *reinterpret_cast<const double*>(tc_ + 3 * rs_ + bo_);               \
+      S[2 * (q_) + j_].cgb = *reinterpret_cast<const double*>(tc_ + 4 * rs_ + bo_);               \
+      S[2 * (q_) + j_].cbb = *reinterpret_cast<const double*>(tc_ + 5 * rs_ + bo_);               \
+    }                                                                                             \
+    if (__ballot(beyond_) != 0ull) {                                                              \
+      const Noise<double> qtt_ = pub_noise(pub_args_now(rp));                                     \
+      _Pragma("unroll 1") for (int j_ = 0; j_ < 2; ++j_) {                                        \
+        Landmark<double>& lmt_ = j_ == 0 ? S[2 * (q_)] : S[2 * (q_) + 1];                         \
+        const unsigned k_ = min(colour_level(lmt_.count), D_ + kColourBeyondMax);                 \
+        Sym3<double> C_{lmt_.crr, lmt_.crg, lmt_.crb, lmt_.cgg, lmt_.cgb, lmt_.cbb};              \
+        _Pragma("unroll 1") for (unsigned kk_ = D_ - 1u; kk_ < k_; ++kk_) C_ = colour_block_step(C_, qtt_); \
+        lmt_.crr = C_.a;                                                                          \
+        lmt_.crg = C_.b;                                                                          \
+        lmt_.crb = C_.c;                                                                          \
+        lmt_.cgg = C_.d;                                                                          \
+        lmt_.cgb = C_.e;                                                                          \
+        lmt_.cbb = C_.f;                                                                          \
+      }                                                                                           \
+    }                                                                                             \
+    asm volatile("" ::: "memory");                                                                \
+  }
+  // (TAB: the counts came with PK_PUB_LOAD_COUNT)
 #define PK_PUB_LOAD_COVS(q_, sslot_, coff_, lb_)                                                  \
   {                                                                                               \
     const double* sf_ = reinterpret_cast<const double*>(sslot_);                                  \
-    const int* sc_ = reinterpret_cast<const int*>((sslot_) + (coff_));                            \
     const int lbq_ = (lb_);                                                                       \
     PK_PUB_ROW(q_, pxx, F_PXX)                                                                    \
     PK_PUB_ROW(q_, pxy, F_PXY)                                                                    \
     PK_PUB_ROW(q_, pyy, F_PYY)                                                                    \
-    PK_PUB_ROW(q_, crr, F_CRR)                                                                    \
-    PK_PUB_ROW(q_, crg, F_CRG)                                                                    \
-    PK_PUB_ROW(q_, crb, F_CRB)                                                                    \
-    PK_PUB_ROW(q_, cgg, F_CGG)                                                                    \
-    PK_PUB_ROW(q_, cgb, F_CGB)                                                                    \
-    PK_PUB_ROW(q_, cbb, F_CBB)                                                                    \
-    const Int2 c_ = *reinterpret_cast<const Int2*>(sc_ + lbq_);                                   \
-    S[2 * (q_)].count = c_.x;                                                                     \
-    S[2 * (q_) + 1].count = c_.y;                                                                 \
-    asm volatile("" ::: "memory");                                                                \
+    if constexpr (!TAB) {                                                                         \
+      const int* sc_ = reinterpret_cast<const int*>((sslot_) + (coff_));                          \
+      PK_PUB_ROW(q_, crr, F_CRR)                                                                  \
+      PK_PUB_ROW(q_, crg, F_CRG)                                                                  \
+      PK_PUB_ROW(q_, crb, F_CRB)                                                                  \
+      PK_PUB_ROW(q_, cgg, F_CGG)                                                                  \
+      PK_PUB_ROW(q_, cgb, F_CGB)                                                                  \
+      PK_PUB_ROW(q_, cbb, F_CBB)                                                                  \
+      const Int2 c_ = *reinterpret_cast<const Int2*>(sc_ + lbq_);                                 \
+      S[2 * (q_)].count = c_.x;                                                                   \
+      S[2 * (q_) + 1].count = c_.y;                                                               \
+      asm volatile("" ::: "memory");                                                              \
+    } else {                                                                                      \
+      PK_PUB_TAB_ROWS(q_, lbq_)                                                                   \
+    }                                                                                             \
   }
+  // (TAB: counts first, no colour rows -- PK_PUB_TAB_ROWS follows at the top of the particle, when the counts have long arrived)
 #define PK_PUB_LOAD_PAIR(q_, sslot_, coff_, lb_)                                                  \
   {                                                                                               \
     const double* sf_ = reinterpret_cast<const double*>(sslot_);                                  \
     const int* sc_ = reinterpret_cast<const int*>((sslot_) + (coff_));                            \
     const int lbq_ = (lb_);                                                                       \
+    if constexpr (TAB) {                                                                          \
+      const Int2 c_ = *reinterpret_cast<const Int2*>(sc_ + lbq_);                                 \
+      S[2 * (q_)].count = c_.x;                                                                   \
+      S[2 * (q_) + 1].count = c_.y;                                                               \
+    }                                                                                             \
     PK_PUB_ROW(q_, mx, F_MX)                                                                      \
     PK_PUB_ROW(q_, my, F_MY)                                                                      \
     PK_PUB_ROW(q_, mr, F_MR)                                                                      \
@@ -1207,15 +1283,17 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
     PK_PUB_ROW(q_, pxx, F_PXX)                                                                    \
     PK_PUB_ROW(q_, pxy, F_PXY)                                                                    \
     PK_PUB_ROW(q_, pyy, F_PYY)                                                                    \
-    PK_PUB_ROW(q_, crr, F_CRR)                                                                    \
-    PK_PUB_ROW(q_, crg, F_CRG)                                                                    \
-    PK_PUB_ROW(q_, crb, F_CRB)                                                                    \
-    PK_PUB_ROW(q_, cgg, F_CGG)                                                                    \
-    PK_PUB_ROW(q_, cgb, F_CGB)                                                                    \
-    PK_PUB_ROW(q_, cbb, F_CBB)                                                                    \
-    const Int2 c_ = *reinterpret_cast<const Int2*>(sc_ + lbq_);                                   \
-    S[2 * (q_)].count = c_.x;                                                                     \
-    S[2 * (q_) + 1].count = c_.y;                                                                 \
+    if constexpr (!TAB) {                                                                         \
+      PK_PUB_ROW(q_, crr, F_CRR)                                                                  \
+      PK_PUB_ROW(q_, crg, F_CRG)                                                                  \
+      PK_PUB_ROW(q_, crb, F_CRB)                                                                  \
+      PK_PUB_ROW(q_, cgg, F_CGG)                                                                  \
+      PK_PUB_ROW(q_, cgb, F_CGB)                                                                  \
+      PK_PUB_ROW(q_, cbb, F_CBB)                                                                  \
+      const Int2 c_ = *reinterpret_cast<const Int2*>(sc_ + lbq_);                                 \
+      S[2 * (q_)].count = c_.x;                                                                   \
+      S[2 * (q_) + 1].count = c_.y;                                                               \
+    }                                                                                             \
     asm volatile("" ::: "memory");                                                                \
   }
   // The lane's FIRST pair of the next particle is asked for as soon as this particle's first pair has been stored -- into
@@ -1300,6 +1378,10 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
         };
         request_cand(0);
         asm volatile("" ::: "memory");
+        if constexpr (TAB) {  // the first pair's colour blocks (its counts came a particle ago)
+          static_assert(kPipe == 1, "the pairs asked for ahead take their table rows here");
+          PK_PUB_TAB_ROWS(0, lbase[0])
+        }
         // (pair by pair, means before covariance rows: the first pair's gates and verdicts are worked out while the second
         // pair's rows are still on their way -- the vector memory counter retires in order)
         {  // the next particle's source slot (pinned here: the wait for it passes under the wait for the first rows)
@@ -1400,6 +1482,11 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
             // the eight waves stood between the last row stores and what the first gates need at once, and the rows still arrive
             // long before the second pair's gates are through their atan2.  At the top: 9.96 ms per step; behind the first pair's
             // gates 9.83; behind its keys 9.71; here 9.465 (profiles/r04/ab_second_pair_rows_later.log, ab_request_order_*.log).
+            if constexpr (TAB) {  // (first in its batch: the table rows below wait for it, and with it for everything asked for before it)
+              PubArgsPtr R8 = pub_args_now(rp);
+              PK_PUB_LOAD_COUNT(1, sslot, R8->count_off, lbase[1])
+              asm volatile("" ::: "memory");
+            }
             PK_PUB_LOAD_MEANS(1, sslot, lbase[1])
             request_cand(NP - 1);
             {
@@ -1408,6 +1495,11 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
               PK_PUB_LOAD_COVS(1, sslot, R7->count_off, lbase[1])
             }
             do_pair(std::integral_constant<int, 1>{});
+            if constexpr (TAB) {
+              // (the first pair's colour blocks were let go behind its verdicts -- 24 registers the second pair's verdicts need -- and
+              // come once more from the table, L2 hits that land while the barriers and the settling pass)
+              PK_PUB_TAB_ROWS(0, lbase[0])
+            }
           }
         }
         PK_STAMP(s2)
@@ -1504,7 +1596,7 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
             const bool imm = immutable[min(l0 + j, Lp - 1)] != 0;
             if (PK_PUB_ABLATE < 1)
               acc += THREADS == kPubSmallThreads ? pub_apply_loop(Q[i], ex, order, qt, S[i], imm, sx, sy, pse[i], nullptr, 0, 0, 0xFFFFu, PK_PROD_PTR(nprod))
-                                                 : pub_apply(Q[i], ex, order, qt, S[i], imm, sx, sy, pse[i], PK_PROD_PTR(nprod));
+                                                 : pub_apply<TAB>(Q[i], ex, order, qt, S[i], imm, sx, sy, pse[i], PK_PROD_PTR(nprod));
           }
           pub_fold_norms(acc, nprod, q == NP - 1);
         };
@@ -1527,12 +1619,14 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
             PK_PUB_STORE(pxx, F_PXX)
             PK_PUB_STORE(pxy, F_PXY)
             PK_PUB_STORE(pyy, F_PYY)
-            PK_PUB_STORE(crr, F_CRR)
-            PK_PUB_STORE(crg, F_CRG)
-            PK_PUB_STORE(crb, F_CRB)
-            PK_PUB_STORE(cgg, F_CGG)
-            PK_PUB_STORE(cgb, F_CGB)
-            PK_PUB_STORE(cbb, F_CBB)
+            if constexpr (!TAB) {
+              PK_PUB_STORE(crr, F_CRR)
+              PK_PUB_STORE(crg, F_CRG)
+              PK_PUB_STORE(crb, F_CRB)
+              PK_PUB_STORE(cgg, F_CGG)
+              PK_PUB_STORE(cgb, F_CGB)
+              PK_PUB_STORE(cbb, F_CBB)
+            }
 #undef PK_PUB_STORE
             const Int2 c = {S[2 * q].count, S[2 * q + 1].count};
             __builtin_nontemporal_store(c, reinterpret_cast<Int2*>(dc + l0));
@@ -1576,6 +1670,18 @@ __global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(Pu
       if (THREADS == 512) atomicAdd(&pk_pstamp_wave[tid0 >> 6][k], pst[k]);
     }
 #endif
+  if constexpr (TAB) {  // (behind the last barrier A: every lane's level is in)
+    if (tid0 == 0) atomicMax(pub_args_now(rp)->ctab_max, s_kmax);
+  }
+}
+template <int NP, int THREADS>
+__global__ void __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) k_step_pub(PubArgs a_unused) {
+  step_pub_body<NP, THREADS, false>();
+}
+template <int NP, int THREADS, bool TAB>
+__global__ void __launch_bounds__(THREADS, 1) k_step_pub(PubArgs a_unused) {
+  static_assert(TAB, "the plain instances are k_step_pub<NP, THREADS>");
+  step_pub_body<NP, THREADS, true>();
 }
 
 // ------------------------------------------------------------------ maps beyond 2 048 landmarks: the same, in two passes
@@ -2248,7 +2354,8 @@ void launch_step_pub(hipStream_t s, DeviceState& d, int B, const double* exact_d
   static bool attr_set[kMaxDevices] = {false};
   if (first_time_on_this_device(attr_set)) {
     for (const void* fn : {reinterpret_cast<const void*>(k_step_pub<1, kPubSmallThreads>), reinterpret_cast<const void*>(k_step_pub<1, kPubThreads>),
-                           reinterpret_cast<const void*>(k_step_pub<2, kPubThreads>)})
+                           reinterpret_cast<const void*>(k_step_pub<2, kPubThreads>), reinterpret_cast<const void*>(k_step_pub<1, kPubThreads, true>),
+                           reinterpret_cast<const void*>(k_step_pub<2, kPubThreads, true>)})
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess) (void)hipGetLastError();
   }
   PubArgs a;
@@ -2289,6 +2396,10 @@ void launch_step_pub(hipStream_t s, DeviceState& d, int B, const double* exact_d
   // persistent grid: one workgroup per CU (512 lanes x 256 VGPRs), three of the 256-lane instance (143 VGPRs; LDS permitting);
   // reserve_cus as in launch_step_regs
   const bool small = d.lay.Lp <= 2 * kPubSmallThreads;
+  const bool tab = ex.ctab != nullptr && !small;
+  a.ctab = tab ? ex.ctab : nullptr;
+  a.ctab_max = ex.ctab_max;
+  a.ctab_depth = ex.ctab_depth;
   const size_t lds = step_pub_lds_bytes(B, ecap, small);
   int per_cu = 1;
   if (small) per_cu = (int)std::min<size_t>(3, std::max<size_t>(1, (160 * 1024 - 1024) / (lds + 256)));
@@ -2296,10 +2407,17 @@ void launch_step_pub(hipStream_t s, DeviceState& d, int B, const double* exact_d
   if (grid_n > p1 - p0) grid_n = p1 - p0;
   if (small)
     hipLaunchKernelGGL((k_step_pub<1, kPubSmallThreads>), dim3((unsigned)grid_n), dim3(kPubSmallThreads), lds, s, a);
-  else if (d.lay.Lp <= 2 * kPubThreads)
-    hipLaunchKernelGGL((k_step_pub<1, kPubThreads>), dim3((unsigned)grid_n), dim3(kPubThreads), lds, s, a);
-  else
-    hipLaunchKernelGGL((k_step_pub<2, kPubThreads>), dim3((unsigned)grid_n), dim3(kPubThreads), lds, s, a);
+  else if (d.lay.Lp <= 2 * kPubThreads) {
+    if (tab)
+      hipLaunchKernelGGL((k_step_pub<1, kPubThreads, true>), dim3((unsigned)grid_n), dim3(kPubThreads), lds, s, a);
+    else
+      hipLaunchKernelGGL((k_step_pub<1, kPubThreads>), dim3((unsigned)grid_n), dim3(kPubThreads), lds, s, a);
+  } else {
+    if (tab)
+      hipLaunchKernelGGL((k_step_pub<2, kPubThreads, true>), dim3((unsigned)grid_n), dim3(kPubThreads), lds, s, a);
+    else
+      hipLaunchKernelGGL((k_step_pub<2, kPubThreads>), dim3((unsigned)grid_n), dim3(kPubThreads), lds, s, a);
+  }
 }
 
 #include "pk_k_step_duo.inl"

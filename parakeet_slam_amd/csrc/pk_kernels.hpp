@@ -162,7 +162,23 @@ struct ObserveExtras {
   bool single_sightings = false;                // known ids: no landmark is matched by more than one blob
   unsigned* unm = nullptr;                      // growing maps on the publish / subscribe routes: out [P][unm_words] -- every particle's unmatched
   int unm_words = 0;                            //   blobs as a bit row in scan order (pk_k_step_pub.hip: pub_note_unmatched)
+  const double* ctab = nullptr;                 // k_step_pub's 512-lane instances in table mode: the colour table (ColourTable below), its
+  int ctab_depth = 0;                           //   depth, and where the kernel leaves the highest level it read
+  unsigned* ctab_max = nullptr;
 };
+// The colour table (pk_k_colour.hip): tab[k][6][Lp], rows crr crg crb cgg cgb cbb as in a slot -- landmark l's
+// colour block after k updates from the one pk_upload_map broadcast (base[6][Lp]; the uploaded counts are 0, so a landmark's level is
+// its update count / 2).  Null tab: not in use.
+struct ColourTable {
+  const double* tab = nullptr;
+  int depth = 0;
+};
+void launch_colour_table(hipStream_t s, const double* base_dev, double* tab_dev, int depth, int Lp, const NoiseD& qt);
+// The six colour rows of map slots written from the table at the slots' counts (levels beyond the table: the recurrence from its last
+// level).  pflag_dev == NULL: every slot of the live buffer; else the SOURCE slots of the particles whose flag is set, and nothing at
+// all while *n_flagged_dev == 0.  [p0, p1): the slots (or, with pflag_dev, the particles) covered; p1 < 0: all of them.
+void launch_colour_rows(hipStream_t s, DeviceState& d, const ColourTable& ct, const NoiseD& qt, const unsigned char* pflag_dev = nullptr,
+                        const unsigned* n_flagged_dev = nullptr, int64_t p0 = 0, int64_t p1 = -1);
 constexpr int kFastSlots = 4;   // gate-passing blobs a landmark can hand over to k_observe_fast; more -> general path
 constexpr int kSweepSlots = 8;  // ... to k_observe_sweep (large maps: a landmark's colour neighbourhood is busier)
 constexpr int kFastMaxL = 512;  // k_observe_fast / k_step_fused keep a particle's whole map in registers (one landmark per lane, 512 lanes)
@@ -238,7 +254,8 @@ void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& gri
 void launch_candidates(hipStream_t s, DeviceState& d, int B, const double* exact_dev, int64_t ref_particle, uint4* rec_dev,
                        unsigned* over_dev, unsigned* bcnt_dev = nullptr, uint4* brec_dev = nullptr, unsigned* stray_dev = nullptr,
                        int slots = kCandSlots, const double* pose_sums4_dev = nullptr, unsigned char* npass_dev = nullptr,
-                       uint4* far_dev = nullptr, const double* pose_part_dev = nullptr);  // pose_part_dev: the motion launch's per-block sums instead of pose_sums4_dev
+                       uint4* far_dev = nullptr, const double* pose_part_dev = nullptr,  // pose_part_dev: the motion launch's per-block sums instead of pose_sums4_dev
+                       const ColourTable& ct = ColourTable(), const NoiseD* qt = nullptr);  // ct.tab: the reference's colour blocks come from the table
 // K2 + K3 in one pass (pk_k_observe_ml.hip, pk_k_step_pub.hip).  (k_step_owner, a barrier-free variant in which every
 // landmark settled its blobs against the rivals named by the two-way lists, was measured at 56 ms against 13 and removed
 // in round 3: DESIGN.md section 4.)

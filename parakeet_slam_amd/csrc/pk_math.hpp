@@ -293,7 +293,52 @@ struct EkfAux {
 // With a diagonal Qc the colour block is written C' = Qc (C + Qc)^-1 C (the same matrix:
 // I - C (C + Qc)^-1 = Qc (C + Qc)^-1), six products instead of eighteen and without the
 // subtraction; the Mahalanobis term is d'v with v = (C + Qc)^-1 d in both forms.
+//
+// The colour block's step depends on C and Qt alone -- not on the pose, not on the blob: colour_block_update, one function for
+// every caller (ekf_update; the colour table of pk_k_colour.hip), so that -ffp-contract=on rounds it the same way everywhere.
+// qci = (C + Qc)^-1 as sym3_inverse gives it.
 template <typename T>
+__device__ __forceinline__ Sym3<T> colour_block_update(const Sym3<T>& C, const Sym3<T>& qci, const Noise<T>& qt) {
+  const T crr = C.a, crg = C.b, crb = C.c, cgg = C.d, cgb = C.e, cbb = C.f;
+  T nrr, nrg, nrb, ngg, ngb, nbb;
+  // M = Qci C (rows r, g, b)
+  T m00 = qci.a * crr + qci.b * crg + qci.c * crb;
+  T m01 = qci.a * crg + qci.b * cgg + qci.c * cgb;
+  T m02 = qci.a * crb + qci.b * cgb + qci.c * cbb;
+  T m11 = qci.b * crg + qci.d * cgg + qci.e * cgb;
+  T m12 = qci.b * crb + qci.d * cgb + qci.e * cbb;
+  T m22 = qci.c * crb + qci.e * cgb + qci.f * cbb;
+  if (qt.diag) {  // uniform.  C' = Qc M: the upper triangle of M is all it takes
+    nrr = qt.rr * m00;
+    nrg = qt.rr * m01;
+    nrb = qt.rr * m02;
+    ngg = qt.gg * m11;
+    ngb = qt.gg * m12;
+    nbb = qt.bb * m22;
+  } else {  // C' = C - C M (symmetric)
+    T m10 = qci.b * crr + qci.d * crg + qci.e * crb;
+    T m20 = qci.c * crr + qci.e * crg + qci.f * crb;
+    T m21 = qci.c * crg + qci.e * cgg + qci.f * cgb;
+    nrr = crr - (crr * m00 + crg * m10 + crb * m20);
+    nrg = crg - (crr * m01 + crg * m11 + crb * m21);
+    nrb = crb - (crr * m02 + crg * m12 + crb * m22);
+    ngg = cgg - (crg * m01 + cgg * m11 + cgb * m21);
+    ngb = cgb - (crg * m02 + cgg * m12 + cgb * m22);
+    nbb = cbb - (crb * m02 + cgb * m12 + cbb * m22);
+  }
+  return Sym3<T>{nrr, nrg, nrb, ngg, ngb, nbb};
+}
+// ... from C and Qt: one level of the colour table (the sum and the inverse as ekf_update forms them)
+template <typename T>
+__device__ __forceinline__ Sym3<T> colour_block_step(const Sym3<T>& C, const Noise<T>& qt) {
+  Sym3<T> qc{C.a + qt.rr, C.b + qt.rg, C.c + qt.rb, C.d + qt.gg, C.e + qt.gb, C.f + qt.bb};
+  T detc;
+  Sym3<T> qci = sym3_inverse(qc, detc);
+  return colour_block_update(C, qci, qt);
+}
+// COLOUR = false (k_step_pub in table mode, a landmark's only update of the scan): the colour block is left as it was -- the caller
+// neither stores it nor reads it again; everything else as ever.
+template <typename T, bool COLOUR = true>
 __device__ __forceinline__ T ekf_update(Landmark<T>& f, T sx, T sy, const BlobT<T>& z,
                                         const Noise<T>& qt, bool immutable,
                                         EkfAux<T>* aux = nullptr, const T* zhat0_known = nullptr, T* fro_prod = nullptr) {
@@ -372,44 +417,22 @@ __device__ __forceinline__ T ekf_update(Landmark<T>& f, T sx, T sy, const BlobT<
     T nxx = f.pxx - k0 * a0;
     T nxy = f.pxy - T(0.5) * (k0 * a1 + k1 * a0);
     T nyy = f.pyy - k1 * a1;
-    T nrr, nrg, nrb, ngg, ngb, nbb;
-    // M = Qci C (rows r, g, b)
-    T m00 = qci.a * f.crr + qci.b * f.crg + qci.c * f.crb;
-    T m01 = qci.a * f.crg + qci.b * f.cgg + qci.c * f.cgb;
-    T m02 = qci.a * f.crb + qci.b * f.cgb + qci.c * f.cbb;
-    T m11 = qci.b * f.crg + qci.d * f.cgg + qci.e * f.cgb;
-    T m12 = qci.b * f.crb + qci.d * f.cgb + qci.e * f.cbb;
-    T m22 = qci.c * f.crb + qci.e * f.cgb + qci.f * f.cbb;
-    if (qt.diag) {  // uniform.  C' = Qc M: the upper triangle of M is all it takes
-      nrr = qt.rr * m00;
-      nrg = qt.rr * m01;
-      nrb = qt.rr * m02;
-      ngg = qt.gg * m11;
-      ngb = qt.gg * m12;
-      nbb = qt.bb * m22;
-    } else {  // C' = C - C M (symmetric)
-      T m10 = qci.b * f.crr + qci.d * f.crg + qci.e * f.crb;
-      T m20 = qci.c * f.crr + qci.e * f.crg + qci.f * f.crb;
-      T m21 = qci.c * f.crg + qci.e * f.cgg + qci.f * f.cgb;
-      nrr = f.crr - (f.crr * m00 + f.crg * m10 + f.crb * m20);
-      nrg = f.crg - (f.crr * m01 + f.crg * m11 + f.crb * m21);
-      nrb = f.crb - (f.crr * m02 + f.crg * m12 + f.crb * m22);
-      ngg = f.cgg - (f.crg * m01 + f.cgg * m11 + f.cgb * m21);
-      ngb = f.cgb - (f.crg * m02 + f.cgg * m12 + f.cgb * m22);
-      nbb = f.cbb - (f.crb * m02 + f.cgb * m12 + f.cbb * m22);
-    }
+    Sym3<T> nc{f.crr, f.crg, f.crb, f.cgg, f.cgb, f.cbb};
+    if constexpr (COLOUR) nc = colour_block_update(nc, qci, qt);
     f.mr = nr;
     f.mg = ng;
     f.mb = nb;
     f.pxx = nxx;
     f.pxy = nxy;
     f.pyy = nyy;
-    f.crr = nrr;
-    f.crg = nrg;
-    f.crb = nrb;
-    f.cgg = ngg;
-    f.cgb = ngb;
-    f.cbb = nbb;
+    if constexpr (COLOUR) {
+      f.crr = nc.a;
+      f.crg = nc.b;
+      f.crb = nc.c;
+      f.cgg = nc.d;
+      f.cgb = nc.e;
+      f.cbb = nc.f;
+    }
     count_update(f.count);
   }
   return logw;
