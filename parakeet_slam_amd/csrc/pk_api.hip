@@ -185,7 +185,8 @@ struct pk_filter {
   int colour_table_depth = 1024;  // option: levels of the table
   int colour_table_margin = -1;   // option: the host leaves the mode this many levels short of the table's end; -1: min(16, depth / 2); 0: never
   bool ct_eligible = false;       // the maps came from pk_upload_map and nothing has ended the mode since
-  bool ct_updated = false;        // some observe has run since that upload
+  bool ct_updated = false;        // some landmark may be off level 0: an observe has run since that upload (pk_set_measurement_noise clears
+                                  // it again where ct_maps_untouched finds every count of the live buffer at 0 still)
   bool ct_sharded = false;        // a shard / pack / adopt call was made on this filter: never
   bool ct_built = false;          // ct_tab holds the levels of ct_base under ct_qt
   bool ct_scan = false;           // the observe in progress takes the table-mode kernel
@@ -195,8 +196,10 @@ struct pk_filter {
   double* ct_tab = nullptr;       // [ct_depth][6][Lp]
   int ct_depth = 0;
   NoiseD ct_qt{};
-  unsigned* ct_max_dev = nullptr; // the highest level a table-mode kernel has read since the upload
-  unsigned* ct_seen = nullptr;    // pinned host word: that figure, copied behind every table-mode scan (the last finished scan's, or the one before)
+  unsigned* ct_max_dev = nullptr; // word 0: the highest level a table-mode kernel has read since the upload; word 1: ct_maps_untouched's
+                                  // flag (some count of the live buffer is not 0); words 2, 3 free
+  unsigned* ct_seen = nullptr;    // pinned host words.  0: that figure, copied behind every table-mode scan (the last finished scan's, or the
+                                  // one before); 1: ct_maps_untouched's flag, read behind a synchronisation
   int64_t ct_scans = 0, ct_whole = 0;  // scans taken in the mode, whole-buffer materialisations
   bool adopt_local_done = false;  // pk_shard_adopt_local_dev made the new generation current; pk_shard_adopt_remote_dev may fill it
   int pub_ecap = 0;       // k_step_pub was prepared for the current scan with this many publish entries (0: not prepared)
@@ -464,6 +467,20 @@ bool ct_scan_ok(const pk_filter* f, const AssocLaunch& al, int B) {
   const int margin = f->colour_table_margin >= 0 ? f->colour_table_margin : std::min(16, f->ct_depth > 0 ? f->ct_depth / 2 : 16);
   if (margin > 0 && f->ct_built && f->ct_seen && (int64_t)*reinterpret_cast<volatile unsigned*>(f->ct_seen) + margin >= f->ct_depth) return false;
   return true;
+}
+// Has no slot of the live buffer a landmark off level 0?  (Every slot: behind an observe each of them was written, by the upload or by
+// the kernels; behind a resample some are nobody's any more, which errs on the safe side.)  A full pass over the counts -- P L 4 B read at a stride of slot_bytes, 0.8 GB at 100 000 x 2 000 -- and a
+// synchronisation: for pk_set_measurement_noise on an engaged filter only, never for a call of the step.
+int ct_maps_untouched(pk_filter* f, bool* untouched) {
+  *untouched = false;
+  if (!f->ct_max_dev || !f->ct_seen) return PK_OK;
+  PK_HIP(hipMemsetAsync(f->ct_max_dev + 1, 0, sizeof(unsigned), f->stream));
+  launch_colour_counts_any(f->stream, f->d, f->ct_max_dev + 1);
+  PK_LAUNCH_CHECK("colour counts");
+  PK_HIP(hipMemcpyAsync(f->ct_seen + 1, f->ct_max_dev + 1, sizeof(unsigned), hipMemcpyDeviceToHost, f->stream));
+  PK_HIP(hipStreamSynchronize(f->stream));
+  *untouched = f->ct_seen[1] == 0u;
+  return PK_OK;
 }
 // The table is allocated and built when the mode first engages on a map (built again if Qt changed before any update); the depth is
 // the option's value at that first scan, and holds until the next pk_upload_map
@@ -1202,8 +1219,14 @@ int pk_set_measurement_noise(pk_filter* f, const double Qt[16]) {
       if (fabs(Qt[i * 4 + j] - Qt[j * 4 + i]) > 1e-9 * (scale > 0 ? scale : 1.0)) coupled = true;
   int rc;
   if ((rc = use_device(f))) return rc;
-  // (the table's levels were made under the old Qt: once an update has used them the mode ends; before that the table is built afresh)
-  if (f->ct_updated && (rc = ct_end(f))) return rc;
+  // (the table's levels were made under the old Qt: once an update has used them the mode ends; before that -- scans that matched
+  // nothing included: every count is 0 still -- the mode stays and ct_engage builds the table afresh)
+  if (f->ct_updated) {
+    bool untouched = false;
+    if (f->ct_eligible && f->ct_built && !coupled && (rc = ct_maps_untouched(f, &untouched))) return rc;
+    if (untouched) f->ct_updated = false;
+    else if ((rc = ct_end(f))) return rc;
+  }
   if (coupled && !f->dense && (rc = relayout(f, true, f->map_loaded))) return rc;
   for (int i = 0; i < 16; ++i) f->qt16[i] = Qt[i];
   f->qt_dense = coupled;

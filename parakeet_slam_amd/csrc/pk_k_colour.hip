@@ -92,4 +92,24 @@ void launch_colour_rows(hipStream_t s, DeviceState& d, const ColourTable& ct, co
   hipLaunchKernelGGL(k_colour_rows, dim3((unsigned)grid), dim3(256), 0, s, a);
 }
 
+// Is any landmark of any slot of the live buffer off level 0?  (pk_set_measurement_noise: a new Qt before any update leaves the mode
+// on, the table is built afresh.)  A full pass over the counts of the buffer, P L 4 B: not for a call of the step.  A workgroup per
+// slot and turn; *any_dev is set, never cleared here.
+__global__ void __launch_bounds__(256) k_colour_counts_any(const unsigned char* map, size_t slot_bytes, size_t count_off, int L, int64_t P,
+                                                           unsigned* any_dev) {
+  bool any = false;
+  for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
+    const int* cnt = reinterpret_cast<const int*>(map + (size_t)p * slot_bytes + count_off);
+    for (int l = threadIdx.x; l < L; l += 256) any |= cnt[l] != 0;
+  }
+  if (any) atomicOr(any_dev, 1u);
+}
+
+void launch_colour_counts_any(hipStream_t s, DeviceState& d, unsigned* any_dev) {
+  if (d.P <= 0 || d.lay.L <= 0) return;
+  const int64_t grid = std::min<int64_t>(d.P, 4 * (int64_t)device_cu_count());
+  hipLaunchKernelGGL(k_colour_counts_any, dim3((unsigned)grid), dim3(256), 0, s, d.map[d.mcur], d.lay.slot_bytes, d.lay.count_off, d.lay.L,
+                     d.P, any_dev);
+}
+
 }  // namespace pk

@@ -179,6 +179,8 @@ void launch_colour_table(hipStream_t s, const double* base_dev, double* tab_dev,
 // all while *n_flagged_dev == 0.  [p0, p1): the slots (or, with pflag_dev, the particles) covered; p1 < 0: all of them.
 void launch_colour_rows(hipStream_t s, DeviceState& d, const ColourTable& ct, const NoiseD& qt, const unsigned char* pflag_dev = nullptr,
                         const unsigned* n_flagged_dev = nullptr, int64_t p0 = 0, int64_t p1 = -1);
+// *any_dev |= 1 when some landmark of some slot of the live buffer has a count other than 0.
+void launch_colour_counts_any(hipStream_t s, DeviceState& d, unsigned* any_dev);
 constexpr int kFastSlots = 4;   // gate-passing blobs a landmark can hand over to k_observe_fast; more -> general path
 constexpr int kSweepSlots = 8;  // ... to k_observe_sweep (large maps: a landmark's colour neighbourhood is busier)
 constexpr int kFastMaxL = 512;  // k_observe_fast / k_step_fused keep a particle's whole map in registers (one landmark per lane, 512 lanes)
