@@ -462,7 +462,7 @@ class DeviceFilter(object):
     def observe_pub_stats(self):
         """The last scan's publish table (pk_observe_pub_stats): dict of entries, contested blobs, landmarks of the reference
         particle with several blobs inside their gates, longest candidate list, entry capacity, instance (0 none, 1 one
-        workgroup per CU, 2 k_step_pub_duo)."""
+        workgroup per CU, 2 and 3 k_step_pub_duo with "pub_duo" = 1 and 2)."""
         a = np.zeros(6, dtype=np.int64)
         check(self._lib.pk_observe_pub_stats(self._h, lptr(a)))
         return dict(zip(("entries", "contested_blobs", "multi_landmarks", "longest_list", "entry_capacity", "instance"), (int(v) for v in a)))

@@ -70,15 +70,49 @@ struct TimedSpan {
 
 }  // namespace
 
+// The kernels of one maximum-likelihood scan ("Routing": the table of kinds against their conditions).
+// plan_scan decides it once per scan; every stage of the observe follows it.
+enum class ScanKind {
+  Brute,         // k_assoc_brute + k_observe
+  General,       // k_assoc_grid + k_observe
+  HandoffFast,   // k_assoc_grid's hand-off + k_observe_fast
+  HandoffSweep,  // ... + k_observe_sweep
+  // the one-pass kinds: the association launches nothing, one kernel does gates + EKF, what it flags goes to the kernels above
+  Fused,         // k_step_fused
+  PubSmall,      // k_step_pub<1, 256>
+  Regs,          // k_step_regs, no publish table
+  PubRegs,       // k_step_pub<2, 512>, k_step_regs behind it for the scans it stands back from
+  Pub,           // k_step_pub<2, 512> alone (pruned lists, growing maps)
+  PubBig,        // k_step_pub_big, k_step_pub_duo in front of it with "pub_duo"
+};
+struct ScanPlan {
+  ScanKind kind = ScanKind::Brute;
+  int route = PK_ROUTE_ML_GENERAL;  // what pk_observe_route reports
+  // the hand-off: slots per landmark, lists allocated (for every particle on the hand-off kinds, for the second-chance rows behind
+  // k_step_regs / k_step_pub / k_step_pub_big), the second chance runs
+  int slots = kFastSlots;
+  bool lists = false;
+  bool retry = false;
+  // the reference particle's candidate lists: entries per list (0: none made), inverse lists and the publish table's layout
+  // (k_cand_entries) for ecap entries, look-alikes beyond the underflow edge pruned
+  int cand_slots = 0;
+  bool publish = false;
+  int ecap = 0;
+  bool far = false;
+  DuoLimits duo;            // PubBig: what k_step_pub_duo has room for (all zero: the instance is off)
+  // a scan the kernel stands back from, with no stand-by kernel behind it, flags its particles for the fall-back kernels: inside
+  // k_cand_entries when the launches cover every particle, else by a k_flag_range_if launch per range (3 us a step)
+  bool flag_fold = false, flag_range = false;
+  bool colour_table = false;  // Pub: the table-mode instance
+  bool onepass() const { return kind >= ScanKind::Fused; }
+  bool ranged() const { return kind >= ScanKind::Regs; }  // runs on particle ranges (pk_observe_staged_range)
+};
+
 struct AssocLaunch {
-  bool fused = false;  // nothing launched yet: k_step_fused does gates + EKF in one kernel
-  bool regs = false;   // nothing launched yet: k_step_regs does the same for 512 < L <= 2048
-  bool retry = false;  // with regs: the hand-off lists for the flagged particles' second chance are allocated
-  bool big = false;    // nothing launched yet: k_step_pub_big (2 048 < L <= 6 144: publish / subscribe in two passes over the map)
+  ScanPlan plan;
   BlobGrid grid{};
   int n9 = 0;
   const unsigned char* tables = nullptr;
-  bool fast = false;  // hand-off written: k_observe_fast can run
   const double* blobs = nullptr;
   const double* dir = nullptr;
   const double* exact = nullptr;
@@ -149,9 +183,8 @@ struct pk_filter {
   uint4* cand_dev = nullptr;  // [Lp + kCandSpare][3] candidate records (two or three uint4 per landmark in use)
   int regs_step = 1;     // 512 < L <= 2048 and scan tables that fit LDS: k_step_regs (one pass, map in registers)
   int pub_step = 1;      // ... with the contested blobs settled by static publish / subscribe (k_step_pub) while the publish table fits LDS
-  bool flag_folded = false;  // this scan's k_cand_entries flags every particle itself when nobody takes the scan (whole observes)
   int pub_small = -1;    // L <= 512: k_step_pub<256 lanes> instead of k_step_fused -- 1 / 0, or -1 (default): where it is measured faster
-                         // (pub_small_now below)
+                         // (kPubSmallAutoWork below)
   int duo_park_limit = -1;  // >= 0: k_step_pub_duo's overflow area is treated as this small (tests: particles that need more go to the fall-back kernels)
   int duo_on = 0;        // "pub_duo" (measured, off: DESIGN.md section 4): 2 048 < L <= 5 120, scans whose publish table fits its share of a CU's LDS go to
                          // k_step_pub_duo -- 1: two 512-lane workgroups per CU (<= 128 VGPRs), 2: three 256-lane workgroups (<= 168) -- the others to k_step_pub_big
@@ -189,7 +222,6 @@ struct pk_filter {
                                   // it again where ct_maps_untouched finds every count of the live buffer at 0 still)
   bool ct_sharded = false;        // a shard / pack / adopt call was made on this filter: never
   bool ct_built = false;          // ct_tab holds the levels of ct_base under ct_qt
-  bool ct_scan = false;           // the observe in progress takes the table-mode kernel
   bool ct_engaged = false;        // the last observe did, and nothing has ended the mode since
   bool colour_rows_valid = true;
   double* ct_base = nullptr;      // [6][Lp] the uploaded colour rows
@@ -419,6 +451,14 @@ int materialise(pk_filter* f) {
   return PK_OK;
 }
 
+// Behind an observe: every map slot was just rewritten from its source (the receive buffer of the last exchange is free), and ctl
+// holds the maximum of the new log-weights
+void observe_done(pk_filter* f) {
+  f->src_identity = true;
+  f->d.alt = nullptr;
+  f->gmax_fused = true;
+}
+
 // ---- the colour table's host side
 ColourTable ct_view(const pk_filter* f) { return ColourTable{f->ct_tab, f->ct_depth}; }
 // The slots of the live buffer get their colour rows back (no-op while they are valid).  Called at the top of every entry point that
@@ -449,19 +489,15 @@ int colour_rows_for_download(pk_filter* f, int64_t p0, int64_t p1) {
 // ... and the mode stays off until the next pk_upload_map
 int ct_end(pk_filter* f) {
   f->ct_eligible = false;
-  f->ct_scan = false;
   f->ct_engaged = false;
   return ensure_colour_rows(f);
 }
-// Does this observe take the table-mode kernel?  (The conditions under which onepass_prepare / onepass_launch hand the scan to
-// k_step_pub's 512-lane instances, with pruned lists: a scan that kernel stands back from then goes to the general kernels as a
-// whole, behind k_colour_rows, and never to k_step_regs.)
-bool ct_scan_ok(const pk_filter* f, const AssocLaunch& al, int B) {
+// Does the filter's colour-table state let a scan take the table-mode kernel?  (plan_scan asks for the scans that go to k_step_pub's
+// 512-lane instances alone, with pruned lists: a scan that kernel stands back from then goes to the general kernels as a whole,
+// behind k_colour_rows, and never to k_step_regs.)
+bool ct_state_ok(const pk_filter* f) {
   if (f->colour_table == 0 || !f->ct_eligible || f->ct_sharded || f->grow_on || f->dense || !f->ct_base) return false;
-  if (!al.regs || al.fused || al.big) return false;
-  if (!f->cand_lists || !f->pub_step || !f->far_prune) return false;
-  if (f->d.lay.Lp <= 2 * kPubSmallThreads || f->d.lay.L > kRegsMaxL) return false;
-  if (regs_cand_lds_bytes(f->d.lay.Lp, B) > kMaxDynLds || step_pub_entry_capacity(B) <= 0) return false;
+  if (f->d.lay.Lp <= 2 * kPubSmallThreads) return false;
   // beyond the table's end the kernel runs the recurrence itself, lane by lane (exact, slow): the host leaves the mode before the
   // levels it knows of get there (colour_table_margin = 0: never -- the kernel's own handling carries every scan)
   const int margin = f->colour_table_margin >= 0 ? f->colour_table_margin : std::min(16, f->ct_depth > 0 ? f->ct_depth / 2 : 16);
@@ -802,24 +838,93 @@ int stage_ml_scan(pk_filter* f, const double* blobs, int B) {
   return PK_OK;
 }
 
-// Will a production observe of a scan with these tables take the register route (k_step_regs)?
-// ... or, for maps beyond it, the two-pass publish / subscribe route (k_step_pub_big)?  Both run on particle ranges, which is
-// what the split step of the sharded filter needs (the conditions are enqueue_association's).
-static bool regs_route_taken(pk_filter* f, const BlobGrid& g, int B, int n9) {
-  if (f->fast_observe != 1 || B <= 0 || f->d.lay.L >= 65535) return false;
-  if (f->regs_step && f->d.lay.L > kFastMaxL && f->d.lay.L <= kRegsMaxL && n9 > 0 && regs_lds_bytes(g.ncell, B, n9) <= kMaxDynLds) return true;
-  return f->pub_step && f->cand_lists && f->d.lay.L > kRegsMaxL && f->d.lay.L <= kPubBigMaxL && step_pub_big_entry_capacity(B) > 0 &&
-         observe_sweep_plan(f->d, B).grid > 0;
+// Maps of at most 512 landmarks: the publish / subscribe instance (k_step_pub<1, 256> on candidate lists) or k_step_fused?  The former's
+// kernel is the faster one and costs two per-scan kernels whatever the number of particles; measured over P x L (DESIGN.md section 10,
+// profiles/r06/pub_small_sweep*.log) the whole step ties at 10 000 x 500 and wins from there on: from 5e6 particle.landmarks on, and
+// not below 128 landmarks, where nothing was measured.
+constexpr int64_t kPubSmallAutoWork = 5000000;
+constexpr int kPubSmallAutoLandmarks = 128;
+
+// Which kernels does this scan get?  The one place that decides (the conditions, kind by kind: DESIGN.md section 4, "Routing").  Reads
+// the filter and the scan's facts, touches nothing.  grow: the new-landmark bookkeeping follows the scan -- a kernel of the publish /
+// subscribe family (they leave every particle's unmatched blobs as bit rows) or the general association (ids), never another.
+// whole: the launches that follow cover every particle.
+ScanPlan plan_scan(const pk_filter* f, int B, bool use_grid, int ncell, int n9, bool want_fast, bool finalize, bool grow, bool whole) {
+  ScanPlan p;
+  if (!use_grid) return p;
+  p.kind = ScanKind::General;
+  const int L = f->d.lay.L, Lp = f->d.lay.Lp;
+  const bool sweep = L > kFastMaxL || f->fast_observe >= 2;
+  auto sweep_fits = [&] { return observe_sweep_plan(f->d, B).grid > 0; };
+  auto limited = [&](int ecap) { return f->pub_entry_limit > 0 && ecap > f->pub_entry_limit ? f->pub_entry_limit : ecap; };
+  const bool lists_both_ways = f->pub_step && f->cand_lists;
+  const bool onepass = want_fast && !finalize && f->fast_observe == 1 && B > 0 && (!grow || (lists_both_ways && B <= 32 * 176));
+  if (onepass && f->fused_step && !sweep && n9 > 0 && fused_lds_bytes(ncell, B, n9) <= kFusedMaxLds &&
+      (!grow || (step_pub_entry_capacity_small(B) > 0 && B <= 32 * 32))) {
+    const bool wanted = grow || (f->pub_small >= 0 ? f->pub_small != 0
+                                                   : f->d.P * (int64_t)L >= kPubSmallAutoWork && L >= kPubSmallAutoLandmarks);
+    p.kind = wanted && lists_both_ways && step_pub_entry_capacity_small(B) > 0 ? ScanKind::PubSmall : ScanKind::Fused;
+    p.route = PK_ROUTE_ML_FUSED;
+    if (p.kind == ScanKind::PubSmall) {
+      p.cand_slots = kCandSlots;
+      p.ecap = limited(step_pub_entry_capacity_small(B));
+    }
+  } else if (onepass && f->regs_step && L > kFastMaxL && L <= kRegsMaxL && n9 > 0 && regs_lds_bytes(ncell, B, n9) <= kMaxDynLds &&
+             (!grow || (step_pub_entry_capacity(B) > 0 && regs_cand_lds_bytes(Lp, B) <= kMaxDynLds && B <= 32 * 96))) {
+    // the flags, and -- when the two-sweep kernel can take this scan -- eight-slot hand-off lists for the second chance of the
+    // particles k_step_regs flags (growing maps: no second chance -- what the kernel hands on goes to the general kernels, which leave ids)
+    p.lists = f->regs_retry && sweep_fits();
+    p.retry = p.lists && !grow;
+    p.slots = p.lists ? kSweepSlots : kFastSlots;
+    p.kind = ScanKind::Regs;
+    p.route = PK_ROUTE_ML_REGS;
+    if (f->cand_lists && regs_cand_lds_bytes(Lp, B) <= kMaxDynLds) {
+      p.cand_slots = kCandSlots;
+      p.ecap = f->pub_step ? limited(step_pub_entry_capacity(B)) : 0;
+      // pruned lists: k_step_regs' candidate-list instance never takes them (k_cand_entries: skip_cand) and is not even launched
+      if (p.ecap > 0) p.kind = f->far_prune || grow ? ScanKind::Pub : ScanKind::PubRegs;
+    }
+  } else if (onepass && lists_both_ways && L > kRegsMaxL && L <= kPubBigMaxL && step_pub_big_entry_capacity(B) > 0 && sweep_fits()) {
+    // what k_step_pub_big flags -- or the whole scan, when a sixteen-entry list overflows or the publish table does not fit LDS --
+    // goes through the eight-slot hand-off and k_observe_sweep, then the general kernels
+    p.kind = ScanKind::PubBig;
+    p.route = PK_ROUTE_ML_PUB_BIG;
+    p.lists = true;
+    p.retry = !grow;
+    p.slots = kSweepSlots;
+    p.cand_slots = 2 * kCandSlots;
+    p.ecap = limited(step_pub_big_entry_capacity(B));
+    if (f->duo_on) {
+      step_pub_duo_limits(B, Lp, f->duo_on, &p.duo);
+      p.duo.ecap = limited(p.duo.ecap);
+      p.duo.park_limit = f->duo_park_limit;
+    }
+  } else if (want_fast && !grow && !finalize && f->fast_observe && B > 0 && (sweep ? sweep_fits() : observe_fast_lds_bytes(B) <= kMaxDynLds)) {
+    // eight hand-off slots per landmark for the large scans (a landmark's colour neighbourhood gets busier with B: at B = 5 000
+    // random colours some landmark of every particle passes 5-7 blobs), four (16-byte entries) otherwise; "fast_observe" = 3 forces eight
+    p.kind = sweep ? ScanKind::HandoffSweep : ScanKind::HandoffFast;
+    p.route = sweep ? PK_ROUTE_ML_SWEEP : PK_ROUTE_ML_HANDOFF;
+    p.lists = true;
+    p.slots = sweep && (B >= 3000 || f->fast_observe == 3) ? kSweepSlots : kFastSlots;
+    // the hand-off instance tests each landmark against the reference particle's candidate list instead of walking the colour grid
+    // (sixteen entries per list: with several thousand blobs around the robot eight overflow somewhere in every scan)
+    if (f->cand_lists && L < 65535) p.cand_slots = 2 * kCandSlots;
+  }
+  p.publish = p.ecap > 0;
+  p.far = p.publish && f->far_prune;
+  // no stand-by kernel behind these: a scan they stand back from goes to the fall-back kernels as a whole
+  const bool alone = p.kind == ScanKind::PubSmall || p.kind == ScanKind::Pub || p.kind == ScanKind::PubBig;
+  p.flag_fold = alone && whole;
+  p.flag_range = alone && !whole;
+  p.colour_table = p.kind == ScanKind::Pub && p.far && ct_state_ok(f);
+  return p;
 }
 
-// Upload one scan for maximum-likelihood association (one block) and enqueue the association.
-// `blobs` may be the staged copy itself (pk_observe_staged).
-// onepass_only (growing maps: the bookkeeping kernel needs every particle's unmatched blobs -- the publish / subscribe kernels leave them
-// as bit rows, the general association as ids): a one-pass route whose kernel is of the publish / subscribe family, or else the
-// general association; never the hand-off routes, k_step_fused or k_step_regs
-int enqueue_association(pk_filter* f, const double* blobs, int B, bool finalize, bool want_fast, AssocLaunch* out, bool onepass_only = false) {
+// Upload one scan for maximum-likelihood association (one block), plan it and enqueue what the plan wants of the association:
+// nothing (the one-pass kinds), k_candidates + k_assoc_grid, or k_assoc_brute.  `blobs` may be the staged copy itself (pk_observe_staged).
+int enqueue_association(pk_filter* f, const double* blobs, int B, bool finalize, bool want_fast, AssocLaunch* out, bool grow = false,
+                        bool whole = false) {
   int rc;
-  const bool pub_ok = !onepass_only || (f->pub_step && f->cand_lists && B <= 32 * 176);
   pk_filter::Staged& sg = f->staged;
   const size_t o_blobs = kCtlBytes;
   const size_t o_dir = o_blobs + (size_t)B * 4 * sizeof(double);
@@ -828,114 +933,59 @@ int enqueue_association(pk_filter* f, const double* blobs, int B, bool finalize,
   if (!(sg.valid && sg.B == B && blobs == reinterpret_cast<const double*>(sg.st + o_blobs)))
     if ((rc = stage_ml_scan(f, blobs, B))) return rc;
   sg.valid = false;  // consumed
-  unsigned char* st = sg.st;
-  const int slot = sg.slot;
-  const BlobGrid g = sg.g;
-  const int n9 = sg.n9;
-  const bool use_grid = sg.use_grid;
-  const size_t tab_bytes = sg.tab_bytes;
   if (!sg.uploaded) {
-    if ((rc = upload_scan(f, st, use_grid ? o_tab + tab_bytes : o_exact))) return rc;
-    if ((rc = note_upload(f, slot))) return rc;
+    if ((rc = upload_scan(f, sg.st, sg.use_grid ? o_tab + sg.tab_bytes : o_exact))) return rc;
+    if ((rc = note_upload(f, sg.slot))) return rc;
   }
   sg.uploaded = false;
   f->gmax_fused = false;
-  const double* blobs_dev = reinterpret_cast<const double*>(f->scan_dev + o_blobs);
-  const double* dir_dev = reinterpret_cast<const double*>(f->scan_dev + o_dir);
+  AssocLaunch al;
+  al.plan = plan_scan(f, B, sg.use_grid, sg.g.ncell, sg.n9, want_fast, finalize, grow, whole);
+  const ScanPlan& plan = al.plan;
+  al.grid = sg.g;
+  al.n9 = sg.n9;
+  al.blobs = reinterpret_cast<const double*>(f->scan_dev + o_blobs);
+  al.dir = reinterpret_cast<const double*>(f->scan_dev + o_dir);
+  if (sg.use_grid) {
+    const size_t cs_b = ((size_t)(sg.g.ncell + 1) * 2 + 15) & ~(size_t)15;
+    al.tables = f->scan_dev + o_tab;
+    al.exact = reinterpret_cast<const double*>(f->scan_dev + o_exact);
+    al.order = reinterpret_cast<const unsigned short*>(f->scan_dev + o_tab + cs_b + (size_t)B * 16 + (size_t)sg.n9 * 2);
+  }
   if (out) {
-    out->blobs = blobs_dev;
-    out->dir = dir_dev;
+    *out = al;
+    f->route = plan.route;  // (the one place: pk_associate, which passes no `out`, leaves the last observe's)
   }
-  if (use_grid) {
-    FastHandoff fh{};
-    const bool sweep = f->d.lay.L > kFastMaxL || f->fast_observe >= 2;
-    if (out && want_fast && !finalize && f->fast_observe == 1 && f->fused_step && !sweep && B > 0 && n9 > 0 &&
-        fused_lds_bytes(g.ncell, B, n9) <= kFusedMaxLds && pub_ok && (!onepass_only || (step_pub_entry_capacity_small(B) > 0 && B <= 32 * 32))) {
-      if ((rc = ensure_handoff(f, B, kFastSlots, false))) return rc;
-      out->fused = true;
-      out->grid = g;
-      out->n9 = n9;
-      out->tables = f->scan_dev + o_tab;
-      out->exact = reinterpret_cast<const double*>(f->scan_dev + o_exact);
-      const size_t cs_b = ((size_t)(g.ncell + 1) * 2 + 15) & ~(size_t)15;
-      out->order = reinterpret_cast<const unsigned short*>(f->scan_dev + o_tab + cs_b + (size_t)B * 16 + (size_t)n9 * 2);
-      return PK_OK;
-    }
-    if (out && want_fast && !finalize && f->fast_observe == 1 && f->regs_step && f->d.lay.L > kFastMaxL &&
-        f->d.lay.L <= kRegsMaxL && B > 0 && n9 > 0 && regs_lds_bytes(g.ncell, B, n9) <= kMaxDynLds && pub_ok &&
-        (!onepass_only || (step_pub_entry_capacity(B) > 0 && regs_cand_lds_bytes(f->d.lay.Lp, B) <= kMaxDynLds && B <= 32 * 96))) {
-      // the flags, and -- when the two-sweep kernel can take this scan -- eight-slot hand-off lists for the second chance of
-      // the particles k_step_regs flags (allocated here, not at the first flagged particle in the middle of a run)
-      out->retry = f->regs_retry && observe_sweep_plan(f->d, B).grid > 0;
-      if ((rc = ensure_handoff(f, B, out->retry ? kSweepSlots : kFastSlots, out->retry, true))) return rc;
-      out->regs = true;
-      out->grid = g;
-      out->n9 = n9;
-      out->tables = f->scan_dev + o_tab;
-      out->exact = reinterpret_cast<const double*>(f->scan_dev + o_exact);
-      const size_t cs_b = ((size_t)(g.ncell + 1) * 2 + 15) & ~(size_t)15;
-      out->order = reinterpret_cast<const unsigned short*>(f->scan_dev + o_tab + cs_b + (size_t)B * 16 + (size_t)n9 * 2);
-      return PK_OK;
-    }
-    if (out && want_fast && !finalize && f->fast_observe == 1 && f->pub_step && f->cand_lists && f->d.lay.L > kRegsMaxL &&
-        f->d.lay.L <= kPubBigMaxL && B > 0 && step_pub_big_entry_capacity(B) > 0 && observe_sweep_plan(f->d, B).grid > 0 && pub_ok) {
-      // maps beyond the register route: publish / subscribe in two passes (k_step_pub_big); what it flags -- or the whole scan,
-      // when a sixteen-entry list overflows or the publish table does not fit LDS -- goes through the eight-slot hand-off
-      // and k_observe_sweep, then the general kernels
-      if ((rc = ensure_handoff(f, B, kSweepSlots, true, true))) return rc;
-      out->big = true;
-      out->retry = true;
-      out->grid = g;
-      out->n9 = n9;
-      out->tables = f->scan_dev + o_tab;
-      out->exact = reinterpret_cast<const double*>(f->scan_dev + o_exact);
-      const size_t cs_b = ((size_t)(g.ncell + 1) * 2 + 15) & ~(size_t)15;
-      out->order = reinterpret_cast<const unsigned short*>(f->scan_dev + o_tab + cs_b + (size_t)B * 16 + (size_t)n9 * 2);
-      return PK_OK;
-    }
-    if (want_fast && !onepass_only && !finalize && f->fast_observe && B > 0 &&
-        (sweep ? observe_sweep_plan(f->d, B).grid > 0 : observe_fast_lds_bytes(B) <= kMaxDynLds)) {
-      // eight hand-off slots per landmark for the large scans (a landmark's colour neighbourhood gets
-      // busier with B: at B = 5 000 random colours some landmark of every particle passes 5-7 blobs),
-      // four (16-byte entries) otherwise; "fast_observe" = 3 forces eight
-      const int slots = (sweep && (B >= 3000 || f->fast_observe == 3)) ? kSweepSlots : kFastSlots;
-      if ((rc = ensure_handoff(f, B, slots))) return rc;
-      f->fh.slots = slots;
-      fh = f->fh;
-      fh.n_flagged = ctl_n_flagged(f);
-    }
-    if ((rc = ct_end(f))) return rc;  // (the general association reads the slots' colour rows)
-    Span t(f, PK_T_ASSOC);
-    CandTable cand;
-    if (fh.lmpass && f->cand_lists && f->d.lay.L < 65535) {
-      // the hand-off instance tests each landmark against the reference particle's candidate list (k_candidates, once per
-      // scan) instead of walking the colour grid; a list that overflows leaves the scan to the walk
-      if (!f->cand_dev && (rc = dev_alloc(f, &f->cand_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
-      // (sixteen entries per list: with several thousand blobs around the robot eight overflow somewhere in every scan)
-      launch_summary_partials(f->stream, f->d, f->partial, f->out4);  // the reference pose: the particles' mean
-      launch_candidates(f->stream, f->d, B, reinterpret_cast<const double*>(f->scan_dev + o_exact), 0, f->cand_dev, ctl_cand_over(f),
-                        nullptr, nullptr, nullptr, 2 * kCandSlots, f->out4);
-      cand.rec = f->cand_dev;
-      cand.over = ctl_cand_over(f);
-      cand.slots = 2 * kCandSlots;
-    }
-    launch_assoc_grid(f->stream, f->d, B, g, n9, f->scan_dev + o_tab, reinterpret_cast<const double*>(f->scan_dev + o_exact),
-                      f->ids_dev, finalize, fh, cand);
-    if (out) {
-      out->fast = fh.lmpass != nullptr;
-      out->exact = reinterpret_cast<const double*>(f->scan_dev + o_exact);
-      const size_t cs_b = ((size_t)(g.ncell + 1) * 2 + 15) & ~(size_t)15;
-      out->order = reinterpret_cast<const unsigned short*>(f->scan_dev + o_tab + cs_b + (size_t)B * 16 + (size_t)n9 * 2);
-    }
-    return PK_OK;
-  }
-  if (assoc_brute_lds_bytes(B) > kMaxDynLds)
+  // the hand-off's buffers (allocated here, not at the first flagged particle in the middle of a run)
+  if (plan.onepass() || plan.lists)
+    if ((rc = ensure_handoff(f, B, plan.slots, plan.lists, plan.ranged()))) return rc;
+  if (plan.onepass()) return PK_OK;
+  if (plan.kind == ScanKind::Brute && assoc_brute_lds_bytes(B) > kMaxDynLds)
     return fail(PK_ERR_UNSUPPORTED,
                 "maximum-likelihood association of %d blobs: neither the colour-grid tables nor the brute-force kernel's "
                 "%zu bytes of per-blob state fit the workgroup's %zu bytes of LDS", B, assoc_brute_lds_bytes(B), (size_t)kMaxDynLds);
-  if ((rc = ct_end(f))) return rc;
+  if ((rc = ct_end(f))) return rc;  // (the general association reads the slots' colour rows)
   Span t(f, PK_T_ASSOC);
-  launch_assoc_brute(f->stream, f->d, blobs_dev, dir_dev, B, f->ids_dev);
+  if (plan.kind == ScanKind::Brute) {
+    launch_assoc_brute(f->stream, f->d, al.blobs, al.dir, B, f->ids_dev);
+    return PK_OK;
+  }
+  FastHandoff fh{};
+  CandTable cand;
+  if (plan.lists) {
+    f->fh.slots = plan.slots;
+    fh = f->fh;
+    fh.n_flagged = ctl_n_flagged(f);
+    if (plan.cand_slots) {  // (a list that overflows leaves the scan to the grid walk)
+      if (!f->cand_dev && (rc = dev_alloc(f, &f->cand_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
+      launch_summary_partials(f->stream, f->d, f->partial, f->out4);  // the reference pose: the particles' mean
+      launch_candidates(f->stream, f->d, B, al.exact, 0, f->cand_dev, ctl_cand_over(f), nullptr, nullptr, nullptr, plan.cand_slots, f->out4);
+      cand.rec = f->cand_dev;
+      cand.over = ctl_cand_over(f);
+      cand.slots = plan.cand_slots;
+    }
+  }
+  launch_assoc_grid(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, f->ids_dev, finalize, fh, cand);
   return PK_OK;
 }
 
@@ -1261,7 +1311,6 @@ int pk_upload_map(pk_filter* f, const double* means, const double* covs, const u
   launch_broadcast_slot(f->stream, f->d, f->slot_tmp);
   // every particle holds this map with update counts 0: the colour table's level 0 (the 512-lane publish / subscribe route only)
   f->colour_rows_valid = true;  // (every slot of the live buffer was just rewritten)
-  f->ct_scan = false;
   f->ct_engaged = false;
   f->ct_built = false;
   f->ct_updated = false;
@@ -1530,9 +1579,7 @@ static int dense_observe(pk_filter* f, const double* blobs, int32_t B, const int
   }
   PK_LAUNCH_CHECK("pk_observe (dense)");
   if (update) {
-    f->src_identity = true;
-    f->d.alt = nullptr;  // every map slot was just rewritten from its source: the receive buffer of the last exchange is free
-    f->gmax_fused = true;
+    observe_done(f);
     f->route = PK_ROUTE_DENSE;
   } else {
     f->gmax_fused = false;  // the control words were overwritten by this upload
@@ -1548,9 +1595,9 @@ static int dense_observe(pk_filter* f, const double* blobs, int32_t B, const int
   return PK_OK;
 }
 
-// ---- the one-pass routes (k_step_fused / k_step_regs) in three pieces, so that the sharded filter can run the middle one
-// on a part of the particles while the rest are still on the wire (pk_observe_staged_range) -------------------------------
-// 1. the reference particle's candidate lists (register route), timed with the association
+// ---- the one-pass kinds (ScanPlan::onepass) in three pieces, so that the sharded filter can run the middle one on a part of the
+// particles while the rest are still on the wire (pk_observe_staged_range) ------------------------------------------------
+// 1. the reference particle's candidate lists and the publish table's layout, timed with the association; first their buffers
 static int ensure_inverse_lists(pk_filter* f, int B, int slots = kCandSlots) {
   int rc;
   B = B * (slots / kCandSlots);  // (capacity in units of eight-entry lists: sixteen-entry lists take two)
@@ -1577,152 +1624,109 @@ static int ensure_inverse_lists(pk_filter* f, int B, int slots = kCandSlots) {
   }
   return PK_OK;
 }
-// what k_step_pub_duo has room for at this scan size (all zero: the instance is off, k_step_pub_big takes every scan)
-static DuoLimits duo_limits(const pk_filter* f, int B) {
-  DuoLimits d;
-  if (!f->duo_on) return d;
-  step_pub_duo_limits(B, f->d.lay.Lp, f->duo_on, &d);
-  if (f->pub_entry_limit > 0 && d.ecap > f->pub_entry_limit) d.ecap = f->pub_entry_limit;
-  d.park_limit = f->duo_park_limit;
-  return d;
+// the per-map buffers of the plan's lists, allocated when a scan first wants them
+static int ensure_list_buffers(pk_filter* f, const ScanPlan& plan, int B) {
+  int rc;
+  const size_t Lpp = (size_t)f->d.lay.Lp + kCandSpare;
+  const bool big = plan.kind == ScanKind::PubBig;  // sixteen-entry lists both ways
+  if (!f->cand_dev && (rc = dev_alloc(f, &f->cand_dev, Lpp * 3))) return rc;
+  if (!plan.publish) return PK_OK;
+  if (big ? !f->erec_dev2 && (rc = dev_alloc(f, &f->erec_dev2, Lpp * 2)) : !f->erec_dev && (rc = dev_alloc(f, &f->erec_dev, Lpp))) return rc;
+  if (!f->npass_dev && (rc = dev_alloc(f, &f->npass_dev, Lpp))) return rc;
+  if (!f->far_dev && (rc = dev_alloc(f, &f->far_dev, Lpp * 3))) return rc;
+  if (big && !f->prim_dev && (rc = dev_alloc(f, &f->prim_dev, prim_table_uint4(f->d.lay.Lp)))) return rc;
+  return ensure_inverse_lists(f, B, plan.cand_slots);
 }
 // ref: the particle whose MAP the candidate lists are made from -- particle 0, or in a split step the first particle of the range
 // that has been filled already (the slots at either end still hold the old generation then)
-// Maps of at most 512 landmarks: the publish / subscribe instance (k_step_pub<1, 256> on candidate lists) or k_step_fused?  The former's
-// kernel is the faster one (11 % at 10 000 x 500, 18 % at 100 000 x 256) and costs two per-scan kernels and a flag launch (27 us) whatever
-// the number of particles.  Measured over P x L (profiles/r06/pub_small_sweep*.log): the whole step loses with it at 5 000 x 500 (+14 %)
-// and 8 000 x 500 (+3 %), ties at 10 000 x 500 (+0.6 %, -0.4 % at 12 000) and wins from there on (-5 % at 16 000 x 500, -8 % at
-// 100 000 x 500, -15 % at 100 000 x 256); at 10 000 x 256 it is +1.5 %, at 10 000 x 128 +7 %, at 100 000 x 128 -7.5 %.  The gain grows
-// with P x L, the cost does not: the publish / subscribe instance from 5e6 particle.landmarks on -- BASELINE configs[1], 10 000 x 500,
-// is the tie.  Below 128 landmarks nothing was measured: k_step_fused.
-constexpr int64_t kPubSmallAutoWork = 5000000;
-constexpr int kPubSmallAutoLandmarks = 128;
-static bool pub_small_now(const pk_filter* f) {
-  if (f->grow_on) return true;  // (growing maps: only the publish / subscribe kernels leave the unmatched blobs' bit rows)
-  if (f->pub_small >= 0) return f->pub_small != 0;
-  return f->d.P * (int64_t)f->d.lay.L >= kPubSmallAutoWork && f->d.lay.L >= kPubSmallAutoLandmarks;
-}
-// whole: the launch that follows covers every particle -- a scan the publish / subscribe kernel stands back from and nobody else takes
-// then flags the particles in k_cand_entries itself (f->flag_folded) instead of a k_flag_range_if launch of its own (3 us a step)
-static int onepass_prepare(pk_filter* f, const AssocLaunch& al, int B, CandTable* cand, int64_t ref = 0, bool whole = false) {
+static int onepass_prepare(pk_filter* f, const AssocLaunch& al, int B, CandTable* cand, int64_t ref = 0) {
   int rc;
-  f->pub_ecap = 0;
-  f->flag_folded = false;
-  // the register route; with "pub_small" (on from 5e6 particle.landmarks: pub_small_now) also the L <= 512 route through the publish /
-  // subscribe instance of three 256-lane workgroups per CU
-  const bool small_pub = al.fused && pub_small_now(f) && f->pub_step && f->cand_lists && step_pub_entry_capacity_small(B) > 0;
-  if (al.big) {  // sixteen-entry lists both ways and the publish table's layout
-    if (!f->cand_dev && (rc = dev_alloc(f, &f->cand_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
-    if (!f->npass_dev && (rc = dev_alloc(f, &f->npass_dev, (size_t)f->d.lay.Lp + kCandSpare))) return rc;
-    if (!f->erec_dev2 && (rc = dev_alloc(f, &f->erec_dev2, ((size_t)f->d.lay.Lp + kCandSpare) * 2))) return rc;
-    if ((rc = ensure_inverse_lists(f, B, 2 * kCandSlots))) return rc;
-    if (!f->far_dev && (rc = dev_alloc(f, &f->far_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
-    if (!f->prim_dev && (rc = dev_alloc(f, &f->prim_dev, prim_table_uint4(f->d.lay.Lp)))) return rc;
-    int ecap = step_pub_big_entry_capacity(B);
-    if (f->pub_entry_limit > 0 && ecap > f->pub_entry_limit) ecap = f->pub_entry_limit;
-    Span t(f, PK_T_ASSOC);
-    uint4* far = f->far_prune ? f->far_dev : nullptr;
-    // the reference pose: the particles' mean -- from the sums the motion launch left, or (poses touched since) two launches
-    const double* part = f->pose_part_ok ? f->pose_part : nullptr;
-    if (!part) launch_summary_partials(f->stream, f->d, f->partial, f->out4);
-    launch_candidates(f->stream, f->d, B, al.exact, ref, f->cand_dev, ctl_cand_over(f), f->bcnt_dev, f->brec_dev, ctl_n_stray(f),
-                      2 * kCandSlots, f->out4, f->npass_dev, far, part);
-    launch_cand_entries(f->stream, f->d, B, f->cand_dev, f->erec_dev2, f->bcnt_dev, f->brec_dev, f->binfo_dev, f->glist_dev, ctl_cand_over(f),
-                        ctl_skip_pub(f), ctl_skip_cand(f), ecap, 2 * kCandSlots, al.exact, f->gate4_dev, f->npass_dev, far != nullptr,
-                        ctl_pub_stats(f), ctl_skip_duo(f), ctl_skip_big(f), duo_limits(f, B), f->prim_dev, whole ? f->fh.pflag : nullptr,
-                        whole ? ctl_n_flagged(f) : nullptr);
-    f->flag_folded = whole;
-    cand->rec = f->cand_dev;
-    cand->far = far;
-    cand->over = ctl_cand_over(f);
-    cand->slots = 2 * kCandSlots;
-    f->pub_ecap = ecap;
+  const ScanPlan& plan = al.plan;
+  f->pub_ecap = plan.ecap;
+  if (!plan.cand_slots) return PK_OK;
+  if ((rc = ensure_list_buffers(f, plan, B))) return rc;
+  Span t(f, PK_T_ASSOC);
+  // the reference pose: the particles' mean -- from the sums the motion launch left, or (poses touched since) two launches
+  const double* part = f->pose_part_ok ? f->pose_part : nullptr;
+  if (!part) launch_summary_partials(f->stream, f->d, f->partial, f->out4);
+  cand->rec = f->cand_dev;
+  cand->over = ctl_cand_over(f);
+  cand->slots = plan.cand_slots;
+  if (!plan.publish) {
+    launch_candidates(f->stream, f->d, B, al.exact, ref, f->cand_dev, ctl_cand_over(f), nullptr, nullptr, nullptr, plan.cand_slots, f->out4, nullptr, nullptr, part);
     return PK_OK;
   }
-  if ((al.regs && f->cand_lists && regs_cand_lds_bytes(f->d.lay.Lp, B) <= kMaxDynLds) || small_pub) {
-    if (!f->cand_dev && (rc = dev_alloc(f, &f->cand_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
-    int ecap = !f->pub_step ? 0 : al.fused ? step_pub_entry_capacity_small(B) : step_pub_entry_capacity(B);
-    if (f->pub_entry_limit > 0 && ecap > f->pub_entry_limit) ecap = f->pub_entry_limit;
-    if (ecap > 0) {
-      if (!f->erec_dev && (rc = dev_alloc(f, &f->erec_dev, (size_t)f->d.lay.Lp + kCandSpare))) return rc;
-      if (!f->npass_dev && (rc = dev_alloc(f, &f->npass_dev, (size_t)f->d.lay.Lp + kCandSpare))) return rc;
-      if (!f->far_dev && (rc = dev_alloc(f, &f->far_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
-      if ((rc = ensure_inverse_lists(f, B))) return rc;
-    }
-    Span t(f, PK_T_ASSOC);
-    const double* part = f->pose_part_ok ? f->pose_part : nullptr;  // (as above)
-    if (!part) launch_summary_partials(f->stream, f->d, f->partial, f->out4);
-    cand->rec = f->cand_dev;
-    cand->over = ctl_cand_over(f);
-    if (ecap > 0) {  // candidate lists both ways, and the publish table's layout
-      uint4* far = f->far_prune ? f->far_dev : nullptr;
-      launch_candidates(f->stream, f->d, B, al.exact, ref, f->cand_dev, ctl_cand_over(f), f->bcnt_dev, f->brec_dev, ctl_n_stray(f),
-                        kCandSlots, f->out4, f->npass_dev, far, part, f->ct_scan ? ct_view(f) : ColourTable(), &f->ct_qt);
-      // (the flags are folded where no stand-by kernel takes a scan k_step_pub leaves: pruned lists, growing maps, maps of at most 512 landmarks)
-      const bool fold = whole && (far != nullptr || f->grow_on || al.fused);
-      launch_cand_entries(f->stream, f->d, B, f->cand_dev, f->erec_dev, f->bcnt_dev, f->brec_dev, f->binfo_dev, f->glist_dev, ctl_cand_over(f),
-                          ctl_skip_pub(f), ctl_skip_cand(f), ecap, kCandSlots, nullptr, nullptr, f->npass_dev, far != nullptr, ctl_pub_stats(f),
-                          nullptr, nullptr, DuoLimits(), nullptr, fold ? f->fh.pflag : nullptr, fold ? ctl_n_flagged(f) : nullptr);
-      f->flag_folded = fold;
-      cand->far = far;
-      cand->skip_cand = ctl_skip_cand(f);
-      f->pub_ecap = ecap;
-    } else {
-      launch_candidates(f->stream, f->d, B, al.exact, ref, f->cand_dev, ctl_cand_over(f), nullptr, nullptr, nullptr, kCandSlots, f->out4, nullptr, nullptr, part);
-    }
-  }
+  // candidate lists both ways, and the publish table's layout; the two-pass kernels also get the blobs' float records, the
+  // primary-blob table and the choice between their two instances
+  const bool big = plan.kind == ScanKind::PubBig;
+  uint4* far = plan.far ? f->far_dev : nullptr;
+  launch_candidates(f->stream, f->d, B, al.exact, ref, f->cand_dev, ctl_cand_over(f), f->bcnt_dev, f->brec_dev, ctl_n_stray(f), plan.cand_slots,
+                    f->out4, f->npass_dev, far, part, plan.colour_table ? ct_view(f) : ColourTable(), big ? nullptr : &f->ct_qt);
+  launch_cand_entries(f->stream, f->d, B, f->cand_dev, big ? f->erec_dev2 : f->erec_dev, f->bcnt_dev, f->brec_dev, f->binfo_dev, f->glist_dev,
+                      ctl_cand_over(f), ctl_skip_pub(f), ctl_skip_cand(f), plan.ecap, plan.cand_slots, big ? al.exact : nullptr,
+                      big ? f->gate4_dev : nullptr, f->npass_dev, plan.far, ctl_pub_stats(f), big ? ctl_skip_duo(f) : nullptr,
+                      big ? ctl_skip_big(f) : nullptr, plan.duo, big ? f->prim_dev : nullptr, plan.flag_fold ? f->fh.pflag : nullptr,
+                      plan.flag_fold ? ctl_n_flagged(f) : nullptr);
+  cand->far = far;
+  if (!big) cand->skip_cand = ctl_skip_cand(f);
   return PK_OK;
 }
-// 2. the one-pass kernel on the particles [p0, p1) (the fused kernel: the whole range only)
+// 2. the one-pass kernel on the particles [p0, p1) (k_step_fused: the whole range only)
 static int onepass_launch(pk_filter* f, const AssocLaunch& al, int B, const ObserveExtras& ex, const CandTable& cand, int64_t p0,
                           int64_t p1, int reserve_cus = 0) {
+  const ScanPlan& plan = al.plan;
   FastHandoff fh = f->fh;
   fh.n_flagged = ctl_n_flagged(f);
   fh.flags_only = true;
   Span t(f, PK_T_OBSERVE);
   ObserveExtras e1 = ex;
   e1.flip = false;
-  if (al.big) {
-    // the scan goes to ONE of the two instances (k_cand_entries decided which: the two-workgroups-per-CU instance when its share of
-    // LDS holds the scan's publish table); both are launched, one returns at once
-    const DuoLimits duo = duo_limits(f, B);
-    if (duo.tbytes > 0)
-      launch_step_pub_duo(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev2, f->glist_dev, ctl_skip_duo(f), ctl_pub_stats(f), duo,
-                          f->gate4_dev, f->prim_dev, p0, p1, reserve_cus);
-    launch_step_pub_big(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev2, f->glist_dev, ctl_skip_big(f), f->pub_ecap, f->gate4_dev,
-                        p0, p1, reserve_cus, f->prim_dev, ctl_pub_stats(f));
-    // a scan the kernel stood back from (a list overflowed, the table did not fit): every particle to the fall-back kernels
-    if (!f->flag_folded) launch_flag_range_if(f->stream, ctl_skip_pub(f), fh.pflag, fh.n_flagged, p0, p1);
-  } else if (al.regs) {
-    if (f->ct_scan) {
-      e1.ctab = f->ct_tab;
-      e1.ctab_depth = f->ct_depth;
-      e1.ctab_max = f->ct_max_dev;
-    }
-    if (f->pub_ecap > 0 && cand.rec)
-      launch_step_pub(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev, f->glist_dev, ctl_skip_pub(f), f->pub_ecap,
-                      p0, p1, reserve_cus);
-    // pruned lists (cand.far): k_step_regs' candidate-list instance never takes them (k_cand_entries: skip_cand) -- it is not even
-    // launched then (5 us a step for a kernel that returns at once) --, so a scan the publish / subscribe kernel stood back from goes
-    // to the fall-back kernels as a whole
-    if ((cand.far || f->grow_on) && f->pub_ecap > 0) {  // (growing maps: only the publish / subscribe kernels leave the unmatched blobs' bit rows)
-      if (!f->flag_folded) launch_flag_range_if(f->stream, ctl_skip_pub(f), fh.pflag, fh.n_flagged, p0, p1);
-    } else
-      launch_step_regs(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, al.order, fh, f->qt, e1, f->regs_warm, cand, p0, p1,
-                       reserve_cus);
-  } else {
-    if (f->pub_ecap > 0 && cand.rec)
-      launch_step_pub(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev, f->glist_dev, ctl_skip_pub(f), f->pub_ecap,
-                      p0, p1, reserve_cus);
-    // (round 6: no k_step_fused stand-by behind the publish / subscribe instance -- 10 000 workgroups that return at once were 5.7 us of a
-    // 270-us step; a scan that kernel stands back from -- its table does not fit a third of a CU's LDS: a few hundred entries do -- goes
-    // to the general kernels as a whole.  Growing maps need it that way: only the publish / subscribe kernels leave the unmatched blobs' rows)
-    if (f->pub_ecap > 0 && cand.rec) {
-      if (!f->flag_folded) launch_flag_range_if(f->stream, ctl_skip_pub(f), fh.pflag, fh.n_flagged, p0, p1);
-    } else
-      launch_step_fused(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, al.order, fh, f->qt, e1,
-                        (f->pub_ecap > 0 && cand.rec) ? ctl_skip_pub(f) : nullptr);
+  if (plan.colour_table) {
+    e1.ctab = f->ct_tab;
+    e1.ctab_depth = f->ct_depth;
+    e1.ctab_max = f->ct_max_dev;
   }
+  switch (plan.kind) {
+    case ScanKind::PubBig:
+      // the scan goes to ONE of the two instances (k_cand_entries decided which: the two-workgroups-per-CU instance when its share of
+      // LDS holds the scan's publish table); both are launched, one returns at once
+      if (plan.duo.tbytes > 0)
+        launch_step_pub_duo(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev2, f->glist_dev, ctl_skip_duo(f), ctl_pub_stats(f),
+                            plan.duo, f->gate4_dev, f->prim_dev, p0, p1, reserve_cus);
+      launch_step_pub_big(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev2, f->glist_dev, ctl_skip_big(f), plan.ecap, f->prim_dev,
+                          ctl_pub_stats(f), f->gate4_dev, p0, p1, reserve_cus);
+      break;
+    case ScanKind::PubSmall:
+    case ScanKind::Pub:
+    case ScanKind::PubRegs:
+      launch_step_pub(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev, f->glist_dev, ctl_skip_pub(f), plan.ecap, p0, p1,
+                      reserve_cus);
+      if (plan.kind != ScanKind::PubRegs) break;
+      [[fallthrough]];  // (the stand-by: returns at once unless k_step_pub stood back)
+    case ScanKind::Regs:
+      launch_step_regs(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, al.order, fh, f->qt, e1, f->regs_warm, cand, p0, p1, reserve_cus);
+      break;
+    case ScanKind::Fused:
+      launch_step_fused(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, al.order, fh, f->qt, e1);
+      break;
+    default:
+      break;
+  }
+  // a scan the kernel stood back from (a list overflowed, the table did not fit): every particle to the fall-back kernels
+  if (plan.flag_range) launch_flag_range_if(f->stream, ctl_skip_pub(f), fh.pflag, fh.n_flagged, p0, p1);
+  return PK_OK;
+}
+// k_observe_sweep's per-workgroup result lists
+static int ensure_sweep_results(pk_filter* f, const SweepPlan& plan) {
+  const size_t need = (size_t)plan.grid * plan.results_per_wg;
+  if (need <= f->sweep_cap) return PK_OK;
+  PK_HIP(hipStreamSynchronize(f->stream));
+  if (f->sweep_results) (void)hipFree(f->sweep_results);
+  f->sweep_results = nullptr;
+  f->sweep_cap = 0;
+  int rc;
+  if ((rc = dev_alloc(f, &f->sweep_results, need))) return rc;
+  f->sweep_cap = need;
   return PK_OK;
 }
 // 3. what the one-pass kernel flagged, over all particles: second chance, then the general kernels (which swap the map buffers)
@@ -1731,22 +1735,14 @@ static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const Obse
   FastHandoff fh = f->fh;
   fh.n_flagged = ctl_n_flagged(f);
   fh.flags_only = true;
-  if ((al.regs || al.big) && al.retry) {
+  if (al.plan.retry) {
     // second chance for what k_step_regs flagged (some landmark passes more than its four register slots -- 2 us per
     // particle in the general kernels, and up to 9 % of the particles at some poses of the bench's trajectory): the
     // hand-off instance with eight slots and k_observe_sweep, both on the flagged particles only (timed with the other
     // fallbacks in the association slot: the observe slot holds the one-pass kernel alone, one span per launch)
     Span t(f, PK_T_ASSOC);
     const SweepPlan plan = observe_sweep_plan(f->d, B);
-    const size_t need = (size_t)plan.grid * plan.results_per_wg;
-    if (need > f->sweep_cap) {
-      PK_HIP(hipStreamSynchronize(f->stream));
-      if (f->sweep_results) (void)hipFree(f->sweep_results);
-      f->sweep_results = nullptr;
-      f->sweep_cap = 0;
-      if ((rc = dev_alloc(f, &f->sweep_results, need))) return rc;
-      f->sweep_cap = need;
-    }
+    if ((rc = ensure_sweep_results(f, plan))) return rc;
     FastHandoff fr = f->fh;
     fr.slots = kSweepSlots;
     fr.retry = true;
@@ -1848,9 +1844,7 @@ static int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int3
                      reinterpret_cast<const int32_t*>(f->scan_dev + o_next), n0, nullptr, f->qt, ex);
     }
     PK_LAUNCH_CHECK("pk_observe");
-    f->src_identity = true;
-    f->d.alt = nullptr;  // every map slot was just rewritten from its source: the receive buffer of the last exchange is free
-    f->gmax_fused = true;
+    observe_done(f);
     f->route = PK_ROUTE_KNOWN_IDS;
     if (ids_out)
       for (int64_t p = 0; p < f->d.P; ++p) memcpy(ids_out + (size_t)p * B, ids, (size_t)B * 4);
@@ -1859,15 +1853,13 @@ static int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int3
   // maximum-likelihood association on the device
   AssocLaunch al;
   // (ids wanted: the association kernel + k_observe; growing maps: a publish / subscribe kernel, or that)
-  if ((rc = enqueue_association(f, blobs, B, false, ids_out == nullptr, &al, grow))) return rc;
+  if ((rc = enqueue_association(f, blobs, B, false, ids_out == nullptr, &al, grow, true))) return rc;
+  const ScanPlan& plan = al.plan;
   // the colour table's mode: this scan takes the table-mode kernel, or the mode ends here (the slots get their colour rows first)
-  f->ct_scan = ct_scan_ok(f, al, B);
-  if (f->ct_scan ? (rc = ct_engage(f)) : (rc = ct_end(f))) return rc;
+  if (plan.colour_table ? (rc = ct_engage(f)) : (rc = ct_end(f))) return rc;
   f->grow_bits = false;
-  if (grow && (al.fused || al.regs || al.big)) {
-    // round 6: the one-pass kernel leaves every particle's unmatched blobs as a bit row (scan order); no second chance -- what it
-    // hands on goes to the general kernels, which leave ids
-    al.retry = false;
+  if (grow && plan.onepass()) {
+    // round 6: the one-pass kernel leaves every particle's unmatched blobs as a bit row (scan order)
     const int words = 2 * ((B + 63) / 64);
     if ((int64_t)f->d.P * words > f->unm_cap) {
       PK_HIP(hipStreamSynchronize(f->stream));
@@ -1884,18 +1876,11 @@ static int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int3
     f->grow_bits = true;
   }
   ex.gmax_key = ctl_gmax_key(f);
-  f->route = al.big ? PK_ROUTE_ML_PUB_BIG
-             : al.fused ? PK_ROUTE_ML_FUSED
-             : al.regs ? PK_ROUTE_ML_REGS
-             : !al.fast ? PK_ROUTE_ML_GENERAL
-             : (f->d.lay.L > kFastMaxL || f->fast_observe >= 2) ? PK_ROUTE_ML_SWEEP : PK_ROUTE_ML_HANDOFF;
-  if (al.fused || al.regs || al.big) {
+  if (plan.onepass()) {
     CandTable cand;
-    if ((rc = onepass_prepare(f, al, B, &cand, 0, true))) return rc;
-    // (ct_scan_ok restates what sends the scan to k_step_pub; should the two ever part, the scan simply leaves the mode)
-    if (f->ct_scan && !(f->pub_ecap > 0 && cand.rec && cand.far) && (rc = ct_end(f))) return rc;
+    if ((rc = onepass_prepare(f, al, B, &cand))) return rc;
     if ((rc = onepass_launch(f, al, B, ex, cand, 0, f->d.P))) return rc;
-    if (f->ct_scan) {
+    if (plan.colour_table) {
       // what the kernel handed on (or the whole scan, where it stood back) goes to kernels that read whole slots: the SOURCE slots of
       // those particles get their colour rows from the table first -- a launch that returns in its first wave on the usual scan
       Span t(f, PK_T_ASSOC);
@@ -1907,39 +1892,25 @@ static int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int3
       f->ct_scans += 1;
     }
     if ((rc = onepass_finish(f, al, B, ex, cand))) return rc;
-    f->ct_scan = false;
   } else {
     Span t(f, PK_T_OBSERVE);
-    if (al.fast) {
+    if (plan.lists) {  // the hand-off was written
       ObserveExtras e1 = ex;
       e1.flip = false;
-      if (f->d.lay.L > kFastMaxL || f->fast_observe >= 2) {
-        const SweepPlan plan = observe_sweep_plan(f->d, B);
-        const size_t need = (size_t)plan.grid * plan.results_per_wg;
-        if (need > f->sweep_cap) {
-          PK_HIP(hipStreamSynchronize(f->stream));
-          if (f->sweep_results) (void)hipFree(f->sweep_results);
-          f->sweep_results = nullptr;
-          f->sweep_cap = 0;
-          if ((rc = dev_alloc(f, &f->sweep_results, need))) return rc;
-          f->sweep_cap = need;
-        }
-        launch_observe_sweep(f->stream, f->d, B, al.exact, al.order, f->fh, f->qt, e1, plan, f->sweep_results);
+      if (plan.kind == ScanKind::HandoffSweep) {
+        const SweepPlan sweep = observe_sweep_plan(f->d, B);
+        if ((rc = ensure_sweep_results(f, sweep))) return rc;
+        launch_observe_sweep(f->stream, f->d, B, al.exact, al.order, f->fh, f->qt, e1, sweep, f->sweep_results);
       } else {
         launch_observe_fast(f->stream, f->d, B, al.exact, al.order, f->fh, f->qt, e1);
       }
-      ObserveExtras e2 = ex;
-      e2.only_flagged = f->fh.pflag;
-      e2.n_flagged = ctl_n_flagged(f);
-      launch_observe(f->stream, f->d, al.blobs, al.dir, B, nullptr, nullptr, 0, f->ids_dev, f->qt, e2);
-    } else {
-      launch_observe(f->stream, f->d, al.blobs, al.dir, B, nullptr, nullptr, 0, f->ids_dev, f->qt, ex);
+      ex.only_flagged = f->fh.pflag;
+      ex.n_flagged = ctl_n_flagged(f);
     }
+    launch_observe(f->stream, f->d, al.blobs, al.dir, B, nullptr, nullptr, 0, f->ids_dev, f->qt, ex);
   }
   PK_LAUNCH_CHECK("pk_observe");
-  f->src_identity = true;
-  f->d.alt = nullptr;  // every map slot was just rewritten from its source: the receive buffer of the last exchange is free
-  f->gmax_fused = true;
+  observe_done(f);
   if (grow) {  // :92-95 for every particle, on the ids the association kernel left in HBM (every particle's slot is its own now)
     Span t(f, PK_T_OBSERVE);
     launch_new_landmarks(f->stream, f->d, f->grow, f->ids_dev, al.blobs, B, f->grow_bits ? f->unm_dev : nullptr, f->unm_words,
@@ -1990,8 +1961,9 @@ int pk_observe_staged(pk_filter* f, int32_t fresh) {
 }
 
 int pk_staged_takes_regs(pk_filter* f) {
-  if (!f || f->dense || f->grow_on || !f->staged.valid || !f->staged.use_grid) return 0;  // (the bookkeeping wants the ids in HBM: the general route)
-  return regs_route_taken(f, f->staged.g, f->staged.B, f->staged.n9) ? 1 : 0;
+  if (!f || f->dense || f->grow_on || !f->staged.valid) return 0;  // (growing maps: whole observes only)
+  const pk_filter::Staged& sg = f->staged;
+  return plan_scan(f, sg.B, sg.use_grid, sg.g.ncell, sg.n9, true, false, false, false).ranged() ? 1 : 0;
 }
 
 int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1, int32_t first, int32_t last) {
@@ -2012,8 +1984,7 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
     sp.reset = fresh != 0;
     sp.al = AssocLaunch();
     if ((rc = enqueue_association(f, blobs, sp.B, false, true, &sp.al))) return rc;
-    if (!sp.al.regs && !sp.al.big) return fail(PK_ERR_STATE, "pk_observe_staged_range: the scan did not take the register route");
-    f->route = sp.al.big ? PK_ROUTE_ML_PUB_BIG : PK_ROUTE_ML_REGS;
+    if (!sp.al.plan.ranged()) return fail(PK_ERR_STATE, "pk_observe_staged_range: the scan did not take the register route");
     sp.cand = CandTable();
     if ((rc = onepass_prepare(f, sp.al, sp.B, &sp.cand, p1 > p0 ? p0 : 0))) return rc;
     sp.active = true;
@@ -2032,9 +2003,7 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
     sp.active = false;
     if ((rc = onepass_finish(f, sp.al, sp.B, ex, sp.cand))) return rc;
     PK_LAUNCH_CHECK("pk_observe_staged_range");
-    f->src_identity = true;
-    f->d.alt = nullptr;
-    f->gmax_fused = true;
+    observe_done(f);
   }
   return PK_OK;
 }

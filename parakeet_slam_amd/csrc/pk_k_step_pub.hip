@@ -2287,10 +2287,10 @@ __global__ void __launch_bounds__(kPubThreads) k_step_pub_big(PubArgs a_unused) 
 
 void launch_step_pub_big(hipStream_t s, DeviceState& d, int B, const double* exact_dev, const unsigned short* order_dev,
                          const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const CandTable& cand, const uint4* erec_dev,
-                         const unsigned* glist_dev, const unsigned* skip_dev, int ecap, const float4* gate4_dev, int64_t p0, int64_t p1,
-                         int reserve_cus, const uint4* prim_dev, const unsigned* stats_dev) {
+                         const unsigned* glist_dev, const unsigned* skip_dev, int ecap, const uint4* prim_dev, const unsigned* stats_dev,
+                         const float4* gate4_dev, int64_t p0, int64_t p1, int reserve_cus) {
   if (p1 < 0) p1 = d.P;
-  if (d.P == 0 || p1 <= p0 || !prim_dev || !stats_dev) return;  // (the scan's primary-blob table and figures: onepass_prepare makes them)
+  if (d.P == 0 || p1 <= p0) return;
   static bool attr_set[kMaxDevices] = {false};
   if (first_time_on_this_device(attr_set)) {
     for (const void* fn : {reinterpret_cast<const void*>(k_step_pub_big<3>), reinterpret_cast<const void*>(k_step_pub_big<5>),

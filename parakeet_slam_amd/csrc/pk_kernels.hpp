@@ -313,8 +313,8 @@ int step_pub_big_entry_capacity(int B);
 size_t step_pub_big_lds_bytes(int B, int ecap);
 void launch_step_pub_big(hipStream_t s, DeviceState& d, int B, const double* exact_dev, const unsigned short* order_dev,
                          const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const CandTable& cand, const uint4* erec_dev,
-                         const unsigned* glist_dev, const unsigned* skip_dev, int ecap, const float4* gate4_dev = nullptr, int64_t p0 = 0,
-                         int64_t p1 = -1, int reserve_cus = 0, const uint4* prim_dev = nullptr, const unsigned* stats_dev = nullptr);
+                         const unsigned* glist_dev, const unsigned* skip_dev, int ecap, const uint4* prim_dev, const unsigned* stats_dev,
+                         const float4* gate4_dev = nullptr, int64_t p0 = 0, int64_t p1 = -1, int reserve_cus = 0);
 // The two-workgroups-per-CU instance of the two-pass kernel (pk_k_step_duo.hip): ONE landmark per lane and turn, one carried word
 // per landmark, the expected bearing worked out again in pass 2 -- at most 128 VGPRs, so that two 512-lane workgroups share a CU
 // (four waves per SIMD) and one's row latency is the other's float64 issue.  Each has half the CU's LDS: k_cand_entries decides per

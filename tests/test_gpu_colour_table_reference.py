@@ -399,7 +399,7 @@ def test_the_staged_path(lib, ranged):
     close(fs)
 
 
-# Lp = L rounded up to a multiple of 16 (pk_layout.hpp), and the mode wants 512 < Lp, L <= 2048 (ct_scan_ok, pk_upload_map):
+# Lp = L rounded up to a multiple of 16 (pk_layout.hpp), and the mode wants 512 < Lp, L <= 2048 (plan_scan / ct_state_ok, pk_upload_map):
 # L = 513 has Lp = 528 > 512 -- the smallest map on the table's side (L = 512: Lp = 512, k_step_fused);
 # 1024 is the last map of the NP = 1 instance, 1025 (Lp = 1040) and 1026 the first of NP = 2; 2047 and 2048 (Lp = 2048) the last.
 @pytest.mark.parametrize("L", [513, 1024, 1025, 1026, 2047, 2048])
