@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/parakeet_slam.h"
+#include "pk_devmem.hpp"
 #include "pk_kernels.hpp"
 #include "pk_pub_layout.hpp"
 
@@ -66,6 +67,24 @@ int fail(int code, const char* fmt, ...) {
 struct TimedSpan {
   int slot;
   hipEvent_t a, b;
+};
+
+// what the filter's memory registry (pk_devmem.hpp) allocates and frees with
+struct HipRaw {
+  int device_alloc(void** p, size_t bytes) {
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return PK_OK;
+    (void)hipGetLastError();
+    return fail(PK_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+  }
+  void device_free(void* p) { (void)hipFree(p); }
+  int host_alloc(void** p, size_t bytes, unsigned flags) {
+    hipError_t e = hipHostMalloc(p, bytes, flags);
+    if (e == hipSuccess) return PK_OK;
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? PK_ERR_NOMEM : PK_ERR_HIP, "hipHostMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+  }
+  void host_free(void* p) { (void)hipHostFree(p); }
 };
 
 }  // namespace
@@ -132,7 +151,7 @@ struct pk_filter {
   bool map_loaded = false;
   bool src_identity = true;
   int64_t nblocks = 0;  // weight-scan blocks
-  int64_t device_bytes = 0;
+  DevMem<HipRaw> mem;   // owns every device and pinned block below and in d, fh, grow, bal (dev_alloc / dev_reserve / host_alloc)
   // workspaces
   double* z_dev = nullptr;        // P x 3
   unsigned char* scan_dev = nullptr;  // per-scan block: ctl | blobs | chains or association tables
@@ -283,16 +302,40 @@ struct pk_filter {
 
 namespace {
 
+// A filter's device and pinned memory comes from these alone ("Memory"): f->mem records every block, and
+// pk_destroy frees what it holds.
 template <typename T>
-int dev_alloc(pk_filter* f, T** p, size_t n) {
+int dev_alloc(pk_filter* f, T** p, size_t n) { return f->mem.alloc(p, n ? n : 1); }
+template <typename T>
+void dev_free(pk_filter* f, T** p) {
+  f->mem.release(*p);
   *p = nullptr;
-  if (n == 0) n = 1;
-  hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(PK_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-  }
-  f->device_bytes += (int64_t)(n * sizeof(T));
+}
+// a buffer allocated once, when something first wants it (no synchronisation: nothing is freed)
+template <typename T>
+int dev_lazy(pk_filter* f, T** p, size_t n) { return *p ? PK_OK : dev_alloc(f, p, n); }
+// The grow pattern: nothing while need <= *cap; else the stream is synchronised, the members are freed and allocated afresh, and
+// *cap = new_cap last (a failure leaves *cap == 0).  dev_reserve: one buffer of new_cap elements; dev_reserve_group: several
+// buffers behind one capacity, each want(&p, n) with its own element count.
+template <typename C, typename... T>
+int dev_reserve_group(pk_filter* f, C* cap, C need, C new_cap, Want<T>... w) {
+  auto idle = [f]() -> int {
+    PK_HIP(hipStreamSynchronize(f->stream));
+    return PK_OK;
+  };
+  return f->mem.reserve(cap, need, new_cap, idle, w...);
+}
+template <typename T, typename C>
+int dev_reserve(pk_filter* f, T** p, C* cap, C need, C new_cap) { return dev_reserve_group(f, cap, need, new_cap, want(p, (size_t)new_cap)); }
+// pinned host memory (registered, not counted in pk_device_bytes)
+template <typename T>
+int host_alloc(pk_filter* f, T** p, size_t n, unsigned flags) { return f->mem.alloc_host(p, n, flags); }
+// a pinned block of 64 bytes whose first word starts at 0 (retry_seen, ct_seen)
+int host_word(pk_filter* f, unsigned** p) {
+  if (*p) return PK_OK;
+  int rc;
+  if ((rc = host_alloc(f, p, 16, hipHostMallocDefault))) return rc;
+  **p = 0u;
   return PK_OK;
 }
 
@@ -353,29 +396,15 @@ int use_device(pk_filter* f) {
 constexpr size_t kCtlBytes = 8 * kGmaxKeys + 64;  // running-max keys, then the flagged-particle count, the route control words and the publish table's figures
 int ensure_scan_capacity(pk_filter* f, size_t bytes) {
   if (bytes <= f->scan_cap) return PK_OK;
-  PK_HIP(hipStreamSynchronize(f->stream));
-  if (f->scan_dev) (void)hipFree(f->scan_dev);
-  f->scan_dev = nullptr;
-  f->scan_cap = 0;
-  const size_t cap = bytes + bytes / 4 + 4096;
   int rc;
-  if ((rc = dev_alloc(f, &f->scan_dev, cap))) return rc;
-  f->scan_cap = cap;
+  if ((rc = dev_reserve(f, &f->scan_dev, &f->scan_cap, bytes, bytes + bytes / 4 + 4096))) return rc;
   f->gmax_fused = false;  // the running-max keys lived in the block that was just freed
   return PK_OK;
 }
 
 int ensure_ids_capacity(pk_filter* f, int B) {
-  int64_t need = f->d.P * (int64_t)B;
-  if (need <= f->ids_cap) return PK_OK;
-  PK_HIP(hipStreamSynchronize(f->stream));
-  if (f->ids_dev) (void)hipFree(f->ids_dev);
-  f->ids_dev = nullptr;
-  f->ids_cap = 0;
-  int rc;
-  if ((rc = dev_alloc(f, &f->ids_dev, (size_t)need))) return rc;
-  f->ids_cap = need;
-  return PK_OK;
+  const int64_t need = f->d.P * (int64_t)B;
+  return dev_reserve(f, &f->ids_dev, &f->ids_cap, need, need);
 }
 
 // One scan block host -> device in stream order.  The staging ring is pinned and device-mapped, so
@@ -406,11 +435,12 @@ int note_upload(pk_filter* f, int slot) {
 int take_stage(pk_filter* f, size_t bytes, unsigned char** out, int* slot) {
   if (bytes > f->stage_cap) {
     PK_HIP(hipStreamSynchronize(f->stream));
+    int rc;
+    f->stage_cap = 0;
     size_t cap = bytes + bytes / 4 + 4096;
     for (int i = 0; i < pk_filter::kRing; ++i) {
-      if (f->stage[i]) (void)hipHostFree(f->stage[i]);
-      f->stage[i] = nullptr;
-      PK_HIP(hipHostMalloc((void**)&f->stage[i], cap, hipHostMallocMapped));
+      dev_free(f, &f->stage[i]);
+      if ((rc = host_alloc(f, &f->stage[i], cap, hipHostMallocMapped))) return rc;
       if (!f->stage_done[i]) PK_HIP(hipEventCreateWithFlags(&f->stage_done[i], hipEventDisableTiming));
       f->slot_seq[i] = 0;  // the stream is idle: nothing reads the old blocks any more
     }
@@ -524,20 +554,13 @@ int ct_engage(pk_filter* f) {
   int rc;
   const int Lp = f->d.lay.Lp;
   const int depth = f->ct_built ? f->ct_depth : f->colour_table_depth;
-  if (!f->ct_seen) {
-    PK_HIP(hipHostMalloc((void**)&f->ct_seen, 64, hipHostMallocDefault));
-    *f->ct_seen = 0u;
-  }
-  if (!f->ct_max_dev && (rc = dev_alloc(f, &f->ct_max_dev, 16))) return rc;
+  if ((rc = host_word(f, &f->ct_seen))) return rc;
+  if ((rc = dev_lazy(f, &f->ct_max_dev, 16))) return rc;
   const bool same_qt = memcmp(&f->ct_qt, &f->qt, sizeof(NoiseD)) == 0;
   if (f->ct_built && same_qt && f->ct_depth == depth) return PK_OK;
   if (!f->ct_tab || f->ct_depth != depth) {
     PK_HIP(hipStreamSynchronize(f->stream));
-    if (f->ct_tab) {
-      (void)hipFree(f->ct_tab);
-      f->device_bytes -= (int64_t)((size_t)f->ct_depth * 6 * Lp * sizeof(double));
-      f->ct_tab = nullptr;
-    }
+    dev_free(f, &f->ct_tab);
     if ((rc = dev_alloc(f, &f->ct_tab, (size_t)depth * 6 * Lp))) return rc;
     f->ct_depth = depth;
   }
@@ -750,25 +773,24 @@ int ensure_handoff(pk_filter* f, int B, int slots, bool lists = true, bool retry
   const int64_t need_l = lists ? rows * (int64_t)f->d.lay.Lp * (slots == kSweepSlots ? 2 : 1) : 0;
   const int64_t need_b = lists ? rows * (int64_t)std::max(B, 1) : 0;
   int rc;
-  if (retry_only && !f->fh.row_of && (rc = dev_alloc(f, &f->fh.row_of, (size_t)f->d.P))) return rc;
-  if (need_l > f->fh_cap_l) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    if (f->fh.lmpass) (void)hipFree(f->fh.lmpass);
-    f->fh.lmpass = nullptr;
-    f->fh_cap_l = 0;
-    if ((rc = dev_alloc(f, &f->fh.lmpass, (size_t)need_l))) return rc;
-    f->fh_cap_l = need_l;
-  }
-  if (need_b > f->fh_cap_b) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    if (f->fh.bcount) (void)hipFree(f->fh.bcount);
-    f->fh.bcount = nullptr;
-    f->fh_cap_b = 0;
-    if ((rc = dev_alloc(f, &f->fh.bcount, (size_t)need_b))) return rc;
-    f->fh_cap_b = need_b;
-  }
-  if (!f->fh.pflag && (rc = dev_alloc(f, &f->fh.pflag, (size_t)f->d.P))) return rc;
-  return PK_OK;
+  if (retry_only && (rc = dev_lazy(f, &f->fh.row_of, (size_t)f->d.P))) return rc;
+  if ((rc = dev_reserve(f, &f->fh.lmpass, &f->fh_cap_l, need_l, need_l))) return rc;
+  if ((rc = dev_reserve(f, &f->fh.bcount, &f->fh_cap_b, need_b, need_b))) return rc;
+  return dev_lazy(f, &f->fh.pflag, (size_t)f->d.P);
+}
+
+// ---- buffers of the sharded resample that several entry points share
+// every shard's block totals and their scan
+int ensure_global_totals(pk_filter* f, int64_t n_global_blocks) {
+  return dev_reserve_group(f, &f->gblocks_cap, n_global_blocks, n_global_blocks, want(&f->g_totals, (size_t)n_global_blocks),
+                           want(&f->g_offsets, (size_t)n_global_blocks + 1));
+}
+int ensure_hi(pk_filter* f) { return dev_lazy(f, &f->hi_dev, (size_t)f->d.P + 1); }
+// (lo, hi) of the received records: `words` int64 are wanted (two per record, three with the balanced placement).  The capacity
+// is kept in words too, rounded down to whole pairs -- the figure it had when it counted pairs, so the buffer grows when it did.
+int ensure_rlohi(pk_filter* f, int64_t words) {
+  const int64_t slack = words + words / 4;
+  return dev_reserve_group(f, &f->rlohi_cap, words, slack / 2 * 2, want(&f->rlohi_dev, (size_t)(slack + 16)));
 }
 
 inline unsigned long long* ctl_gmax_key(pk_filter* f) { return reinterpret_cast<unsigned long long*>(f->scan_dev); }
@@ -977,7 +999,7 @@ int enqueue_association(pk_filter* f, const double* blobs, int B, bool finalize,
     fh = f->fh;
     fh.n_flagged = ctl_n_flagged(f);
     if (plan.cand_slots) {  // (a list that overflows leaves the scan to the grid walk)
-      if (!f->cand_dev && (rc = dev_alloc(f, &f->cand_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
+      if ((rc = dev_lazy(f, &f->cand_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
       launch_summary_partials(f->stream, f->d, f->partial, f->out4);  // the reference pose: the particles' mean
       launch_candidates(f->stream, f->d, B, al.exact, 0, f->cand_dev, ctl_cand_over(f), nullptr, nullptr, nullptr, plan.cand_slots, f->out4);
       cand.rec = f->cand_dev;
@@ -1058,14 +1080,8 @@ int relayout(pk_filter* f, bool dense, bool keep) {
   }
   if ((rc = ct_end(f))) return rc;  // (the buffers go: nothing left to write rows into)
   PK_HIP(hipStreamSynchronize(f->stream));
-  for (int i = 0; i < 2; ++i) {
-    if (d.map[i]) (void)hipFree(d.map[i]);
-    d.map[i] = nullptr;
-    f->device_bytes -= (int64_t)((size_t)P * old.slot_bytes);
-  }
-  if (f->slot_tmp) (void)hipFree(f->slot_tmp);
-  f->slot_tmp = nullptr;
-  f->device_bytes -= (int64_t)old.slot_bytes;
+  for (int i = 0; i < 2; ++i) dev_free(f, &d.map[i]);
+  dev_free(f, &f->slot_tmp);
   d.lay = neu;
   f->dense = dense;
   d.alt = nullptr;
@@ -1192,40 +1208,9 @@ int pk_destroy(pk_filter* f) {
     (void)hipEventDestroy(t.b);
   }
   for (auto e : f->pool) (void)hipEventDestroy(e);
-  DeviceState& d = f->d;
-  for (int i = 0; i < 2; ++i) {
-    (void)hipFree(d.x[i]);
-    (void)hipFree(d.y[i]);
-    (void)hipFree(d.h[i]);
-    (void)hipFree(d.logw[i]);
-    (void)hipFree(d.src[i]);
-    (void)hipFree(d.map[i]);
-  }
-  if (f->scan_dev) (void)hipFree(f->scan_dev);
-  for (void* q : {(void*)f->fh.lmpass, (void*)f->fh.bcount, (void*)f->fh.pflag, (void*)f->fh.row_of, (void*)f->sweep_results, (void*)f->cand_dev, (void*)f->bcnt_dev, (void*)f->brec_dev, (void*)f->erec_dev, (void*)f->erec_dev2, (void*)f->binfo_dev, (void*)f->glist_dev, (void*)f->gate4_dev, (void*)f->npass_dev, (void*)f->far_dev, (void*)f->prim_dev, (void*)f->unm_dev})
-    if (q) (void)hipFree(q);
-  for (int i = 0; i < 2; ++i)
-    for (void* q : {(void*)f->grow.hyp[i], (void*)f->grow.cnt[i], (void*)f->grow.slot_id[i]})
-      if (q) (void)hipFree(q);
-  for (void* q : {(void*)f->g_totals, (void*)f->g_offsets, (void*)f->hi_dev, (void*)f->gl_clocal, (void*)f->gl_totals, (void*)f->gl_offsets, (void*)f->plan_ticket, (void*)f->idx_dev, (void*)f->srcs_dev, (void*)f->rlohi_dev})
-    if (q) (void)hipFree(q);
-  for (void* q : {(void*)d.logical[0], (void*)d.logical[1], (void*)f->bal.glogw, (void*)f->bal.clocal, (void*)f->bal.totals, (void*)f->bal.offsets,
-                  (void*)f->bal.sum, (void*)f->bal.H, (void*)f->bal.cloc, (void*)f->bal.ctot, (void*)f->bal.coff, (void*)f->bal.rel, (void*)f->bal.Hl,
-                  (void*)f->bal.alive, (void*)f->bal.bad})
-    if (q) (void)hipFree(q);
-  void* rest[] = {d.immutable, f->z_dev,  f->ids_dev,
-                  f->partial,  f->gmax,   f->clocal,    f->totals,      f->offsets,   f->sum,      f->out4, f->pose_part,
-                  f->anc,      f->slot_tmp};
-  for (void* p : rest)
-    if (p) (void)hipFree(p);
-  for (int i = 0; i < pk_filter::kRing; ++i) {
-    if (f->stage[i]) (void)hipHostFree(f->stage[i]);
-    if (f->stage_done[i]) (void)hipEventDestroy(f->stage_done[i]);
-  }
-  if (f->retry_seen) (void)hipHostFree(f->retry_seen);
-  for (void* q : {(void*)f->ct_base, (void*)f->ct_tab, (void*)f->ct_max_dev})
-    if (q) (void)hipFree(q);
-  if (f->ct_seen) (void)hipHostFree(f->ct_seen);
+  for (hipEvent_t e : f->stage_done)
+    if (e) (void)hipEventDestroy(e);
+  f->mem.release_all();
   if (f->own_stream) (void)hipStreamDestroy(f->own_stream);
   delete f;
   return PK_OK;
@@ -1251,7 +1236,7 @@ int pk_synchronize(pk_filter* f) {
 
 int64_t pk_num_particles(const pk_filter* f) { return f ? f->d.P : -1; }
 int32_t pk_num_landmarks(const pk_filter* f) { return f ? f->d.lay.L : -1; }
-int64_t pk_device_bytes(const pk_filter* f) { return f ? f->device_bytes : -1; }
+int64_t pk_device_bytes(const pk_filter* f) { return f ? (int64_t)f->mem.device_bytes() : -1; }
 
 int pk_set_measurement_noise(pk_filter* f, const double Qt[16]) {
   if (!f || !Qt) return fail(PK_ERR_INVALID, "pk_set_measurement_noise: NULL argument");
@@ -1316,7 +1301,7 @@ int pk_upload_map(pk_filter* f, const double* means, const double* covs, const u
   f->ct_updated = false;
   f->ct_eligible = false;
   if (!f->dense && lay.Lp > 2 * kPubSmallThreads && L <= kRegsMaxL) {
-    if (!f->ct_base && (rc = dev_alloc(f, &f->ct_base, (size_t)6 * lay.Lp))) return rc;
+    if ((rc = dev_lazy(f, &f->ct_base, (size_t)6 * lay.Lp))) return rc;
     PK_HIP(hipMemcpyAsync(f->ct_base, slot.data() + (size_t)F_CRR * lay.Lp * sizeof(double), (size_t)6 * lay.Lp * sizeof(double),
                           hipMemcpyHostToDevice, f->stream));
     f->ct_eligible = true;
@@ -1602,25 +1587,14 @@ static int ensure_inverse_lists(pk_filter* f, int B, int slots = kCandSlots) {
   int rc;
   B = B * (slots / kCandSlots);  // (capacity in units of eight-entry lists: sixteen-entry lists take two)
   if (B > f->bcand_cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    for (void* q : {(void*)f->bcnt_dev, (void*)f->brec_dev, (void*)f->binfo_dev, (void*)f->glist_dev, (void*)f->gate4_dev})
-      if (q) (void)hipFree(q);
-    f->gate4_dev = nullptr;
-    f->bcnt_dev = nullptr;
-    f->brec_dev = nullptr;
-    f->binfo_dev = nullptr;
-    f->glist_dev = nullptr;
-    f->bcand_cap = 0;
     const int64_t cap = (int64_t)B + B / 4 + 64;
-    if ((rc = dev_alloc(f, &f->bcnt_dev, (size_t)cap))) return rc;
-    if ((rc = dev_alloc(f, &f->brec_dev, (size_t)cap))) return rc;
-    if ((rc = dev_alloc(f, &f->binfo_dev, (size_t)cap))) return rc;
-    if ((rc = dev_alloc(f, &f->glist_dev, 2 * (size_t)cap + 1 + 256 + 16))) return rc;
-    if ((rc = dev_alloc(f, &f->gate4_dev, (size_t)cap))) return rc;
+    if ((rc = dev_reserve_group(f, &f->bcand_cap, (int64_t)B, cap, want(&f->bcnt_dev, (size_t)cap), want(&f->brec_dev, (size_t)cap),
+                                want(&f->binfo_dev, (size_t)cap), want(&f->glist_dev, 2 * (size_t)cap + 1 + 256 + 16),
+                                want(&f->gate4_dev, (size_t)cap))))
+      return rc;
     // (empty inverse lists: k_candidates appends to them, k_cand_entries empties them again behind its last read)
     PK_HIP(hipMemsetAsync(f->bcnt_dev, 0, (size_t)cap * sizeof(unsigned), f->stream));
     PK_HIP(hipMemsetAsync(f->brec_dev, 0xFF, (size_t)cap * sizeof(uint4), f->stream));
-    f->bcand_cap = cap;
   }
   return PK_OK;
 }
@@ -1629,12 +1603,12 @@ static int ensure_list_buffers(pk_filter* f, const ScanPlan& plan, int B) {
   int rc;
   const size_t Lpp = (size_t)f->d.lay.Lp + kCandSpare;
   const bool big = plan.kind == ScanKind::PubBig;  // sixteen-entry lists both ways
-  if (!f->cand_dev && (rc = dev_alloc(f, &f->cand_dev, Lpp * 3))) return rc;
+  if ((rc = dev_lazy(f, &f->cand_dev, Lpp * 3))) return rc;
   if (!plan.publish) return PK_OK;
-  if (big ? !f->erec_dev2 && (rc = dev_alloc(f, &f->erec_dev2, Lpp * 2)) : !f->erec_dev && (rc = dev_alloc(f, &f->erec_dev, Lpp))) return rc;
-  if (!f->npass_dev && (rc = dev_alloc(f, &f->npass_dev, Lpp))) return rc;
-  if (!f->far_dev && (rc = dev_alloc(f, &f->far_dev, Lpp * 3))) return rc;
-  if (big && !f->prim_dev && (rc = dev_alloc(f, &f->prim_dev, prim_table_uint4(f->d.lay.Lp)))) return rc;
+  if ((rc = big ? dev_lazy(f, &f->erec_dev2, Lpp * 2) : dev_lazy(f, &f->erec_dev, Lpp))) return rc;
+  if ((rc = dev_lazy(f, &f->npass_dev, Lpp))) return rc;
+  if ((rc = dev_lazy(f, &f->far_dev, Lpp * 3))) return rc;
+  if (big && (rc = dev_lazy(f, &f->prim_dev, prim_table_uint4(f->d.lay.Lp)))) return rc;
   return ensure_inverse_lists(f, B, plan.cand_slots);
 }
 // ref: the particle whose MAP the candidate lists are made from -- particle 0, or in a split step the first particle of the range
@@ -1719,15 +1693,7 @@ static int onepass_launch(pk_filter* f, const AssocLaunch& al, int B, const Obse
 // k_observe_sweep's per-workgroup result lists
 static int ensure_sweep_results(pk_filter* f, const SweepPlan& plan) {
   const size_t need = (size_t)plan.grid * plan.results_per_wg;
-  if (need <= f->sweep_cap) return PK_OK;
-  PK_HIP(hipStreamSynchronize(f->stream));
-  if (f->sweep_results) (void)hipFree(f->sweep_results);
-  f->sweep_results = nullptr;
-  f->sweep_cap = 0;
-  int rc;
-  if ((rc = dev_alloc(f, &f->sweep_results, need))) return rc;
-  f->sweep_cap = need;
-  return PK_OK;
+  return dev_reserve(f, &f->sweep_results, &f->sweep_cap, need, need);
 }
 // 3. what the one-pass kernel flagged, over all particles: second chance, then the general kernels (which swap the map buffers)
 static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const ObserveExtras& ex, const CandTable& cand) {
@@ -1756,7 +1722,7 @@ static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const Obse
     e3.sweep_only_value = 2;
     e3.n_flagged = ctl_n_flagged(f);
     launch_observe_sweep(f->stream, f->d, B, al.exact, al.order, fr, f->qt, e3, plan, f->sweep_results);
-    if (!f->retry_seen && hipHostMalloc((void**)&f->retry_seen, 64, hipHostMallocDefault) == hipSuccess) *f->retry_seen = 0u;
+    (void)host_word(f, &f->retry_seen);  // (without it the rows do not grow: no error)
     if (f->retry_seen) (void)hipMemcpyAsync(f->retry_seen, ctl_retry_rows(f), sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
     (void)hipGetLastError();
   }
@@ -1861,15 +1827,7 @@ static int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int3
   if (grow && plan.onepass()) {
     // round 6: the one-pass kernel leaves every particle's unmatched blobs as a bit row (scan order)
     const int words = 2 * ((B + 63) / 64);
-    if ((int64_t)f->d.P * words > f->unm_cap) {
-      PK_HIP(hipStreamSynchronize(f->stream));
-      if (f->unm_dev) (void)hipFree(f->unm_dev);
-      f->unm_dev = nullptr;
-      f->unm_cap = 0;
-      const int64_t cap = (int64_t)f->d.P * (words + words / 4 + 2);
-      if ((rc = dev_alloc(f, &f->unm_dev, (size_t)cap))) return rc;
-      f->unm_cap = cap;
-    }
+    if ((rc = dev_reserve(f, &f->unm_dev, &f->unm_cap, (int64_t)f->d.P * words, (int64_t)f->d.P * (words + words / 4 + 2)))) return rc;
     f->unm_words = words;
     ex.unm = f->unm_dev;
     ex.unm_words = words;
@@ -2393,17 +2351,8 @@ int pk_shard_offspring(pk_filter* f, const double* global_totals, int64_t n_glob
                 (long long)first_block, (long long)f->nblocks, (long long)n_global_blocks);
   int rc;
   if ((rc = use_device(f))) return rc;
-  if (n_global_blocks > f->gblocks_cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    if (f->g_totals) (void)hipFree(f->g_totals);
-    if (f->g_offsets) (void)hipFree(f->g_offsets);
-    f->g_totals = f->g_offsets = nullptr;
-    f->gblocks_cap = 0;
-    if ((rc = dev_alloc(f, &f->g_totals, (size_t)n_global_blocks))) return rc;
-    if ((rc = dev_alloc(f, &f->g_offsets, (size_t)n_global_blocks + 1))) return rc;
-    f->gblocks_cap = n_global_blocks;
-  }
-  if (!f->hi_dev && (rc = dev_alloc(f, &f->hi_dev, (size_t)f->d.P + 1))) return rc;
+  if ((rc = ensure_global_totals(f, n_global_blocks))) return rc;
+  if ((rc = ensure_hi(f))) return rc;
   PK_HIP(hipMemcpyAsync(f->g_totals, global_totals, (size_t)n_global_blocks * sizeof(double), hipMemcpyHostToDevice,
                         f->stream));
   {
@@ -2433,7 +2382,7 @@ int pk_pack_particles(pk_filter* f, const int64_t* local_idx, int64_t n, void* d
   if (n == 0) return PK_OK;
   int rc;
   if ((rc = use_device(f))) return rc;
-  if (!f->idx_dev && (rc = dev_alloc(f, &f->idx_dev, (size_t)f->d.P))) return rc;
+  if ((rc = dev_lazy(f, &f->idx_dev, (size_t)f->d.P))) return rc;
   PK_HIP(hipMemcpyAsync(f->idx_dev, local_idx, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
   {
     Span t(f, PK_T_RESAMPLE);
@@ -2458,7 +2407,7 @@ int pk_adopt_particles(pk_filter* f, const int64_t* src, const void* dev_buf, in
     f->src_identity = false;
     if ((rc = materialise(f))) return rc;
   }
-  if (!f->srcs_dev && (rc = dev_alloc(f, &f->srcs_dev, (size_t)P))) return rc;
+  if ((rc = dev_lazy(f, &f->srcs_dev, (size_t)P))) return rc;
   PK_HIP(hipMemcpyAsync(f->srcs_dev, src, (size_t)P * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
   {
     Span t(f, PK_T_RESAMPLE);
@@ -2504,17 +2453,8 @@ int pk_shard_plan_dev(pk_filter* f, const double* dev_global_totals, int64_t n_g
                 (long long)f->nblocks, (long long)first_block, (long long)n_global_blocks, (long long)f->d.P, world);
   int rc;
   if ((rc = use_device(f))) return rc;
-  if (n_global_blocks > f->gblocks_cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    if (f->g_totals) (void)hipFree(f->g_totals);
-    if (f->g_offsets) (void)hipFree(f->g_offsets);
-    f->g_totals = f->g_offsets = nullptr;
-    f->gblocks_cap = 0;
-    if ((rc = dev_alloc(f, &f->g_totals, (size_t)n_global_blocks))) return rc;
-    if ((rc = dev_alloc(f, &f->g_offsets, (size_t)n_global_blocks + 1))) return rc;
-    f->gblocks_cap = n_global_blocks;
-  }
-  if (!f->hi_dev && (rc = dev_alloc(f, &f->hi_dev, (size_t)f->d.P + 1))) return rc;
+  if ((rc = ensure_global_totals(f, n_global_blocks))) return rc;
+  if ((rc = ensure_hi(f))) return rc;
   if (!f->plan_ticket) {
     if ((rc = dev_alloc(f, &f->plan_ticket, (size_t)1))) return rc;
     PK_HIP(hipMemsetAsync(f->plan_ticket, 0, sizeof(unsigned), f->stream));
@@ -2555,19 +2495,10 @@ int pk_shard_plan_global_dev(pk_filter* f, const double* dev_global_logw, int64_
   int rc;
   if ((rc = use_device(f))) return rc;
   const int64_t nbg = (global_particles + kScanBlock - 1) / kScanBlock;
-  if (global_particles > f->gl_cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    for (double** q : {&f->gl_clocal, &f->gl_totals, &f->gl_offsets}) {
-      if (*q) (void)hipFree(*q);
-      *q = nullptr;
-    }
-    f->gl_cap = 0;
-    if ((rc = dev_alloc(f, &f->gl_clocal, (size_t)global_particles))) return rc;
-    if ((rc = dev_alloc(f, &f->gl_totals, (size_t)nbg))) return rc;
-    if ((rc = dev_alloc(f, &f->gl_offsets, (size_t)nbg + 1))) return rc;
-    f->gl_cap = global_particles;
-  }
-  if (!f->hi_dev && (rc = dev_alloc(f, &f->hi_dev, (size_t)P + 1))) return rc;
+  if ((rc = dev_reserve_group(f, &f->gl_cap, global_particles, global_particles, want(&f->gl_clocal, (size_t)global_particles),
+                              want(&f->gl_totals, (size_t)nbg), want(&f->gl_offsets, (size_t)nbg + 1))))
+    return rc;
+  if ((rc = ensure_hi(f))) return rc;
   Span t(f, PK_T_WEIGHTS);
   // exactly the kernels of the 1-GPU resample on the whole filter's log-weights: same blocks, same additions, same bits
   launch_scan_local_of(f->stream, dev_global_logw, global_particles, dev_gmax ? dev_gmax : f->gmax, weight_domain, f->gl_clocal,
@@ -2640,14 +2571,7 @@ int pk_shard_adopt_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t
     f->src_identity = false;
     if ((rc = materialise(f))) return rc;
   }
-  if (n_received > f->rlohi_cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    if (f->rlohi_dev) (void)hipFree(f->rlohi_dev);
-    f->rlohi_dev = nullptr;
-    f->rlohi_cap = 0;
-    if ((rc = dev_alloc(f, &f->rlohi_dev, (size_t)(2 * n_received + 2 * n_received / 4 + 16)))) return rc;
-    f->rlohi_cap = n_received + n_received / 4;
-  }
+  if ((rc = ensure_rlohi(f, 2 * n_received))) return rc;
   Span t(f, PK_T_RESAMPLE);
   launch_adopt_dev(f->stream, f->d, f->hi_dev, (int64_t)rank * f->d.P, static_cast<const unsigned char*>(dev_recv),
                    n_received, f->rlohi_dev);
@@ -2690,14 +2614,7 @@ int pk_shard_adopt_remote_dev(pk_filter* f, int32_t rank, const void* dev_recv, 
   f->adopt_local_done = false;
   int rc;
   if ((rc = use_device(f))) return rc;
-  if (n_received > f->rlohi_cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    if (f->rlohi_dev) (void)hipFree(f->rlohi_dev);
-    f->rlohi_dev = nullptr;
-    f->rlohi_cap = 0;
-    if ((rc = dev_alloc(f, &f->rlohi_dev, (size_t)(2 * n_received + 2 * n_received / 4 + 16)))) return rc;
-    f->rlohi_cap = n_received + n_received / 4;
-  }
+  if ((rc = ensure_rlohi(f, 2 * n_received))) return rc;
   Span t(f, PK_T_RESAMPLE);
   const int64_t base = (int64_t)rank * f->d.P;
   launch_adopt_dev(f->stream, f->d, f->hi_dev, base, static_cast<const unsigned char*>(dev_recv), n_received, f->rlohi_dev, 2,
@@ -2722,10 +2639,9 @@ static int ensure_logical(pk_filter* f) {
   DeviceState& d = f->d;
   if (d.logical[0]) return PK_OK;
   int rc;
-  int64_t *a = nullptr, *b = nullptr;
-  if ((rc = dev_alloc(f, &a, (size_t)d.P))) return rc;
-  if ((rc = dev_alloc(f, &b, (size_t)d.P))) {
-    (void)hipFree(a);
+  int64_t *a = nullptr, *b = nullptr;  // (a kernel takes a non-null logical[] for indices: both go in, or neither)
+  if ((rc = dev_alloc(f, &a, (size_t)d.P)) || (rc = dev_alloc(f, &b, (size_t)d.P))) {
+    dev_free(f, &a);
     return rc;
   }
   launch_iota64(f->stream, a, d.P, d.global_offset);
@@ -2817,31 +2733,17 @@ int pk_shard_plan_balanced_dev(pk_filter* f, const double* dev_global_state, int
   if ((rc = ensure_logical(f))) return rc;
   BalancedBuffers& b = f->bal;
   const int64_t nbg = (Pg + kScanBlock - 1) / kScanBlock;
-  if (Pg > b.cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    for (void* q : {(void*)b.glogw, (void*)b.clocal, (void*)b.totals, (void*)b.offsets, (void*)b.H, (void*)b.cloc, (void*)b.ctot, (void*)b.coff})
-      if (q) (void)hipFree(q);
-    b.glogw = b.clocal = b.totals = b.offsets = nullptr;
-    b.H = nullptr;
-    b.cloc = b.ctot = b.coff = nullptr;
-    b.cap = 0;
-    if ((rc = dev_alloc(f, &b.glogw, (size_t)Pg))) return rc;
-    if ((rc = dev_alloc(f, &b.clocal, (size_t)Pg))) return rc;
-    if ((rc = dev_alloc(f, &b.totals, (size_t)nbg))) return rc;
-    if ((rc = dev_alloc(f, &b.offsets, (size_t)nbg + 1))) return rc;
-    if ((rc = dev_alloc(f, &b.H, (size_t)Pg + 1))) return rc;
-    if ((rc = dev_alloc(f, &b.cloc, (size_t)Pg))) return rc;
-    if ((rc = dev_alloc(f, &b.ctot, (size_t)nbg))) return rc;
-    if ((rc = dev_alloc(f, &b.coff, (size_t)nbg + 1))) return rc;
-    if (!b.sum && (rc = dev_alloc(f, &b.sum, (size_t)1))) return rc;
-    if (!b.rel && (rc = dev_alloc(f, &b.rel, (size_t)P + 1))) return rc;
-    if (!b.Hl && (rc = dev_alloc(f, &b.Hl, (size_t)P))) return rc;
-    if (!b.alive && (rc = dev_alloc(f, &b.alive, (size_t)P))) return rc;
-    if (!b.bad) {
-      if ((rc = dev_alloc(f, &b.bad, (size_t)1))) return rc;
-      PK_HIP(hipMemsetAsync(b.bad, 0, sizeof(int), f->stream));
-    }
-    b.cap = Pg;
+  if ((rc = dev_reserve_group(f, &b.cap, Pg, Pg, want(&b.glogw, (size_t)Pg), want(&b.clocal, (size_t)Pg), want(&b.totals, (size_t)nbg),
+                              want(&b.offsets, (size_t)nbg + 1), want(&b.H, (size_t)Pg + 1), want(&b.cloc, (size_t)Pg),
+                              want(&b.ctot, (size_t)nbg), want(&b.coff, (size_t)nbg + 1))))
+    return rc;
+  if ((rc = dev_lazy(f, &b.sum, (size_t)1))) return rc;
+  if ((rc = dev_lazy(f, &b.rel, (size_t)P + 1))) return rc;
+  if ((rc = dev_lazy(f, &b.Hl, (size_t)P))) return rc;
+  if ((rc = dev_lazy(f, &b.alive, (size_t)P))) return rc;
+  if (!b.bad) {
+    if ((rc = dev_alloc(f, &b.bad, (size_t)1))) return rc;
+    PK_HIP(hipMemsetAsync(b.bad, 0, sizeof(int), f->stream));
   }
   Span t(f, PK_T_WEIGHTS);
   launch_bal_plan(f->stream, f->d, dev_global_state, Pg, world, rank, dev_gmax ? dev_gmax : f->gmax, weight_domain, u, b, dev_table);
@@ -2959,14 +2861,7 @@ int pk_shard_adopt_balanced_dev(pk_filter* f, const int64_t* table, int32_t worl
     f->src_identity = false;
     if ((rc = materialise(f))) return rc;
   }
-  if (3 * n_received > 2 * f->rlohi_cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    if (f->rlohi_dev) (void)hipFree(f->rlohi_dev);
-    f->rlohi_dev = nullptr;
-    f->rlohi_cap = 0;
-    if ((rc = dev_alloc(f, &f->rlohi_dev, (size_t)(3 * n_received + 3 * n_received / 4 + 16)))) return rc;
-    f->rlohi_cap = (3 * n_received + 3 * n_received / 4) / 2;
-  }
+  if ((rc = ensure_rlohi(f, 3 * n_received))) return rc;
   Span t(f, PK_T_RESAMPLE);
   const size_t stride = record_stride(f);
   launch_bal_adopt(f->stream, f->d, f->bal, m, static_cast<const unsigned char*>(dev_recv), n_received, f->rlohi_dev, mode, stride,
