@@ -1,0 +1,434 @@
+// The filter behind the C ABI (include/parakeet_slam.h): struct pk_filter and what every part of the host layer needs to work on
+// it.  Private to the pk_api*.hip files, which divide the ABI between them:
+//   pk_api.hip          lifecycle, transfers, motion, resample, the step, new-landmark bookkeeping, options, timing, the probe
+//   pk_api_observe.hip  the observe pipeline: staging, routing, association, the one-pass stages, the colour table's host side
+//   pk_api_shard.hip    the multi-GPU protocol: host-side, device-resident and balanced
+// No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/parakeet_slam.h"
+#include "pk_devmem.hpp"
+#include "pk_kernels.hpp"
+#include "pk_pub_layout.hpp"
+
+using namespace pk;
+
+// the status `code`, with the message pk_last_error reports (one thread-local string, in pk_api.hip)
+int fail(int code, const char* fmt, ...);
+
+#define PK_HIP(call)                                                                         \
+  do {                                                                                       \
+    hipError_t e_ = (call);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      (void)hipGetLastError();                                                               \
+      return fail(e_ == hipErrorOutOfMemory ? PK_ERR_NOMEM : PK_ERR_HIP, "%s failed: %s (%s:%d)", #call, \
+                  hipGetErrorString(e_), __FILE__, __LINE__);                                \
+    }                                                                                        \
+  } while (0)
+
+// Kernel launches report configuration errors (too much dynamic LDS, bad grid) through the
+// runtime's last-error slot, not through a return value: every entry point that enqueued kernels
+// asks for it before it reports success.
+#define PK_LAUNCH_CHECK(what)                                                                \
+  do {                                                                                       \
+    hipError_t e_ = hipGetLastError();                                                       \
+    if (e_ != hipSuccess)                                                                    \
+      return fail(PK_ERR_HIP, "%s: a kernel launch failed: %s", what, hipGetErrorString(e_)); \
+  } while (0)
+
+struct TimedSpan {
+  int slot;
+  hipEvent_t a, b;
+};
+
+// what the filter's memory registry (pk_devmem.hpp) allocates and frees with
+struct HipRaw {
+  int device_alloc(void** p, size_t bytes) {
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return PK_OK;
+    (void)hipGetLastError();
+    return fail(PK_ERR_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+  }
+  void device_free(void* p) { (void)hipFree(p); }
+  int host_alloc(void** p, size_t bytes, unsigned flags) {
+    hipError_t e = hipHostMalloc(p, bytes, flags);
+    if (e == hipSuccess) return PK_OK;
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? PK_ERR_NOMEM : PK_ERR_HIP, "hipHostMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+  }
+  void host_free(void* p) { (void)hipHostFree(p); }
+};
+
+// The kernels of one maximum-likelihood scan ("Routing": the table of kinds against their conditions).
+// The observe's planner (pk_api_observe.hip) decides it once per scan; every stage of the observe follows it.
+enum class ScanKind {
+  Brute,         // k_assoc_brute + k_observe
+  General,       // k_assoc_grid + k_observe
+  HandoffFast,   // k_assoc_grid's hand-off + k_observe_fast
+  HandoffSweep,  // ... + k_observe_sweep
+  // the one-pass kinds: the association launches nothing, one kernel does gates + EKF, what it flags goes to the kernels above
+  Fused,         // k_step_fused
+  PubSmall,      // k_step_pub<1, 256>
+  Regs,          // k_step_regs, no publish table
+  PubRegs,       // k_step_pub<2, 512>, k_step_regs behind it for the scans it stands back from
+  Pub,           // k_step_pub<2, 512> alone (pruned lists, growing maps)
+  PubBig,        // k_step_pub_big, k_step_pub_duo in front of it with "pub_duo"
+};
+struct ScanPlan {
+  ScanKind kind = ScanKind::Brute;
+  int route = PK_ROUTE_ML_GENERAL;  // what pk_observe_route reports
+  // the hand-off: slots per landmark, lists allocated (for every particle on the hand-off kinds, for the second-chance rows behind
+  // k_step_regs / k_step_pub / k_step_pub_big), the second chance runs
+  int slots = kFastSlots;
+  bool lists = false;
+  bool retry = false;
+  // the reference particle's candidate lists: entries per list (0: none made), inverse lists and the publish table's layout
+  // (k_cand_entries) for ecap entries, look-alikes beyond the underflow edge pruned
+  int cand_slots = 0;
+  bool publish = false;
+  int ecap = 0;
+  bool far = false;
+  DuoLimits duo;            // PubBig: what k_step_pub_duo has room for (all zero: the instance is off)
+  // a scan the kernel stands back from, with no stand-by kernel behind it, flags its particles for the fall-back kernels: inside
+  // k_cand_entries when the launches cover every particle, else by a k_flag_range_if launch per range (3 us a step)
+  bool flag_fold = false, flag_range = false;
+  bool colour_table = false;  // Pub: the table-mode instance
+  bool onepass() const { return kind >= ScanKind::Fused; }
+  bool ranged() const { return kind >= ScanKind::Regs; }  // runs on particle ranges (pk_observe_staged_range)
+};
+
+struct AssocLaunch {
+  ScanPlan plan;
+  BlobGrid grid{};
+  int n9 = 0;
+  const unsigned char* tables = nullptr;
+  const double* blobs = nullptr;
+  const double* dir = nullptr;
+  const double* exact = nullptr;
+  const unsigned short* order = nullptr;
+};
+
+// What pk_set_option sets: every tuning knob with its default.  (Protocol state that an option name also reaches -- the loopback
+// bounds of the sharded tests -- stays with the shard fields of pk_filter.)
+struct Options {
+  int assoc_kernel = 0;  // 0 = colour-grid kernel, 1 = brute-force reference kernel
+  int assoc_dup = 1;     // grid kernel: use the 9x column-duplicated index list when it fits in LDS
+  int fast_observe = 1;  // association hand-off + k_observe_fast (L <= 512) / k_observe_sweep; 2 = always the sweep kernel
+  int timing_stride = 1; // a timing slot that is switched on (timing_mask) is bracketed every timing_stride-th time it comes up (sampling keeps the probe cheap)
+  int upload_kernel = 1; // per-scan block: read from pinned host memory by a kernel (1) or hipMemcpyAsync (0)
+  int fused_step = 1;    // L <= 512 and small scan tables: k_step_fused instead of hand-off + k_observe_fast
+  int cand_lists = 1;    // k_step_regs: gates against the reference particle's candidate lists (k_candidates) instead of the grid walk
+  int pub_step = 1;      // ... with the contested blobs settled by static publish / subscribe (k_step_pub) while the publish table fits LDS
+  int pub_small = -1;    // L <= 512: k_step_pub<256 lanes> instead of k_step_fused -- 1 / 0, or -1 (default): where it is measured faster
+                         // (kPubSmallAutoWork, pk_api_observe.hip)
+  int far_prune = 1;             // look-alikes certainly beyond the underflow edge leave the candidate lists once per scan (0: as round 4)
+  int duo_on = 0;        // "pub_duo" (measured, off: DESIGN.md section 4): 2 048 < L <= 5 120, scans whose publish table fits its share of a CU's LDS go to
+                         // k_step_pub_duo -- 1: two 512-lane workgroups per CU (<= 128 VGPRs), 2: three 256-lane workgroups (<= 168) -- the others to k_step_pub_big
+  int duo_park_limit = -1;  // >= 0: k_step_pub_duo's overflow area is treated as this small (tests: particles that need more go to the fall-back kernels)
+  int pub_entry_limit = 0;  // > 0: the publish table is treated as this small (tests: scans whose table "does not fit" fall back to k_step_regs)
+  int regs_step = 1;     // 512 < L <= 2048 and scan tables that fit LDS: k_step_regs (one pass, map in registers)
+  int regs_retry = 1;    // k_step_regs: 1 = the particles it flags get a second chance (eight-slot hand-off + k_observe_sweep) before the general kernels
+  int regs_warm = 1;     // k_step_regs: L2 warming of the next particle's slot: 0 none, 1 its mean rows (default), 2 the whole slot (measured slower)
+  int split_reserve_cus = 16;  // CUs the first part of a split step leaves free for the all-to-all's kernels
+  int colour_table_depth = 1024;  // option: levels of the table
+  int colour_table_margin = -1;   // option: the host leaves the mode this many levels short of the table's end; -1: min(16, depth / 2); 0: never
+  int colour_table = -1;          // option: -1 auto, 0 off, 1 as auto
+};
+
+// One row per knob: the name a caller gives, the member, how the value is taken, the inclusive range, the refusal outside it.
+enum class Take {
+  Range,  // as given, inside [lo, hi]
+  Flag,   // value != 0
+  Tri,    // "pub_small": negative -> -1 (automatic), else value != 0
+};
+struct OptionRow {
+  const char* name;
+  int Options::*member;
+  Take take;
+  int64_t lo, hi;
+  const char* refusal;
+};
+inline constexpr OptionRow kOptionTable[] = {
+    {"assoc_kernel", &Options::assoc_kernel, Take::Range, 0, 1, "assoc_kernel: 0 (colour grid) or 1 (brute force)"},
+    {"assoc_dup", &Options::assoc_dup, Take::Flag, 0, 0, nullptr},
+    {"fast_observe", &Options::fast_observe, Take::Range, 0, 3,
+     "fast_observe: 0 (general kernels), 1 (default), 2 (always the sweep kernel) or 3 (... with eight slots)"},
+    {"timing_stride", &Options::timing_stride, Take::Range, 1, 1000000, "timing_stride: 1 .. 1000000"},
+    {"upload_kernel", &Options::upload_kernel, Take::Flag, 0, 0, nullptr},
+    {"fused_step", &Options::fused_step, Take::Flag, 0, 0, nullptr},
+    {"cand_lists", &Options::cand_lists, Take::Flag, 0, 0, nullptr},
+    {"pub_step", &Options::pub_step, Take::Flag, 0, 0, nullptr},
+    {"pub_small", &Options::pub_small, Take::Tri, 0, 0, nullptr},
+    {"far_prune", &Options::far_prune, Take::Flag, 0, 0, nullptr},
+    {"pub_duo", &Options::duo_on, Take::Range, 0, 2,
+     "pub_duo: 0 (off), 1 (two 512-lane workgroups per CU) or 2 (three 256-lane workgroups per CU)"},
+    {"pub_duo_park_limit", &Options::duo_park_limit, Take::Range, -1, 65535, "pub_duo_park_limit: -1 (what LDS holds) .. 65535"},
+    {"pub_entry_limit", &Options::pub_entry_limit, Take::Range, 0, 65534, "pub_entry_limit: 0 (what LDS holds) .. 65534"},
+    {"regs_step", &Options::regs_step, Take::Flag, 0, 0, nullptr},
+    {"regs_retry", &Options::regs_retry, Take::Range, 0, 1, "regs_retry: 0 or 1"},
+    {"regs_warm", &Options::regs_warm, Take::Range, 0, 2, "regs_warm: 0 (off), 1 (mean rows) or 2 (whole slot)"},
+    {"split_reserve_cus", &Options::split_reserve_cus, Take::Range, 0, 128, "split_reserve_cus: 0..128"},
+    // (takes effect when the table is next built: at the first table-mode scan behind a pk_upload_map)
+    {"colour_table_depth", &Options::colour_table_depth, Take::Range, 8, 32768,
+     "colour_table_depth: 8 .. 32768 levels (the table stays below 4 GB: 32-bit offsets)"},
+    {"colour_table_margin", &Options::colour_table_margin, Take::Range, -1, 32768,
+     "colour_table_margin: -1 (auto), 0 (the host never leaves the mode for the table's end) or levels"},
+    // "colour_table" itself is taken by pk_set_option in code: switching it off in mid-run gives the slots their colour rows back
+};
+
+struct pk_filter {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  DeviceState d{};
+  NoiseD qt{0.1, 0.1, 0.0, 0.0, 0.1, 0.0, 0.1};
+  double qt16[16] = {0.1, 0, 0, 0, 0, 0.1, 0, 0, 0, 0, 0.1, 0, 0, 0, 0, 0.1};  // the same, dense (prkt_core_v2.py:50-53)
+  bool qt_dense = false;   // Qt couples bearing and colour or is not symmetric: only the dense kernels take it
+  bool dense = false;      // maps in the dense 30-row layout (pk_layout.hpp): the general dense kernels run the observes
+  std::vector<double> dense_staged;  // pk_stage_scan in dense mode: the blobs, kept on the host
+  bool map_loaded = false;
+  bool src_identity = true;
+  int64_t nblocks = 0;  // weight-scan blocks
+  DevMem<HipRaw> mem;   // owns every device and pinned block below and in d, fh, grow, bal (dev_alloc / dev_reserve / host_alloc)
+  // workspaces
+  double* z_dev = nullptr;        // P x 3
+  unsigned char* scan_dev = nullptr;  // per-scan block: ctl | blobs | chains or association tables
+  size_t scan_cap = 0;
+  bool gmax_fused = false;  // ctl holds the max of the current log-weights (set by observe)
+  int32_t* ids_dev = nullptr;     // P x B
+  int64_t ids_cap = 0;
+  double* g_totals = nullptr;   // sharded resample: every shard's block totals
+  double* g_offsets = nullptr;
+  int64_t gblocks_cap = 0;
+  double* gl_clocal = nullptr;  // global-scan mode of the sharded resample: block-local scans of ALL particles' weights
+  double* gl_totals = nullptr;
+  double* gl_offsets = nullptr;
+  int64_t gl_cap = 0;
+  int64_t* hi_dev = nullptr;    // P + 1
+  unsigned* plan_ticket = nullptr;  // workgroup counter of the one-launch shard plan
+  int64_t* idx_dev = nullptr;   // P
+  int64_t* srcs_dev = nullptr;  // P
+  int64_t* rlohi_dev = nullptr; // (lo, hi) of the received records
+  int64_t rlohi_cap = 0;
+  BalancedBuffers bal{};        // balanced placement of the sharded filter: the plan's tables (every rank holds the whole plan)
+  int64_t bal_m = -1;           // slots this rank's own children fill in the plan that is being carried out (-1: none)
+  int64_t bal_loop_keep = -1;   // "balanced_loopback_keep" (debug, one-rank tests of the exchange): the next balanced adoption fills only the
+                                // slots [0, keep) with this rank's own children; the slots [keep, P) come from records -- which the caller
+                                // packs with pk_shard_pack_balanced_loop_dev and sends through the all-to-all to itself
+  int64_t loop_lo = INT64_MIN, loop_hi = INT64_MAX;  // "split_loopback_lo/hi" (debug): local slots outside come from records
+  Options opt;                  // the tuning knobs (pk_set_option)
+  // host half of an ML scan upload done ahead of time (pk_stage_scan): tables built in a staging slot
+  struct Staged {
+    bool valid = false;
+    int B = 0;
+    unsigned char* st = nullptr;
+    int slot = 0;
+    BlobGrid g{};
+    int n9 = 0;
+    bool use_grid = false;
+    size_t tab_bytes = 0;
+    bool uploaded = false;  // pk_step sent the block to the device together with the motion kernel
+  } staged;
+  int route = PK_ROUTE_NONE;  // kernels used by the last observe
+  unsigned* bcnt_dev = nullptr;  // [bcand_cap] entries of the blobs' inverse candidate lists
+  uint4* brec_dev = nullptr;     // [bcand_cap] the lists
+  int64_t bcand_cap = 0;
+  uint4* cand_dev = nullptr;  // [Lp + kCandSpare][3] candidate records (two or three uint4 per landmark in use)
+  uint4* erec_dev = nullptr;     // [Lp] publish entries of every landmark's candidates (k_cand_entries)
+  uint4* erec_dev2 = nullptr;    // [Lp][2] the same for sixteen-entry lists (k_step_pub_big)
+  unsigned* binfo_dev = nullptr; // [bcand_cap] per blob: first entry | contenders << 16
+  unsigned char* npass_dev = nullptr; // [Lp + kCandSpare] per landmark: blobs inside the reference particle's own gates (k_candidates)
+  unsigned* unm_dev = nullptr;   // growing maps on the publish / subscribe routes: [P][unm_words] every particle's unmatched blobs, bits in scan order
+  int unm_words = 0;
+  int64_t unm_cap = 0;
+  bool grow_bits = false;        // the last observe's one-pass kernel left those rows (k_new_landmarks reads them where the particle was not handed on)
+  uint4* prim_dev = nullptr;     // the two-pass kernels' primary-blob table: every landmark's first candidate in landmark order (prim_table_uint4; k_cand_entries)
+  float4* gate4_dev = nullptr;   // [bcand_cap] every blob's bearing and colour as float: k_step_pub_big's first look (k_cand_entries)
+  uint4* far_dev = nullptr;      // [Lp + kCandSpare][3] per landmark: the bound its list was pruned with | its far list (k_candidates, pk_pub_math.hpp)
+  unsigned* glist_dev = nullptr; // [bcand_cap + 1 + 256] the same for the blobs several landmarks list, compacted; then their number; then the octet orders of k_step_pub (128 u16) and k_step_pub_big (384 u16)
+  // a split observe in progress (pk_observe_staged_range): what the first call set up for the later ones
+  struct Split {
+    bool active = false;
+    AssocLaunch al;
+    CandTable cand;
+    int B = 0;
+    bool reset = false;
+  } split;
+  // The colour table (pk_colour.hpp): while every map descends from one pk_upload_map the colour block of a landmark is
+  // a function of (landmark, update count), and k_step_pub's 512-lane instances take it from ct_tab instead of streaming six rows per
+  // landmark in and out of every slot.  The slots' colour rows go stale then (colour_rows_valid) and are written back from the table
+  // whenever anything else wants them (ensure_colour_rows).
+  bool ct_eligible = false;       // the maps came from pk_upload_map and nothing has ended the mode since
+  bool ct_updated = false;        // some landmark may be off level 0: an observe has run since that upload (pk_set_measurement_noise clears
+                                  // it again where ct_maps_untouched finds every count of the live buffer at 0 still)
+  bool ct_sharded = false;        // a shard / pack / adopt call was made on this filter: never
+  bool ct_built = false;          // ct_tab holds the levels of ct_base under ct_qt
+  bool ct_engaged = false;        // the last observe did, and nothing has ended the mode since
+  bool colour_rows_valid = true;
+  double* ct_base = nullptr;      // [6][Lp] the uploaded colour rows
+  double* ct_tab = nullptr;       // [ct_depth][6][Lp]
+  int ct_depth = 0;
+  NoiseD ct_qt{};
+  unsigned* ct_max_dev = nullptr; // word 0: the highest level a table-mode kernel has read since the upload; word 1: ct_maps_untouched's
+                                  // flag (some count of the live buffer is not 0); words 2, 3 free
+  unsigned* ct_seen = nullptr;    // pinned host words.  0: that figure, copied behind every table-mode scan (the last finished scan's, or the
+                                  // one before); 1: ct_maps_untouched's flag, read behind a synchronisation
+  int64_t ct_scans = 0, ct_whole = 0;  // scans taken in the mode, whole-buffer materialisations
+  bool adopt_local_done = false;  // pk_shard_adopt_local_dev made the new generation current; pk_shard_adopt_remote_dev may fill it
+  int pub_ecap = 0;       // k_step_pub was prepared for the current scan with this many publish entries (0: not prepared)
+  uint4* sweep_results = nullptr;  // k_observe_sweep: per-workgroup result lists
+  size_t sweep_cap = 0;
+  unsigned* retry_seen = nullptr;  // pinned host word: second-chance rows the last scan WANTED (copied behind every second chance)
+  int64_t retry_rows_min = 0;      // what retry_rows() grows to when a scan wanted more rows than there were
+  FastHandoff fh{};      // device buffers of the hand-off
+  int64_t fh_cap_l = 0, fh_cap_b = 0;
+  // pinned host staging ring for the per-scan uploads (blobs, ray directions, chains):
+  // lets pk_observe/pk_step return without synchronising the stream
+  static constexpr int kRing = 8;
+  unsigned char* stage[kRing] = {nullptr};
+  hipEvent_t stage_done[kRing] = {nullptr};
+  // which enqueued upload last read each slot, and up to which upload each slot's event covers
+  // (an event is recorded behind every 4th upload only; a slot whose covering record never came --
+  // its scan was staged and then discarded -- gets one when the slot is next handed out)
+  uint64_t upload_seq = 0;
+  uint64_t slot_seq[kRing] = {0};
+  uint64_t event_seq[kRing] = {0};
+  size_t stage_cap = 0;
+  int stage_next = 0;
+  double* partial = nullptr;  // 4 * 1024
+  double* gmax = nullptr;
+  double* clocal = nullptr;   // P
+  double* totals = nullptr;   // nblocks
+  double* offsets = nullptr;  // nblocks
+  double* sum = nullptr;
+  double* out4 = nullptr;
+  double* pose_part = nullptr;   // [motion_pose_blocks(P)][4]: per-block sums of x, y, sin h, cos h the last whole-filter motion launch left
+  bool pose_part_ok = false;     // ... and nothing has touched the poses since
+  GrowState grow{};                 // section 8(f4) on the device (pk_grow_enable): per-particle new-landmark bookkeeping
+  bool grow_on = false;
+  int32_t* anc = nullptr;           // P
+  unsigned char* slot_tmp = nullptr;  // one slot
+  // timing
+  uint32_t timing_mask = 0;  // bit i: PK_T_* slot i is bracketed by hipEvents
+  int64_t timing_seen[PK_T_COUNT] = {0};
+  std::vector<TimedSpan> pending;
+  std::vector<hipEvent_t> pool;
+  double ms[PK_T_COUNT] = {0};
+  int64_t launches[PK_T_COUNT] = {0};
+};
+
+// A filter's device and pinned memory comes from these alone ("Memory"): f->mem records every block, and
+// pk_destroy frees what it holds.
+template <typename T>
+int dev_alloc(pk_filter* f, T** p, size_t n) { return f->mem.alloc(p, n ? n : 1); }
+template <typename T>
+void dev_free(pk_filter* f, T** p) {
+  f->mem.release(*p);
+  *p = nullptr;
+}
+// a buffer allocated once, when something first wants it (no synchronisation: nothing is freed)
+template <typename T>
+int dev_lazy(pk_filter* f, T** p, size_t n) { return *p ? PK_OK : dev_alloc(f, p, n); }
+// The grow pattern: nothing while need <= *cap; else the stream is synchronised, the members are freed and allocated afresh, and
+// *cap = new_cap last (a failure leaves *cap == 0).  dev_reserve: one buffer of new_cap elements; dev_reserve_group: several
+// buffers behind one capacity, each want(&p, n) with its own element count.
+template <typename C, typename... T>
+int dev_reserve_group(pk_filter* f, C* cap, C need, C new_cap, Want<T>... w) {
+  auto idle = [f]() -> int {
+    PK_HIP(hipStreamSynchronize(f->stream));
+    return PK_OK;
+  };
+  return f->mem.reserve(cap, need, new_cap, idle, w...);
+}
+template <typename T, typename C>
+int dev_reserve(pk_filter* f, T** p, C* cap, C need, C new_cap) { return dev_reserve_group(f, cap, need, new_cap, want(p, (size_t)new_cap)); }
+// pinned host memory (registered, not counted in pk_device_bytes)
+template <typename T>
+int host_alloc(pk_filter* f, T** p, size_t n, unsigned flags) { return f->mem.alloc_host(p, n, flags); }
+
+struct Span {
+  pk_filter* f;
+  int slot;
+  hipEvent_t a = nullptr, b = nullptr;
+  Span(pk_filter* f_, int slot_) : f(f_), slot(slot_) {
+    if (!((f->timing_mask >> slot_) & 1u)) return;
+    if (f->timing_seen[slot_]++ % f->opt.timing_stride != 0) return;
+    a = take();
+    b = take();
+    if (a) (void)hipEventRecord(a, f->stream);
+  }
+  hipEvent_t take() {
+    if (!f->pool.empty()) {
+      hipEvent_t e = f->pool.back();
+      f->pool.pop_back();
+      return e;
+    }
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) return nullptr;
+    return e;
+  }
+  ~Span() {
+    if (!a || !b) return;
+    (void)hipEventRecord(b, f->stream);
+    f->pending.push_back(TimedSpan{slot, a, b});
+  }
+};
+
+inline int use_device(pk_filter* f) {
+  PK_HIP(hipSetDevice(f->device));
+  return PK_OK;
+}
+
+// (the poses change: the motion launch's pose sums are no longer theirs) -- ahead of the argument checks, on any handle
+inline void poses_change(pk_filter* f) {
+  if (f) f->pose_part_ok = false;
+}
+
+// One device block per scan, filled by ONE host->device copy:
+//   [ctl: kGmaxKeys running-max keys (u64), flagged-particle count (u32)] [blobs 4B f64] then either
+//   known ids:  [first Lp i32] [next B i32]
+//   ML:         [dir 2B f64] [exact 6B f64] [association tables]
+// The copy also zeroes ctl, which is how every observe starts with a fresh max / count.
+constexpr size_t kCtlBytes = 8 * kGmaxKeys + 64;  // running-max keys, then the flagged-particle count, the route control words and the publish table's figures
+
+inline unsigned long long* ctl_gmax_key(pk_filter* f) { return reinterpret_cast<unsigned long long*>(f->scan_dev); }
+inline unsigned* ctl_n_flagged(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys); }
+inline unsigned* ctl_cand_over(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 4); }
+inline unsigned* ctl_n_stray(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 8); }
+// written by k_cand_entries: != 0 -> k_step_pub stands back (a candidate list overflowed, or the publish table does not fit LDS)
+inline unsigned* ctl_skip_pub(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 12); }
+// != 0 -> the candidate-list instance of k_step_regs stands back (k_step_pub runs, or the grid walk does)
+inline unsigned* ctl_skip_cand(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 16); }
+// rows of the second-chance hand-off lists dealt out so far (FastHandoff::row_next)
+inline unsigned* ctl_retry_rows(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 20); }
+// written by k_cand_entries: != 0 -> the two-workgroups-per-CU instance of the two-pass kernel (k_step_pub_duo) stands back and
+// k_step_pub_big takes the scan (the publish table, the contested blobs or the landmarks with several blobs exceed its share of LDS)
+inline unsigned* ctl_skip_duo(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 24); }
+// ... != 0 -> k_step_pub_big stands back (no publish / subscribe kernel takes the scan, or k_step_pub_duo does)
+inline unsigned* ctl_skip_big(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 28); }
+// what the scan's publish table came to (k_cand_entries; pk_observe_pub_stats): entries, contested blobs, landmarks of the reference
+// particle with two or more blobs inside their gates, the longest candidate list
+inline unsigned* ctl_pub_stats(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 32); }
+
+// ---- helpers that more than one file calls
+// pk_api.hip
+int materialise(pk_filter* f);
+// pk_api_observe.hip
+int note_upload(pk_filter* f, int slot);
+int colour_rows_for_download(pk_filter* f, int64_t p0, int64_t p1);
+int ct_end(pk_filter* f);
+int ct_maps_untouched(pk_filter* f, bool* untouched);
+void blob_directions(const double* blobs, int B, double* dir);
+int stage_ml_scan(pk_filter* f, const double* blobs, int B);
+int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out, bool reset);
+// pk_api_shard.hip
+int refuse_balanced(const pk_filter* f, const char* who);

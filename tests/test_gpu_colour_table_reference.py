@@ -9,7 +9,7 @@ cannot see:
     world (tests/test_colour_recurrence_reference.py prints it): levels 1 .. 300 from the table, and levels 8 .. 40 from the
     recurrence the kernels run themselves beyond a table of eight;
   * whole steps in table mode against the oracle, six in a row, at L = 520, 1 030 and 2 000;
-  * the transitions of pk_api.hip nobody made: a second pk_upload_map, a Qt change between scans, pk_associate, supplied ids, the
+  * the transitions of pk_api.hip and pk_api_observe.hip nobody made: a second pk_upload_map, a Qt change between scans, pk_associate, supplied ids, the
     option switched in mid-run, the staged path, a ranged observe, and the edges of the map sizes the mode takes.
 
 Every test asserts through colour_table_stats / observe_route / observe_published that the mode took the scans it claims.

@@ -1,4 +1,4 @@
-"""GPU: which kernels a scan gets (pk_api.hip: plan_scan; DESIGN.md section 4, "Routing").  One filter per row of a matrix of map
+"""GPU: which kernels a scan gets (pk_api_observe.hip: plan_scan; DESIGN.md section 4, "Routing").  One filter per row of a matrix of map
 sizes (each beside a routing boundary), scan sizes and settings; two scans with a resample between them; after each scan the route,
 the publish table's figures, the flagged particles, the second-chance rows, the colour table's statistics and the launches per
 timing slot are compared, exactly, with tests/golden/route_matrix.json.
