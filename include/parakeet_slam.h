@@ -130,6 +130,9 @@ int64_t pk_device_bytes(const pk_filter* f);
  *                    (a key beyond the float64 underflow edge by the reference particle's bound with margins) leave the candidate
  *                    lists of the publish / subscribe kernels; a landmark whose own bound is weaker re-checks them itself
  *                    (prkt_core_v2.py:369: probability 0 never matches).  0: every particle tests and judges them (round 4).
+ *   "pub_lean"     = 1 (default) or 0: k_step_pub's two-pair instance (1 025 .. 2 048 landmarks) lets the (wave, pair) groups whose
+ *                    landmarks all have at most one candidate blob that nobody else lists skip the publish / subscribe machinery
+ *                    (pk_observe_lean_stats); the results are the same bits either way.  0: every group takes the usual body;
  *   "pub_small"    = -1 (default), 0 or 1: maps of at most 512 landmarks through k_step_pub's 256-lane instance (three workgroups per
  *                    CU, candidate lists made once per scan) instead of k_step_fused.  Its kernel is 11-18 % faster, its per-scan
  *                    kernels cost 27 us whatever the number of particles: -1 takes it where the whole step was measured no slower --
@@ -474,6 +477,12 @@ int pk_observe_published(pk_filter* f, int32_t* published);
  * two- / three-workgroups-per-CU instance of the two-pass kernel (k_step_pub_duo, option "pub_duo" = 1 / 2).  All zero when the
  * last observe took another route.  Synchronises the stream. */
 int pk_observe_pub_stats(pk_filter* f, int64_t stats[6]);
+/* The lean groups of the last scan (instrumentation; maps of 1 025 .. 2 048 landmarks on the publish / subscribe route, whose kernel
+ * deals sixteen-landmark octets to sixteen (wave, pair) groups): out[0] groups in use that k_cand_entries marked lean -- every
+ * landmark of theirs has at most one candidate blob, which no other landmark lists --, [1] groups in use, [2] pairs of lean groups
+ * that took the usual body after all in the scan's launches (a key near the underflow edge, a mean outside the candidate margins,
+ * a far bound that did not hold; 0 with "pub_lean" = 0).  All zero when the last observe took another route.  Synchronises the stream. */
+int pk_observe_lean_stats(pk_filter* f, int64_t out[3]);
 /* Per particle, how the last one-pass maximum-likelihood observe (k_step_fused / k_step_pub / k_step_pub_big / k_step_regs)
  * dealt with it (instrumentation; what the full-size oracle audits of tests/test_gpu_audit.py pick their samples by):
  * flags[P], 0 = settled by the one-pass kernel itself, 2 = redone by the second-chance route (eight-slot hand-off +

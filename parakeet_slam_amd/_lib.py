@@ -117,6 +117,7 @@ SIGNATURES = {
     "pk_observe_published": (C.c_int, [_h, C.POINTER(C.c_int32)]),
     "pk_observe_flags": (C.c_int, [_h, _bp]),
     "pk_observe_pub_stats": (C.c_int, [_h, _lp]),
+    "pk_observe_lean_stats": (C.c_int, [_h, _lp]),
     "pk_rng_create_numpy": (C.c_int, [C.c_uint32, C.POINTER(_h)]),
     "pk_rng_create_python": (C.c_int, [C.c_uint32, C.POINTER(_h)]),
     "pk_rng_destroy": (C.c_int, [_h]),
@@ -466,6 +467,13 @@ class DeviceFilter(object):
         a = np.zeros(6, dtype=np.int64)
         check(self._lib.pk_observe_pub_stats(self._h, lptr(a)))
         return dict(zip(("entries", "contested_blobs", "multi_landmarks", "longest_list", "entry_capacity", "instance"), (int(v) for v in a)))
+
+    def observe_lean_stats(self):
+        """The last scan's lean groups (pk_observe_lean_stats): dict of marked (groups in use that the scan marked lean), in_use,
+        fallbacks (pairs of lean groups that took the usual body after all)."""
+        a = np.zeros(3, dtype=np.int64)
+        check(self._lib.pk_observe_lean_stats(self._h, lptr(a)))
+        return dict(zip(("marked", "in_use", "fallbacks"), (int(v) for v in a)))
 
     def colour_table_stats(self):
         """The colour table (pk_colour_table_stats): dict of engaged (the last observe ran in the mode and nothing has ended it),

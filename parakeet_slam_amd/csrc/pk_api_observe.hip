@@ -662,6 +662,8 @@ static int onepass_launch(pk_filter* f, const AssocLaunch& al, int B, const Obse
     e1.ctab_depth = f->ct_depth;
     e1.ctab_max = f->ct_max_dev;
   }
+  e1.lean = f->opt.pub_lean;
+  e1.lean_stats = ctl_pub_stats(f);
   switch (plan.kind) {
     case ScanKind::PubBig:
       // the scan goes to ONE of the two instances (k_cand_entries decided which: the two-workgroups-per-CU instance when its share of
@@ -1059,6 +1061,22 @@ int pk_observe_pub_stats(pk_filter* f, int64_t stats[6]) {
     stats[4] = f->pub_ecap;
     // which instance worked on the scan: 0 none of the publish / subscribe kernels, 1 the one-workgroup-per-CU instance, 2 k_step_pub_duo
     stats[5] = sk[0] != 0u ? 0 : (f->route == PK_ROUTE_ML_PUB_BIG && f->opt.duo_on && sk[1] == 0u) ? 1 + f->opt.duo_on : 1;
+  }
+  return PK_OK;
+}
+int pk_observe_lean_stats(pk_filter* f, int64_t out[3]) {
+  if (!f || !out) return fail(PK_ERR_INVALID, "pk_observe_lean_stats: NULL argument");
+  int rc;
+  if ((rc = use_device(f))) return rc;
+  for (int i = 0; i < 3; ++i) out[i] = 0;
+  // (only the two-pair instance deals octets to groups: maps of 1 025 .. 2 048 padded landmarks on the publish / subscribe route)
+  if (f->scan_dev && f->route == PK_ROUTE_ML_REGS && f->pub_ecap > 0 && f->d.lay.Lp > 2 * kPubThreads && f->d.lay.Lp <= 4 * kPubThreads) {
+    unsigned w[3] = {0u, 0u, 0u}, sk = 1u;
+    PK_HIP(hipMemcpyAsync(w, ctl_pub_stats(f) + 4, sizeof(w), hipMemcpyDeviceToHost, f->stream));
+    PK_HIP(hipMemcpyAsync(&sk, ctl_skip_pub(f), sizeof(unsigned), hipMemcpyDeviceToHost, f->stream));
+    PK_HIP(hipStreamSynchronize(f->stream));
+    if (sk == 0u)
+      for (int i = 0; i < 3; ++i) out[i] = w[i];
   }
   return PK_OK;
 }

@@ -130,6 +130,7 @@ struct Options {
   int pub_step = 1;      // ... with the contested blobs settled by static publish / subscribe (k_step_pub) while the publish table fits LDS
   int pub_small = -1;    // L <= 512: k_step_pub<256 lanes> instead of k_step_fused -- 1 / 0, or -1 (default): where it is measured faster
                          // (kPubSmallAutoWork, pk_api_observe.hip)
+  int pub_lean = 1;      // k_step_pub<2, 512>: the (wave, pair) groups of simple landmarks take the lean body (pub_lean_pair); 0: the usual one
   int far_prune = 1;             // look-alikes certainly beyond the underflow edge leave the candidate lists once per scan (0: as round 4)
   int duo_on = 0;        // "pub_duo" (measured, off: DESIGN.md section 4): 2 048 < L <= 5 120, scans whose publish table fits its share of a CU's LDS go to
                          // k_step_pub_duo -- 1: two 512-lane workgroups per CU (<= 128 VGPRs), 2: three 256-lane workgroups (<= 168) -- the others to k_step_pub_big
@@ -169,6 +170,7 @@ inline constexpr OptionRow kOptionTable[] = {
     {"pub_step", &Options::pub_step, Take::Flag, 0, 0, nullptr},
     {"pub_small", &Options::pub_small, Take::Tri, 0, 0, nullptr},
     {"far_prune", &Options::far_prune, Take::Flag, 0, 0, nullptr},
+    {"pub_lean", &Options::pub_lean, Take::Flag, 0, 0, nullptr},
     {"pub_duo", &Options::duo_on, Take::Range, 0, 2,
      "pub_duo: 0 (off), 1 (two 512-lane workgroups per CU) or 2 (three 256-lane workgroups per CU)"},
     {"pub_duo_park_limit", &Options::duo_park_limit, Take::Range, -1, 65535, "pub_duo_park_limit: -1 (what LDS holds) .. 65535"},
@@ -416,7 +418,8 @@ inline unsigned* ctl_skip_duo(pk_filter* f) { return reinterpret_cast<unsigned*>
 // ... != 0 -> k_step_pub_big stands back (no publish / subscribe kernel takes the scan, or k_step_pub_duo does)
 inline unsigned* ctl_skip_big(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 28); }
 // what the scan's publish table came to (k_cand_entries; pk_observe_pub_stats): entries, contested blobs, landmarks of the reference
-// particle with two or more blobs inside their gates, the longest candidate list
+// particle with two or more blobs inside their gates, the longest candidate list; then (pk_observe_lean_stats) the groups marked lean and
+// the groups in use, and -- counted by k_step_pub<2, 512> -- the pairs of lean groups that fell back to the usual body: seven words
 inline unsigned* ctl_pub_stats(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 32); }
 
 // ---- helpers that more than one file calls

@@ -32,8 +32,9 @@ struct CandEntriesArgs {
   int64_t flag_P;
   unsigned* skip_duo;  // k_step_pub_duo (two workgroups per CU: half the LDS each) stands back when != 0, or null
   unsigned* skip_big;  // k_step_pub_big stands back when != 0 (nobody's scan, or k_step_pub_duo's), or null
-  unsigned* stats;     // [4] out, or null: entries of the publish table, contested blobs, landmarks of the reference particle with two
-                       // or more blobs inside their own gates, the longest candidate list
+  unsigned* stats;     // [6] out, or null: entries of the publish table, contested blobs, landmarks of the reference particle with two
+                       // or more blobs inside their own gates, the longest candidate list; [4], [5] (eight-entry lists, maps of up to 128
+                       // octets: k_step_pub<2, 512>'s scans) the (wave, pair) groups marked lean and the groups in use, else 0
   DuoLimits duo;
   uint4* prim;  // out, or null: the PRIMARY blob of every landmark -- of its candidates the closest in colour -- moved to the front of its
                 // list, and that blob's records in LANDMARK order (pk_pub_layout.hpp: prim_*), so that the two-pass kernels read them
@@ -76,13 +77,16 @@ __global__ void __launch_bounds__(1024) k_cand_entries(CandEntriesArgs a) {
   constexpr bool kRankMajor = SLOTS > kCandSlots;  // (sixteen-entry lists: k_step_pub_big; k_step_pub keeps blob-major, +0.6 % otherwise)
   __shared__ unsigned s_tot[SLOTS + 1], s_cbase[SLOTS + 1], s_rbase[SLOTS];
   __shared__ unsigned s_total, s_sw[16];
-  __shared__ unsigned s_multi, s_longest, s_gtotal;
+  __shared__ unsigned s_multi, s_longest, s_gtotal, s_busy;
   if (threadIdx.x == 0) {
     s_multi = 0u;
     s_longest = 0u;
+    s_busy = 0u;
   }
   __shared__ unsigned short s_cls[kRankMajor ? SLOTS + 1 : 1][1024];  // per class (number of contenders) and thread: its blobs of the class, then their scan
   __shared__ unsigned char s_len[kPubBigMaxL + kCandSpare + 14], s_np[kPubBigMaxL + kCandSpare + 14];  // per landmark: list length, npass
+  // per landmark: 1 = NOT simple (pk_pub_layout.hpp: kPubLeanWord) -- its list holds several blobs, or a blob that other landmarks list too
+  __shared__ unsigned char s_busyl[kRankMajor ? 1 : 2 * kPubOctets * 16 + kCandSpare];
   const int tid = threadIdx.x;
   const int chunk = (a.B + 1023) / 1024;
   const int t0 = tid * chunk, t1 = min(a.B, t0 + chunk);
@@ -207,6 +211,7 @@ __global__ void __launch_bounds__(1024) k_cand_entries(CandEntriesArgs a) {
 #pragma unroll
     for (int j = 0; j < SLOTS / 8; ++j) lw[j] = a.cand[RW * (size_t)l + 1 + j];
     int len = 0;
+    unsigned e_front = 0xFFFFu;  // the publish entry of the list's first blob
     constexpr int BATCH = SLOTS > 8 ? 4 : 8;  // candidates looked up side by side (sixteen-entry lists: four -- their rows are 32 bytes)
     unsigned cw[SLOTS / 2];
 #pragma unroll
@@ -305,6 +310,10 @@ __global__ void __launch_bounds__(1024) k_cand_entries(CandEntriesArgs a) {
 #pragma unroll
       for (int k = 0; k < BATCH; k += 2)
         reinterpret_cast<unsigned*>(a.erec)[(size_t)l * (SLOTS / 2) + (BATCH * h + k) / 2] = (ev[k] & 0xFFFFu) | (ev[k + 1] << 16);
+      if (h == 0) e_front = ev[0] & 0xFFFFu;
+    }
+    if constexpr (!kRankMajor) {  // (the lists are filled from the front; a place beyond the map is simple)
+      if (l < (int)sizeof(s_busyl)) s_busyl[l] = (l < a.L && (len > 1 || (len == 1 && e_front != 0xFFFFu))) ? 1 : 0;
     }
     s_len[l] = (unsigned char)len;
     s_np[l] = (a.npass && l < a.L) ? a.npass[l] : (unsigned char)0;
@@ -339,6 +348,8 @@ __global__ void __launch_bounds__(1024) k_cand_entries(CandEntriesArgs a) {
       a.stats[1] = G_;
       a.stats[2] = s_multi;
       a.stats[3] = s_longest;
+      a.stats[4] = 0u;  // (the octet ranking below says otherwise where its kernel deals octets to groups)
+      a.stats[5] = 0u;
     }
   }
   // k_step_pub_big's first look at a candidate: bearing and colour as FLOAT, 16 bytes in one gather instead of 32 in two (the
@@ -371,7 +382,7 @@ __global__ void __launch_bounds__(1024) k_cand_entries(CandEntriesArgs a) {
       if (tid < kPlaces) {
         int c = -1;
         if (tid < n_oct) {
-          int longest = 0, sum = 0, passes = 0;
+          int longest = 0, sum = 0, passes = 0, busy = 0;
 #pragma unroll
           for (int i = 0; i < kLm; ++i) {  // (list lengths and gate passes: left in LDS by the loop above)
             const int l = kLm * tid + i;
@@ -379,10 +390,19 @@ __global__ void __launch_bounds__(1024) k_cand_entries(CandEntriesArgs a) {
             longest = max(longest, n);
             sum += n;
             passes = max(passes, l < a.L ? (int)s_np[l] : 0);
+            if constexpr (!kBig) busy |= (int)s_busyl[l];
           }
           // (first by the blobs inside the reference's own gates -- a verdict round each, and a round costs the whole wave its
           // arithmetic --, then by the longest list -- two candidates a gate round)
           c = min(passes, 15) * 4096 + longest * 256 + sum;
+          // (... and above all of that, k_step_pub<2, 512> only: an octet with a landmark that is not simple.  Those octets stand first
+          // in the ranking, so they fill the fewest groups, and every group behind them is lean: pk_pub_layout.hpp, kPubLeanWord)
+          if constexpr (!kBig) {
+            if (busy) {
+              c += 65536;
+              atomicAdd(&s_busy, 1u);
+            }
+          }
         }
         s_cost[tid] = c;
         perm[tid] = 0xFFFFu;  // a place without an octet: its lanes are beyond the map
@@ -403,6 +423,18 @@ __global__ void __launch_bounds__(1024) k_cand_entries(CandEntriesArgs a) {
           const int g = r >> 3, k = r & 7;
           const int wave = g & 7, pair = g >> 3;
           perm[kPubOctets * pair + 8 * wave + k] = (unsigned short)tid;
+        }
+      }
+      if constexpr (!kBig) {
+        // group g = pair 8 + wave takes the ranks 8 g ... 8 g + 7: the first ceil(busy octets / 8) groups hold every octet that is not
+        // simple; bit g of the mask = bit 8 pair + wave.  (A group without octets is lean: its lanes are beyond the map.)
+        if (tid == 0) {
+          const unsigned busy_groups = (s_busy + 7u) / 8u, used = ((unsigned)n_oct + 7u) / 8u;
+          a.glist[a.B + 1 + kPubLeanWord] = fits ? (0xFFFFu & ~((1u << busy_groups) - 1u)) : 0u;
+          if (a.stats) {
+            a.stats[4] = fits ? used - busy_groups : 0u;
+            a.stats[5] = used;
+          }
         }
       }
     }

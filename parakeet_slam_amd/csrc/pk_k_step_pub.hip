@@ -93,10 +93,12 @@ struct PubArgs {
   int L, Lp, B;
   int ecap;                     // entries of the publish table in LDS
   int reset;
+  int lean = 0;                 // k_step_pub<2, 512> only: != 0: the (wave, pair) groups k_cand_entries marked lean take the lean body
+                                //   (pub_lean_pair); pairs of theirs that fall back to the usual body are counted in stats[6]
   unsigned long long* gmax_key;
   Noise<double> qt;
   // (k_step_pub_duo only; behind everything the other kernels read)
-  const unsigned* stats;        // [4] k_cand_entries' figures of this scan: [0] the entries of its publish table, [3] its longest list
+  const unsigned* stats;        // [7] k_cand_entries' figures of this scan: [0] the entries of its publish table, [3] its longest list
   int tbytes;                   // bytes of LDS the publish table and the overflow area share
   const uint4* prim;            // the two-pass kernels: every landmark's primary blob in landmark order (prim_table_uint4), or null
   const double* ctab = nullptr; // table mode (k_step_pub<NP, 512, true>; pk_colour.hpp): the colour table [depth][6][Lp], else null
@@ -435,6 +437,85 @@ __device__ __forceinline__ void pub_far_recheck(const bool (&viol)[N], const Lan
     }
   }
   if (bad) *flag = 1;
+}
+
+
+// LEAN groups (k_step_pub<2, 512>; DESIGN.md section 4, "lean groups").  k_cand_entries marks the (wave, pair) groups all of whose 128
+// landmarks are SIMPLE: a pruned candidate list of at most one blob that no other landmark lists.  Such a landmark needs none of the
+// publish / subscribe machinery -- no slots to insert into, no second candidate, no table entry to write or read, no settling to wait
+// for: the blob is its own if it passes the gates with a probability > 0 -- and of the key only on which side of the underflow edge
+// it lies: log det is bounded by the determinants' exponents (e ln 2 above, (e - 1) ln 2 below), which saves the logarithm.
+// This body DECIDES only; every number that reaches the map or the weight is made by the same calls on the same arguments as ever
+// (pk_atan2, ekf_update).  Whatever it cannot decide with certainty -- a key inside or near the edge strip, odd covariances, a bound that
+// does not settle the far-list test, a mean outside the candidate margins -- makes the WAVE take the usual body for the pair instead
+// (returns false, wave-uniform; nothing has been written by then), which then does exactly what it always did.
+// bnd: the bounds the landmarks' lists were pruned with (Kb, Ib; Ib = 0: nothing to hold).
+__device__ __forceinline__ bool pub_lean_pair(PubSlots (&q)[2], double (&pse_out)[2], const PubGateIn (&in)[2],
+                                              const Landmark<double>* const (&lmp)[2], const float2 (&bnd)[2], const double* ex,
+                                              unsigned char* any, unsigned anydump, double sx, double sy, double sh) {
+  constexpr double ln2 = 0.69314718055994530942;
+  bool unsure = false, positive[2];
+  unsigned t[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const Landmark<double>& lm = *lmp[j];
+    const double pse = pk_atan2(in[j].my - sy, in[j].mx - sx);
+    pse_out[j] = pse;
+    const double eb = pse - sh;  // :408
+    const double deb = eb - (double)__uint_as_float(in[j].ref.x);
+    const bool inside = (fabs(deb) <= kCandBearing || fabs(deb - Consts<double>::two_pi) <= kCandBearing ||
+                         fabs(deb + Consts<double>::two_pi) <= kCandBearing) &&
+                        fabs(in[j].mr - (double)__uint_as_float(in[j].ref.y)) <= kCandColour &&
+                        fabs(in[j].mg - (double)__uint_as_float(in[j].ref.z)) <= kCandColour &&
+                        fabs(in[j].mb - (double)__uint_as_float(in[j].ref.w)) <= kCandColour;  // (pub_gatesN's test; NaN: outside)
+    t[j] = in[j].has ? (in[j].cw[0].x & 0xFFFFu) : 0xFFFFu;
+    const bool valid = t[j] != 0xFFFFu;
+    const double* rec = ex + 6 * (valid ? t[j] : 0u);
+    const double2 z01 = *reinterpret_cast<const double2*>(rec);
+    const double2 z23 = *reinterpret_cast<const double2*>(rec + 2);
+    const double2 dir = *reinterpret_cast<const double2*>(rec + 4);
+    const double cd = color_distance2(in[j].mr, in[j].mg, in[j].mb, z01.y, z23.x, z23.y);
+    const bool pass = valid && !(fabs(z01.x - eb) > 0.5) && !(fabs(cd) > 300.0);  // :433, :441
+    // pub_keysN's prologue, without the logarithm
+    const double det2 = lm.pxx * lm.pyy - lm.pxy * lm.pxy;
+    double det3;
+    const Sym3<double> adj3 = sym3_adjugate(Sym3<double>{lm.crr, lm.crg, lm.crb, lm.cgg, lm.cgb, lm.cbb}, det3);
+    const bool sane = det2 > 1e-20 && det2 < 1e60 && det3 > 1e-20 && det3 < 1e60;  // NaN: false
+    int e2i, e3i;
+    (void)frexp(det2, &e2i);
+    (void)frexp(det3, &e3i);
+    const double a2base = 2.0 * Consts<double>::log_two_pi + (double)e2i * ln2;
+    const double a3base = 3.0 * Consts<double>::log_two_pi + (double)e3i * ln2;
+    const double khi = a2base + a3base, klo = khi - 2.0 * ln2;  // klo <= 5 log 2 pi + log(det2 det3) <= khi
+    const bool pd3 = sane && lm.crr > 0.0 && adj3.f > 0.0 && lm.pxx > 0.0;
+    const double itr3 = pd3 ? pub_recip(fmax(fmax(lm.crr + (fabs(lm.crg) + fabs(lm.crb)), lm.cgg + (fabs(lm.crg) + fabs(lm.cgb))),
+                                             lm.cbb + (fabs(lm.crb) + fabs(lm.cgb))))
+                            : 0.0;
+    // the landmark's own far bound against the scan's (pub_keysN<CHK>): certain only with room for pub_log's error (1e-12)
+    const bool holds = itr3 >= (double)bnd[j].y && klo >= (double)bnd[j].x + 1e-9;
+    // the verdict (pub_keysN's round): certain on either side of the strip 1489 ... 1491.5, which the usual body evaluates exactly
+    const bool angle_ok = !(fabs(pse - z01.x) > Consts<double>::half_pi);  // :473-475
+    double nx, ny;
+    closest_point(lm.mx, lm.my, sx, sy, dir.x, dir.y, nx, ny);
+    const double ex_ = nx - lm.mx, ey = ny - lm.my;
+    const double d1 = z01.y - lm.mr, d2c = z23.x - lm.mg, d3c = z23.y - lm.mb;
+    const double num2 = lm.pyy * ex_ * ex_ - 2.0 * lm.pxy * ex_ * ey + lm.pxx * ey * ey;
+    const double num3 = sym3_quad(adj3, d1, d2c, d3c);
+    const double maha2 = num2 * pub_recip(det2), maha3 = num3 * pub_recip(det3);
+    const bool nonneg = fmin(num2, num3) >= 0.0;  // NaN: false
+    const double amax = fmax(a2base + maha2, a3base + maha3);
+    const bool sure_pos = angle_ok && nonneg && fmax(khi + (maha2 + maha3), amax) < 1489.0;
+    const bool sure_zero = !angle_ok || klo + (maha2 + maha3) > 1491.5;
+    positive[j] = pass && sure_pos;
+    unsure |= in[j].has && (!inside || !holds || (pass && (!sane || (angle_ok && !nonneg) || (!sure_pos && !sure_zero))));
+    q[j] = kPubNoSlots;
+    q[j].s[0] = pass ? (t[j] | 0xFFFF0000u) : 0xFFFFFFFFu;
+    q[j].st = positive[j] ? 5u : 0u;  // probability > 0, and taken: nobody else lists the blob
+  }
+  if (__ballot(unsure) != 0ull) return false;  // wave-uniform
+#pragma unroll
+  for (int j = 0; j < 2; ++j) any[positive[j] ? t[j] : anydump] = 1;
+  return true;
 }
 
 #ifdef PK_STAMPS
@@ -1090,6 +1171,13 @@ __device__ __forceinline__ void step_pub_body() {
   constexpr int kUnmWords = THREADS == kPubSmallThreads ? 32 : 96;
   __shared__ unsigned s_ubits[kUnmWords];
   __shared__ unsigned s_kmax;  // TAB: the highest level read so far
+  // Lean groups (pub_lean_pair): only this instance deals octets to (wave, pair) groups, and k_cand_entries marks the lean ones for it
+#ifdef PK_DIAG_NO_LEAN_BODY  // diagnostic build only: the kernel without the lean body (k_cand_entries ranks and marks as ever)
+  constexpr bool kLean = false;
+#else
+  constexpr bool kLean = kPerm;
+#endif
+  __shared__ unsigned s_fallbacks;  // kLean: pairs of lean groups that took the usual body after all
   // (the two octet numbers of a lane ride above its index in one register; in a register of their own, or below the index: no
   // better -- profiles/r04/ab_perm_mechanisms.log)
 #define PK_PUB_L0(q_, t_) (!kPerm ? 2 * kPubThreads * (q_) + 2 * (t_) : (int)(((lw >> (16 + 8 * (q_))) & 0xFFu) << 4) + 2 * ((t_)&7))
@@ -1153,6 +1241,16 @@ __device__ __forceinline__ void step_pub_body() {
       wg_flag[0] = 0;
       wg_flag[1] = 0;
       s_kmax = 0u;
+      if constexpr (kLean) s_fallbacks = 0u;
+    }
+  }
+  // which of this wave's two groups are lean: bit q = pair q (a scalar; 0 with the switch off)
+  unsigned lean_bits = 0u;
+  if constexpr (kLean) {
+    PubArgsPtr R = pub_args_now(rp);
+    if (R->lean != 0) {  // kernel-uniform
+      const unsigned m = R->glist[B + 1 + kPubLeanWord], wave = (unsigned)tid0 / kWave;
+      lean_bits = __builtin_amdgcn_readfirstlane(((m >> wave) & 1u) | (((m >> (8u + wave)) & 1u) << 1));
     }
   }
   __syncthreads();
@@ -1334,6 +1432,7 @@ __device__ __forceinline__ void step_pub_body() {
     PubSlots Q[2 * NP];
     double pse[2 * NP];
     bool done;
+    unsigned lean_ok = 0u;  // (wave-uniform) bit q: pair q went through the lean body -- its take bits are set, pub_take has nothing to add
     PK_STAMP(s0)
 #ifdef PK_STAMPS
     unsigned long long s3 = s0;
@@ -1437,6 +1536,17 @@ __device__ __forceinline__ void step_pub_body() {
       }
     } else {
       const Landmark<double>* const l2[2] = {&S[2 * q], &S[2 * q + 1]};
+      bool usual = true;  // wave-uniform
+      if constexpr (kLean) {
+        if (((lean_bits >> q) & 1u) != 0u && PK_PUB_ABLATE == 0) {
+          const float2* bt = reinterpret_cast<const float2*>(smem + o_bnd);
+          const float2 b2[2] = {bt[min(l0, Lp - 1)], bt[min(l0 + 1, Lp - 1)]};
+          usual = !pub_lean_pair(qq, pp, gi, l2, b2, ex, anyc, anydump, sx, sy, sh);
+          lean_ok |= usual ? 0u : (1u << q);
+          if (usual && (tid & (kWave - 1)) == 0) atomicAdd(&s_fallbacks, 1u);
+        }
+      }
+      if (usual) {
       if (PK_PUB_ABLATE < 4) pub_gatesN<2, 1, kPubSlots, true>(qq, pp, gi, ex, pub, dump, &wg_flag[cur], sx, sy, sh);
       PK_STAMP(sk0_)
       if (PK_PUB_ABLATE < 3) {
@@ -1466,6 +1576,7 @@ __device__ __forceinline__ void step_pub_body() {
       }
       PK_STAMP(sk1_)
       PK_PSTAMP(2, sk0_, sk1_) /* keys: part of the gates-and-verdicts slot */
+      }
     }
     Q[2 * q] = qq[0];
     Q[2 * q + 1] = qq[1];
@@ -1551,7 +1662,7 @@ __device__ __forceinline__ void step_pub_body() {
     }
 #pragma unroll
     for (int i = 0; i < 2 * NP; ++i)
-      if (PK_PUB_ABLATE < 2) pub_take(Q[i], pub, dump);
+      if (PK_PUB_ABLATE < 2 && (!kLean || ((lean_ok >> (i / 2)) & 1u) == 0u)) pub_take(Q[i], pub, dump);
     lds_barrier();  // C: every marker has been read -- the table is the next particle's
     PK_STAMP(s6)
     PK_PSTAMP(5, s5, s6)  // barrier B, markers, barrier C
@@ -1672,6 +1783,12 @@ __device__ __forceinline__ void step_pub_body() {
 #endif
   if constexpr (TAB) {  // (behind the last barrier A: every lane's level is in)
     if (tid0 == 0) atomicMax(pub_args_now(rp)->ctab_max, s_kmax);
+  }
+  if constexpr (kLean) {  // (likewise: every fallback was counted in front of a barrier A)
+    if (tid0 == 0 && s_fallbacks != 0u) {
+      unsigned* st = const_cast<unsigned*>((const unsigned*)pub_args_now(rp)->stats);
+      if (st) atomicAdd(st + 6, s_fallbacks);
+    }
   }
 }
 template <int NP, int THREADS>
@@ -2376,7 +2493,7 @@ void launch_step_pub(hipStream_t s, DeviceState& d, int B, const double* exact_d
   a.skip = skip_dev;
   a.gate4 = nullptr;
   a.prim = nullptr;
-  a.stats = nullptr;
+  a.stats = ex.lean_stats;
   a.tbytes = 0;
   a.unm = ex.unm;
   a.unm_words = ex.unm_words;
@@ -2400,6 +2517,7 @@ void launch_step_pub(hipStream_t s, DeviceState& d, int B, const double* exact_d
   a.ctab = tab ? ex.ctab : nullptr;
   a.ctab_max = ex.ctab_max;
   a.ctab_depth = ex.ctab_depth;
+  a.lean = ex.lean;
   const size_t lds = step_pub_lds_bytes(B, ecap, small);
   int per_cu = 1;
   if (small) per_cu = (int)std::min<size_t>(3, std::max<size_t>(1, (160 * 1024 - 1024) / (lds + 256)));

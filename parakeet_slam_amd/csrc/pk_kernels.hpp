@@ -165,6 +165,8 @@ struct ObserveExtras {
   const double* ctab = nullptr;                 // k_step_pub's 512-lane instances in table mode: the colour table (ColourTable below), its
   int ctab_depth = 0;                           //   depth, and where the kernel leaves the highest level it read
   unsigned* ctab_max = nullptr;
+  int lean = 0;                                 // k_step_pub<2, 512>: lean groups take the lean body (option "pub_lean"); the scan's
+  unsigned* lean_stats = nullptr;               //   figures (k_cand_entries), where the kernel counts the pairs that fell back: [6]
 };
 // The colour table (pk_k_colour.hip): tab[k][6][Lp], rows crr crg crb cgg cgb cbb as in a slot -- landmark l's
 // colour block after k updates from the one pk_upload_map broadcast (base[6][Lp]; the uploaded counts are 0, so a landmark's level is

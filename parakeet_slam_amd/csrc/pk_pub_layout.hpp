@@ -10,5 +10,10 @@ constexpr int kPubTailWords = 256;  // words behind glist[B]: the octet orders o
 constexpr int kPubBigPlaces = 384;  // k_step_pub_big: six chunks of 64 octets (kPubBigMaxL / 16)
 constexpr int kPubOctets = 64;  // groups of eight lanes in a 512-lane workgroup: sixteen adjacent landmarks per pair each
 constexpr int kPubSlots = 4;  // gate-passing blobs a landmark keeps; more: the particle is flagged
+// k_step_pub<2, 512>'s LEAN mask ("lean groups"): tail word kPubLeanWord, glist[B + 1 + kPubLeanWord] -- the first
+// word behind that kernel's octet order (k_step_pub_big's order stands there in ITS scans; a map has one of the two).  Bit 8 pair + wave:
+// every landmark of that (wave, pair) group of 128 is SIMPLE -- its pruned candidate list holds at most one blob, and nobody else lists it.
+constexpr int kPubLeanWord = 2 * kPubOctets / 2;
+constexpr int kPubGroups = 2 * kPubOctets / 8;  // (wave, pair) groups of eight octets
 
 }  // namespace pk
