@@ -256,6 +256,22 @@ int pk_summary(pk_filter* f, double out[3]);
  * sum cos h -- what a sharded filter all-reduces before dividing / atan2. */
 int pk_pose_sums(pk_filter* f, double out[4]);
 
+/* The map estimate: per-landmark moments of the particles' landmark EKFs, reduced over the particles on the device (the particles
+ * are read where they are: nothing is materialised, no filter state changes; the reference has no counterpart -- its summary,
+ * prkt_core_v2.py:254-276, stops at the pose).  Landmarks covered: all L, or the preset ones of a growing filter (pk_grow_enable).
+ * weighting PK_MAP_UNIFORM: w_p = 1 (pk_summary's convention: behind a resample the population is the estimate);
+ * PK_MAP_WEIGHTED: w_p = exp(logw_p - gmax), for use between an observe and a resample. */
+#define PK_MAP_UNIFORM 0
+#define PK_MAP_WEIGHTED 1
+/* One shard's moments (what a sharded filter combines, as pk_pose_sums is to pk_summary).  gmax: the filter-wide maximum
+ * log-weight for PK_MAP_WEIGHTED, NaN = this handle's own; ignored for PK_MAP_UNIFORM.  Any output may be NULL.
+ * wsum[2] = sum w, sum w^2;  mean[L*5];  m2[L*15] = sum w (mu-mean)(mu-mean)^T, upper triangle row-major, about THIS shard's mean;
+ * within[L*9] = sum w Sigma_p (compact field order);  counts[L] = sum w * update_count.  Rows l >= Ls are NaN. */
+int pk_map_moments(pk_filter* f, int32_t weighting, double gmax, double wsum[2], double* mean, double* m2, double* within, double* counts);
+/* The finished estimate of ONE filter: mean[L*5], cov_within[L*25], cov_between[L*25] (dense row-major 5x5, like pk_download_landmarks),
+ * update_count[L], n_eff[1].  Any output may be NULL. */
+int pk_map_summary(pk_filter* f, int32_t weighting, double* mean, double* cov_within, double* cov_between, double* update_count, double* n_eff);
+
 /* One whole cam_cb without host synchronisation: reset weights, motion, observe,
  * resample.  Arguments as in the calls above. */
 int pk_step(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed,

@@ -11,12 +11,15 @@ import os
 
 import numpy as np
 
+from . import mapsum
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libparakeet_slam.so")
 
 PK_OK = 0
 PK_ERR_INVALID, PK_ERR_HIP, PK_ERR_STATE, PK_ERR_UNSUPPORTED, PK_ERR_NOMEM = -1, -2, -3, -4, -5
 PK_WEIGHTS_LINEAR, PK_WEIGHTS_LOG = 0, 1
+PK_MAP_UNIFORM, PK_MAP_WEIGHTED = mapsum.UNIFORM, mapsum.WEIGHTED
 PK_LANDMARK_POTENTIAL = 0x40000000  # flag in a landmark's count word: potential feature (prkt_core_v2.py:109-118)
 PK_T_NAMES = ("motion", "assoc", "observe", "weights", "resample", "summary", "materialise")
 PK_T_COUNT = len(PK_T_NAMES)
@@ -61,6 +64,8 @@ SIGNATURES = {
     "pk_resample": (C.c_int, [_h, C.c_double, C.c_int32, _lp]),
     "pk_summary": (C.c_int, [_h, _dp]),
     "pk_pose_sums": (C.c_int, [_h, _dp]),
+    "pk_map_moments": (C.c_int, [_h, C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]),
+    "pk_map_summary": (C.c_int, [_h, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
     "pk_step": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32,
                           _ip, C.c_double, C.c_int32]),
     "pk_shard_max_logw": (C.c_int, [_h, _dp]),
@@ -315,6 +320,25 @@ class DeviceFilter(object):
         out = np.empty(4, dtype=np.float64)
         check(self._lib.pk_pose_sums(self._h, dptr(out)))
         return out
+
+    def map_moments(self, weighting=PK_MAP_UNIFORM, gmax=None):
+        """This handle's per-landmark moments over its particles (pk_map_moments) as ``mapsum.Moments``: what the shards of a
+        filter combine.  gmax: the whole filter's maximum log-weight for PK_MAP_WEIGHTED (None: this handle's own)."""
+        L = self.L
+        wsum, mean, m2 = np.empty(2), np.empty((L, 5)), np.empty((L, 15))
+        within, counts = np.empty((L, 9)), np.empty(L)
+        check(self._lib.pk_map_moments(self._h, int(weighting), float("nan") if gmax is None else float(gmax), dptr(wsum), dptr(mean),
+                                       dptr(m2), dptr(within), dptr(counts)))
+        return mapsum.Moments(wsum, mean, m2, within, counts)
+
+    def map_summary(self, weighting=PK_MAP_UNIFORM):
+        """The map estimate of this filter (pk_map_summary) as ``mapsum.MapSummary``: per landmark the mean over the particles,
+        the averaged EKF covariance, the covariance between the particles, the average update count; and n_eff."""
+        L = self.L
+        mean, within, between = np.empty((L, 5)), np.empty((L, 5, 5)), np.empty((L, 5, 5))
+        count, n_eff = np.empty(L), np.empty(1)
+        check(self._lib.pk_map_summary(self._h, int(weighting), dptr(mean), dptr(within), dptr(between), dptr(count), dptr(n_eff)))
+        return mapsum.MapSummary(mean, within, between, count, n_eff[0])
 
     def step(self, v, w, dt, blobs, u, z=None, seed=0, draw=0, ids=None, domain=PK_WEIGHTS_LINEAR):
         b = f64(blobs).reshape(-1, 4)

@@ -25,7 +25,7 @@ import threading
 
 import numpy as np
 
-from . import _lib, msgs
+from . import _lib, mapsum, msgs
 from .msgs import Blob, Odometry, Twist, heading_to_quaternion, quaternion_to_heading
 
 NO_MATCH_WEIGHT = 0.1  # prkt_core_v2.py:851-857
@@ -911,6 +911,15 @@ class FastSLAM(object):
     def summary(self):
         with self._lock:
             return self._filter.summary()
+
+    def map_summary(self, weighting="uniform"):
+        """The map estimate, reduced over the particles on the device (``mapsum.MapSummary``; the sibling of summary(),
+        prkt_core_v2.py:254-276, which stops at the pose).  weighting "uniform": every particle counts once, as in summary() --
+        behind a resample the population is the estimate; "weights": by the particles' weights, for use between an observe
+        and a resample.  A growing filter's spare landmarks are NaN rows (``as_features()`` leaves them out)."""
+        code = mapsum.weighting_code(weighting)
+        with self._lock:
+            return self._filter.map_summary(code)
 
     # ------------------------------------------------------------------ snapshot / restore
     def save_state(self, path):

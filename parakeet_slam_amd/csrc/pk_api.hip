@@ -739,6 +739,97 @@ int pk_pose_sums(pk_filter* f, double out[4]) {
   return PK_OK;
 }
 
+// ---- the map estimate (pk_k_mapsum.hip) ----------------------------
+// One shard's moments on the host: h = wsum[2] | mean[L][5] | m2[L][15] | within[L][9] | counts[L].  Reads the particles where they
+// are (src[], the adoption buffer): no materialise, no filter state changes -- the colour rows of a table-mode filter are written
+// back first, as for a download, and the mode goes on.
+static int map_moments_host(pk_filter* f, const char* who, int32_t weighting, double gmax, std::vector<double>& h) {
+  if (!f) return fail(PK_ERR_INVALID, "%s: NULL handle", who);
+  if (weighting != PK_MAP_UNIFORM && weighting != PK_MAP_WEIGHTED) return fail(PK_ERR_INVALID, "%s: weighting %d", who, weighting);
+  if (!f->map_loaded) return fail(PK_ERR_STATE, "%s: no map uploaded", who);
+  if (f->dense) return fail(PK_ERR_UNSUPPORTED, "%s: the map estimate reads the compact layout; this filter is on the dense one", who);
+  int rc;
+  if ((rc = use_device(f))) return rc;
+  if ((rc = colour_rows_for_download(f, 0, f->d.P))) return rc;
+  const DeviceState& d = f->d;
+  const int L = d.lay.L;
+  const int Ls = f->grow_on ? f->grow.L0 : L;  // spare slots hold different features in different particles
+  const int groups = map_sum_groups(d.P, Ls, f->opt.map_sum_groups);
+  const size_t need = map_sum_part_doubles(Ls, groups);
+  const size_t head = 2 + 2 * (size_t)kMapSumMaxGroups, n_res = 2 + (size_t)kMapSums * L;
+  if ((rc = dev_reserve_group(f, &f->ms_cap, need, need, want(&f->ms_part, need), want(&f->ms_res, head + n_res)))) return rc;
+  try {
+    h.resize(n_res);
+  } catch (const std::bad_alloc&) {
+    return fail(PK_ERR_NOMEM, "%s: no host memory for %d landmarks' moments", who, L);
+  }
+  {
+    Span t(f, PK_T_SUMMARY);
+    if (weighting == PK_MAP_WEIGHTED && std::isnan(gmax)) {  // this handle's own maximum
+      launch_block_max(f->stream, f->d, f->partial, f->ms_res);
+      PK_HIP(hipMemcpyAsync(&gmax, f->ms_res, sizeof(double), hipMemcpyDeviceToHost, f->stream));
+      PK_HIP(hipStreamSynchronize(f->stream));
+    }
+    if (weighting == PK_MAP_WEIGHTED && !std::isfinite(gmax))
+      return fail(PK_ERR_STATE, "%s: no finite maximum log-weight (%g): every weight is zero, or one is not finite", who, gmax);
+    launch_map_moments(f->stream, d, Ls, weighting == PK_MAP_WEIGHTED, gmax, groups, f->ms_part, f->ms_res + 2, f->ms_res + head);
+  }
+  PK_LAUNCH_CHECK(who);
+  PK_HIP(hipMemcpyAsync(h.data(), f->ms_res + head, n_res * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  PK_HIP(hipStreamSynchronize(f->stream));
+  if (!(h[0] > 0.0) || !std::isfinite(h[0]) || !std::isfinite(h[1]))
+    return fail(PK_ERR_STATE, "%s: the weights sum to %g: not positive and finite", who, h[0]);
+  return PK_OK;
+}
+
+int pk_map_moments(pk_filter* f, int32_t weighting, double gmax, double wsum[2], double* mean, double* m2, double* within, double* counts) {
+  std::vector<double> h;
+  int rc;
+  if ((rc = map_moments_host(f, "pk_map_moments", weighting, gmax, h))) return rc;
+  const size_t L = (size_t)f->d.lay.L;
+  if (wsum) memcpy(wsum, h.data(), 2 * sizeof(double));
+  if (mean) memcpy(mean, h.data() + 2, L * 5 * sizeof(double));
+  if (m2) memcpy(m2, h.data() + 2 + L * 5, L * 15 * sizeof(double));
+  if (within) memcpy(within, h.data() + 2 + L * 20, L * 9 * sizeof(double));
+  if (counts) memcpy(counts, h.data() + 2 + L * 29, L * sizeof(double));
+  return PK_OK;
+}
+
+int pk_map_summary(pk_filter* f, int32_t weighting, double* mean, double* cov_within, double* cov_between, double* update_count, double* n_eff) {
+  std::vector<double> h;
+  int rc;
+  if ((rc = map_moments_host(f, "pk_map_summary", weighting, std::nan(""), h))) return rc;
+  const size_t L = (size_t)f->d.lay.L;
+  const double W = h[0];
+  if (mean) memcpy(mean, h.data() + 2, L * 5 * sizeof(double));
+  for (size_t l = 0; l < L; ++l) {
+    const double* m2 = h.data() + 2 + L * 5 + l * 15;
+    const double* wi = h.data() + 2 + L * 20 + l * 9;
+    if (cov_within) {  // the compact fields back into the dense 5x5 of pk_download_landmarks (a row beyond the estimate: NaN throughout)
+      double* c = cov_within + l * 25;
+      for (int i = 0; i < 25; ++i) c[i] = std::isnan(wi[0]) ? wi[0] : 0.0;
+      c[0] = wi[F_PXX - F_PXX] / W;
+      c[1] = c[5] = wi[F_PXY - F_PXX] / W;
+      c[6] = wi[F_PYY - F_PXX] / W;
+      c[12] = wi[F_CRR - F_PXX] / W;
+      c[13] = c[17] = wi[F_CRG - F_PXX] / W;
+      c[14] = c[22] = wi[F_CRB - F_PXX] / W;
+      c[18] = wi[F_CGG - F_PXX] / W;
+      c[19] = c[23] = wi[F_CGB - F_PXX] / W;
+      c[24] = wi[F_CBB - F_PXX] / W;
+    }
+    if (cov_between) {
+      double* c = cov_between + l * 25;
+      int k = 0;
+      for (int i = 0; i < 5; ++i)
+        for (int j = i; j < 5; ++j) c[i * 5 + j] = c[j * 5 + i] = m2[k++] / W;
+    }
+    if (update_count) update_count[l] = h[2 + L * 29 + l] / W;
+  }
+  if (n_eff) *n_eff = W * W / h[1];
+  return PK_OK;
+}
+
 int pk_step(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw,
             const double* blobs, int32_t B, const int32_t* ids, double u, int32_t weight_domain) {
   int rc;

@@ -143,6 +143,7 @@ struct Options {
   int colour_table_depth = 1024;  // option: levels of the table
   int colour_table_margin = -1;   // option: the host leaves the mode this many levels short of the table's end; -1: min(16, depth / 2); 0: never
   int colour_table = -1;          // option: -1 auto, 0 off, 1 as auto
+  int map_sum_groups = 0;         // the map estimate's particle groups: 0 = map_sum_groups(P, Ls) (pk_kernels.hpp), else forced (tests: many particles per group, ragged last groups)
 };
 
 // One row per knob: the name a caller gives, the member, how the value is taken, the inclusive range, the refusal outside it.
@@ -184,6 +185,7 @@ inline constexpr OptionRow kOptionTable[] = {
      "colour_table_depth: 8 .. 32768 levels (the table stays below 4 GB: 32-bit offsets)"},
     {"colour_table_margin", &Options::colour_table_margin, Take::Range, -1, 32768,
      "colour_table_margin: -1 (auto), 0 (the host never leaves the mode for the table's end) or levels"},
+    {"map_sum_groups", &Options::map_sum_groups, Take::Range, 0, 1024, "map_sum_groups: 0 (chosen from the shape) .. 1024"},
     // "colour_table" itself is taken by pk_set_option in code: switching it off in mid-run gives the slots their colour rows back
 };
 
@@ -315,6 +317,10 @@ struct pk_filter {
   double* out4 = nullptr;
   double* pose_part = nullptr;   // [motion_pose_blocks(P)][4]: per-block sums of x, y, sin h, cos h the last whole-filter motion launch left
   bool pose_part_ok = false;     // ... and nothing has touched the poses since
+  // the map estimate (pk_map_moments / pk_map_summary): nothing until the first call
+  double* ms_part = nullptr;     // [groups][kMapSums][tiles x kMapSumLanes] k_map_partials' sums
+  double* ms_res = nullptr;      // the handle's own maximum log-weight (2 words) | [kMapSumMaxGroups][2] the groups' weight sums | [2 + 30 L] the moments
+  size_t ms_cap = 0;             // doubles of ms_part
   GrowState grow{};                 // section 8(f4) on the device (pk_grow_enable): per-particle new-landmark bookkeeping
   bool grow_on = false;
   int32_t* anc = nullptr;           // P

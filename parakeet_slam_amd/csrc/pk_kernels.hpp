@@ -349,6 +349,19 @@ void launch_ancestors(hipStream_t s, const double* clocal_dev, const double* tot
                       DeviceState* gather = nullptr);  // gather: also gather the poses (fused K5)
 // K6
 void launch_summary_partials(hipStream_t s, DeviceState& d, double* partial_dev, double* out4_dev);
+// The map estimate (pk_k_mapsum.hip): per-landmark moments over the particles, landmarks [0, Ls).  k_map_partials, grid
+// (landmark tiles, particle groups), leaves part[groups][kMapSums][tiles x kMapSumLanes] (5 first moments, 15 second moments --
+// both of mu - the first local particle's mean rows --, 9 within, 1 count) and wpart[groups][2] (sum w, sum w^2); k_map_fold adds them in
+// group order (in place, into group 0's), k_map_finish un-shifts into res[2 + 30 L]: wsum[2] | mean[L][5] | m2[L][15] | within[L][9] | counts[L], rows l >= Ls NaN.
+// weighted: w = exp(logw - gmax), else 1.  The particles are read through src[] where they are: nothing is moved or written.
+constexpr int kMapSumLanes = 256;
+constexpr int kMapSums = 30;
+constexpr int kMapSumMaxGroups = 1024;
+inline int map_sum_tiles(int Ls) { return Ls > 0 ? (Ls + kMapSumLanes - 1) / kMapSumLanes : 1; }
+int map_sum_groups(int64_t P, int Ls, int forced);  // a function of (P, Ls) alone unless forced (option "map_sum_groups") > 0
+inline size_t map_sum_part_doubles(int Ls, int groups) { return (size_t)groups * kMapSums * map_sum_tiles(Ls) * kMapSumLanes; }
+void launch_map_moments(hipStream_t s, const DeviceState& d, int Ls, int weighted, double gmax, int groups, double* part_dev,
+                        double* wpart_dev, double* res_dev);
 // map maintenance
 void launch_materialise(hipStream_t s, DeviceState& d);
 void launch_broadcast_slot(hipStream_t s, DeviceState& d, const unsigned char* slot_dev);

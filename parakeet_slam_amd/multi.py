@@ -91,6 +91,8 @@ def _worker_main(rank, world, device, store_path, backend, P_local, L, means, co
                     conn.send(("ok", None))
                 elif op == "summary":
                     conn.send(("ok", sf.summary()))
+                elif op == "map_summary":
+                    conn.send(("ok", sf.map_summary(cmd[1])))
                 elif op == "poses":  # with the logical index of every slot: the front end answers in the single filter's order
                     conn.send(("ok", (sf.download_poses(), sf.logical_index())))
                 elif op == "landmarks":
@@ -437,6 +439,15 @@ class ShardedFastSLAM(object):
         """:254-276 over all shards."""
         with self._lock:
             return tuple(self._all("summary")[0])
+
+    def map_summary(self, weighting="uniform"):
+        """The map estimate over all shards (FastSLAM.map_summary; sharded.py combines the ranks' moments): rank 0's answer,
+        which is every rank's."""
+        from . import mapsum
+
+        code = mapsum.weighting_code(weighting)
+        with self._lock:
+            return self._all("map_summary", code)[0]
 
     def odom_motion_update(self, odom):
         pass  # :140-146 alpha feature, empty in the reference

@@ -42,7 +42,7 @@ import contextlib
 
 import numpy as np
 
-from . import _lib
+from . import _lib, mapsum
 
 _nullcontext = contextlib.nullcontext
 
@@ -833,3 +833,38 @@ class ShardedFilter(object):
                 s = self._sums.cpu().numpy()
         n = float(self.P_global)
         return float(s[0] / n), float(s[1] / n), float(np.arctan2(s[2], s[3]))
+
+    def map_summary(self, weighting="uniform"):
+        """The map estimate over all shards (``mapsum.MapSummary``, the same on every rank): each rank reduces its own
+        particles on its device (pk_map_moments), one all-gather of the ranks' moments blocks (2 + 30 L doubles each), and
+        Chan's pairwise combination in rank order.  Equal to one filter's estimate to rounding, not bit for bit: the order of
+        the sums differs.  weighting "weights": against the maximum log-weight of the whole filter (all-reduce)."""
+        code = mapsum.weighting_code(weighting)
+        self._complete()
+        f, W = self.f, self.world
+        gmax = None
+        with self._ctx():
+            if code == mapsum.WEIGHTED:
+                f.max_logw_into(self._gmax)
+                if W > 1:
+                    self.comm.all_reduce_max_(self._gmax)
+                gmax = float(self._gmax.cpu().numpy()[0])
+            n = 2 + 30 * self.L
+            err = None
+            try:
+                flat = f.map_moments(code, gmax).flat()
+            except _lib.PkError as e:  # every rank still takes part in the all-gather, and every rank raises behind it
+                flat, err = np.full(n, np.nan), e
+            if W > 1:
+                mine, every = f.new_f64(n), f.new_f64(n * W)
+                mine.copy_(self._to_dev(flat, mine))
+                self.comm.all_gather_(every, mine)
+                rows = every.cpu().numpy().reshape(W, n)
+            else:
+                rows = flat.reshape(1, n)
+        if err is not None:
+            raise err
+        bad = [r for r in range(W) if not rows[r, 0] > 0.0]
+        if bad:
+            raise RuntimeError("map_summary: no estimate from rank(s) %s (their weights do not sum to a positive number)" % bad)
+        return mapsum.finish(mapsum.combine_moments([mapsum.Moments.from_flat(rows[r]) for r in range(W)]))
