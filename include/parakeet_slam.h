@@ -424,6 +424,33 @@ int pk_shard_balanced_errors(pk_filter* f, int64_t* count);
 int pk_probe(int32_t device, const double pose[3], const double mean[5], const double cov[25],
              const double blob[4], const double Qt[16], double* out);
 
+/* ---- math probe ---------------------------------------------------------------
+ * Runs ONE of the float64 primitives the observe kernels are built from (pk_math.hpp, pk_pub_math.hpp, pk_device.hpp) on n
+ * rows of arguments, one element per thread: in[n][arity] -> out[n][outputs], row-major.  Diagnostic: the tests hold each
+ * primitive to an exact reference through it.  n == 0 returns PK_OK without a launch.
+ *   op                        calls                                    arity -> outputs
+ *   PK_MATH_LOG_FEW_ULP       log_few_ulp(x)                           1 -> 1
+ *   PK_MATH_PUB_LOG           pub_log(x)                               1 -> 1
+ *   PK_MATH_PUB_RECIP         pub_recip(x)                             1 -> 1
+ *   PK_MATH_ATAN2             pk_atan2(y, x)                           2 -> 1
+ *   PK_MATH_ROUND_DOWN_F32    (double)pub_round_down_to_float(x)       1 -> 1
+ *   PK_MATH_KEY               double_to_key(x), key_to_double of it    1 -> 2  (both as 64 raw bits in a double's place)
+ *   PK_MATH_FAR_BOUND         pub_far_bound(landmark)                  14 -> 2 (mean x y r g b, pxx pxy pyy, crr crg crb cgg cgb
+ *                                                                               cbb -> fk, fi)
+ *   PK_MATH_PR_FROM_PARTS     pr_from_parts(det2, det3, num2, num3)    4 -> 1 */
+enum {
+  PK_MATH_LOG_FEW_ULP = 0,
+  PK_MATH_PUB_LOG = 1,
+  PK_MATH_PUB_RECIP = 2,
+  PK_MATH_ATAN2 = 3,
+  PK_MATH_ROUND_DOWN_F32 = 4,
+  PK_MATH_KEY = 5,
+  PK_MATH_FAR_BOUND = 6,
+  PK_MATH_PR_FROM_PARTS = 7,
+  PK_MATH_COUNT = 8
+};
+int pk_probe_math(int32_t device, int32_t op, int64_t n, const double* in, double* out);
+
 /* ---- instrumentation ----------------------------------------------------------
  * Kernel launches of the enabled PK_T_* slots are bracketed by hipEvents on the handle's
  * stream: `mask` bit i enables slot i, a negative mask enables all, 0 disables.  pk_timings synchronises, then returns accumulated milliseconds and launch

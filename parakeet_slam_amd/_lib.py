@@ -24,6 +24,10 @@ PK_LANDMARK_POTENTIAL = 0x40000000  # flag in a landmark's count word: potential
 PK_T_NAMES = ("motion", "assoc", "observe", "weights", "resample", "summary", "materialise")
 PK_T_COUNT = len(PK_T_NAMES)
 PK_PROBE_LEN = 79
+(PK_MATH_LOG_FEW_ULP, PK_MATH_PUB_LOG, PK_MATH_PUB_RECIP, PK_MATH_ATAN2, PK_MATH_ROUND_DOWN_F32, PK_MATH_KEY, PK_MATH_FAR_BOUND,
+ PK_MATH_PR_FROM_PARTS) = range(8)
+PK_MATH_SHAPES = {PK_MATH_LOG_FEW_ULP: (1, 1), PK_MATH_PUB_LOG: (1, 1), PK_MATH_PUB_RECIP: (1, 1), PK_MATH_ATAN2: (2, 1),
+                  PK_MATH_ROUND_DOWN_F32: (1, 1), PK_MATH_KEY: (1, 2), PK_MATH_FAR_BOUND: (14, 2), PK_MATH_PR_FROM_PARTS: (4, 1)}  # op -> (arity, outputs)
 PK_ABI_VERSION = 1
 
 _dp = C.POINTER(C.c_double)
@@ -106,6 +110,7 @@ SIGNATURES = {
     "pk_pack_particles": (C.c_int, [_h, _lp, C.c_int64, C.c_void_p]),
     "pk_adopt_particles": (C.c_int, [_h, _lp, C.c_void_p, C.c_int64]),
     "pk_probe": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pk_probe_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp]),
     "pk_enable_timing": (C.c_int, [_h, C.c_int32]),
     "pk_reset_timings": (C.c_int, [_h]),
     "pk_timings": (C.c_int, [_h, _dp, _lp]),
@@ -606,6 +611,20 @@ def probe(pose, mean, cov, blob, Qt=None, device=0):
         K=out[27:47].reshape(5, 4).copy(), weight=out[47], new_mean=out[48:53].copy(),
         new_cov=out[53:78].reshape(5, 5).copy(), log_weight=out[78],
     )
+
+
+def probe_math(op, array, device=0):
+    """One float64 primitive of the kernels (PK_MATH_*) on the rows of ``array`` (n x arity; a flat array for arity 1) on the GPU
+    (pk_probe_math): the n results, or (n, outputs).  PK_MATH_KEY returns (keys uint64[n], round trip float64[n])."""
+    lib = load()
+    arity, outputs = PK_MATH_SHAPES[int(op)]
+    a = f64(array, (-1, arity))
+    n = a.shape[0]
+    out = np.empty((n, outputs), dtype=np.float64)
+    check(lib.pk_probe_math(int(device), int(op), n, dptr(a), dptr(out)))
+    if op == PK_MATH_KEY:
+        return out[:, 0].copy().view(np.uint64), out[:, 1].copy()
+    return out[:, 0].copy() if outputs == 1 else out
 
 
 class HostRng(object):

@@ -1,0 +1,128 @@
+// The math probe (pk_probe_math): the float64 primitives of pk_math.hpp, pk_pub_math.hpp and pk_device.hpp on arrays of
+// arguments, one element per thread, so that the tests can hold each of them to an exact reference over its whole domain
+// (tests/test_gpu_math_probe.py).  The kernels CALL the functions of the three headers -- nothing is restated here: what is
+// measured is what the observe kernels run, inline assembly and all.  Diagnostic only; no kernel of the step is in this file,
+// and the entry point lives here beside its kernels.
+#include "pk_device.hpp"
+#include "pk_filter.hpp"
+#include "pk_pub_math.hpp"
+
+namespace pk {
+
+__device__ __forceinline__ double bits_to_double(unsigned long long b) {
+  double x;
+  memcpy(&x, &b, 8);
+  return x;
+}
+
+// in[n][arity(OP)] -> out[n][outputs(OP)], row-major
+template <int OP>
+__global__ void __launch_bounds__(256) k_probe_math(const double* __restrict__ in, double* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if constexpr (OP == PK_MATH_LOG_FEW_ULP) {
+    out[i] = log_few_ulp(in[i]);
+  } else if constexpr (OP == PK_MATH_PUB_LOG) {
+    out[i] = pub_log(in[i]);
+  } else if constexpr (OP == PK_MATH_PUB_RECIP) {
+    out[i] = pub_recip(in[i]);
+  } else if constexpr (OP == PK_MATH_ATAN2) {
+    out[i] = pk_atan2(in[2 * i], in[2 * i + 1]);
+  } else if constexpr (OP == PK_MATH_ROUND_DOWN_F32) {
+    out[i] = (double)pub_round_down_to_float(in[i]);
+  } else if constexpr (OP == PK_MATH_KEY) {  // both outputs are 64 raw bits
+    const unsigned long long k = double_to_key(in[i]);
+    out[2 * i] = bits_to_double(k);
+    out[2 * i + 1] = key_to_double(k);
+  } else if constexpr (OP == PK_MATH_FAR_BOUND) {  // the compact row order of pk_layout.hpp
+    const double* r = in + (int64_t)F_COUNT_FIELDS * i;
+    Landmark<double> lm;
+    lm.mx = r[F_MX];
+    lm.my = r[F_MY];
+    lm.mr = r[F_MR];
+    lm.mg = r[F_MG];
+    lm.mb = r[F_MB];
+    lm.pxx = r[F_PXX];
+    lm.pxy = r[F_PXY];
+    lm.pyy = r[F_PYY];
+    lm.crr = r[F_CRR];
+    lm.crg = r[F_CRG];
+    lm.crb = r[F_CRB];
+    lm.cgg = r[F_CGG];
+    lm.cgb = r[F_CGB];
+    lm.cbb = r[F_CBB];
+    lm.count = 0;
+    double fk, fi;
+    pub_far_bound(lm, fk, fi);
+    out[2 * i] = fk;
+    out[2 * i + 1] = fi;
+  } else {
+    static_assert(OP == PK_MATH_PR_FROM_PARTS, "unknown op");
+    out[i] = pr_from_parts(in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3]);
+  }
+}
+
+namespace {
+
+template <int OP>
+void launch_one(hipStream_t s, const double* in_dev, double* out_dev, int64_t n) {
+  hipLaunchKernelGGL(k_probe_math<OP>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in_dev, out_dev, n);
+}
+
+// rows of doubles per element, in and out; 0 for an unknown op
+int math_probe_arity(int op) {
+  switch (op) {
+    case PK_MATH_LOG_FEW_ULP:
+    case PK_MATH_PUB_LOG:
+    case PK_MATH_PUB_RECIP:
+    case PK_MATH_ROUND_DOWN_F32:
+    case PK_MATH_KEY: return 1;
+    case PK_MATH_ATAN2: return 2;
+    case PK_MATH_FAR_BOUND: return F_COUNT_FIELDS;
+    case PK_MATH_PR_FROM_PARTS: return 4;
+    default: return 0;
+  }
+}
+int math_probe_outputs(int op) { return op == PK_MATH_KEY || op == PK_MATH_FAR_BOUND ? 2 : 1; }
+
+void launch_probe_math(hipStream_t s, int op, const double* in_dev, double* out_dev, int64_t n) {
+  switch (op) {
+    case PK_MATH_LOG_FEW_ULP: return launch_one<PK_MATH_LOG_FEW_ULP>(s, in_dev, out_dev, n);
+    case PK_MATH_PUB_LOG: return launch_one<PK_MATH_PUB_LOG>(s, in_dev, out_dev, n);
+    case PK_MATH_PUB_RECIP: return launch_one<PK_MATH_PUB_RECIP>(s, in_dev, out_dev, n);
+    case PK_MATH_ATAN2: return launch_one<PK_MATH_ATAN2>(s, in_dev, out_dev, n);
+    case PK_MATH_ROUND_DOWN_F32: return launch_one<PK_MATH_ROUND_DOWN_F32>(s, in_dev, out_dev, n);
+    case PK_MATH_KEY: return launch_one<PK_MATH_KEY>(s, in_dev, out_dev, n);
+    case PK_MATH_FAR_BOUND: return launch_one<PK_MATH_FAR_BOUND>(s, in_dev, out_dev, n);
+    case PK_MATH_PR_FROM_PARTS: return launch_one<PK_MATH_PR_FROM_PARTS>(s, in_dev, out_dev, n);
+    default: return;
+  }
+}
+
+}  // namespace
+
+}  // namespace pk
+
+extern "C" int pk_probe_math(int32_t device, int32_t op, int64_t n, const double* in, double* out) {
+  if (!in || !out) return fail(PK_ERR_INVALID, "pk_probe_math: NULL argument");
+  const int arity = math_probe_arity(op);
+  if (arity == 0) return fail(PK_ERR_INVALID, "pk_probe_math: unknown op %d", op);
+  if (n < 0 || n > 2147483647LL) return fail(PK_ERR_INVALID, "pk_probe_math: n = %lld out of range", (long long)n);
+  int ndev = pk_device_count();
+  if (ndev <= 0) return fail(PK_ERR_HIP, "pk_probe_math: no HIP device visible (the HIP path has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(PK_ERR_INVALID, "pk_probe_math: device %d of %d", device, ndev);
+  if (n == 0) return PK_OK;
+  PK_HIP(hipSetDevice(device));
+  const size_t n_in = (size_t)n * arity, n_out = (size_t)n * math_probe_outputs(op);
+  double* dev = nullptr;
+  PK_HIP(hipMalloc((void**)&dev, (n_in + n_out) * sizeof(double)));
+  hipError_t e = hipMemcpy(dev, in, n_in * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_probe_math(nullptr, op, dev, dev + n_in, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dev + n_in, n_out * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(dev);
+  if (e != hipSuccess) return fail(PK_ERR_HIP, "pk_probe_math: %s", hipGetErrorString(e));
+  return PK_OK;
+}

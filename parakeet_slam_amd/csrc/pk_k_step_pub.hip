@@ -487,10 +487,8 @@ __device__ __forceinline__ bool pub_lean_pair(PubSlots (&q)[2], double (&pse_out
     const double a2base = 2.0 * Consts<double>::log_two_pi + (double)e2i * ln2;
     const double a3base = 3.0 * Consts<double>::log_two_pi + (double)e3i * ln2;
     const double khi = a2base + a3base, klo = khi - 2.0 * ln2;  // klo <= 5 log 2 pi + log(det2 det3) <= khi
-    const bool pd3 = sane && lm.crr > 0.0 && adj3.f > 0.0 && lm.pxx > 0.0;
-    const double itr3 = pd3 ? pub_recip(fmax(fmax(lm.crr + (fabs(lm.crg) + fabs(lm.crb)), lm.cgg + (fabs(lm.crg) + fabs(lm.cgb))),
-                                             lm.cbb + (fabs(lm.crb) + fabs(lm.cgb))))
-                            : 0.0;
+    bool pd3;
+    const double itr3 = pub_far_slope(lm, sane, det2, det3, adj3.f, pd3);
     // the landmark's own far bound against the scan's (pub_keysN<CHK>): certain only with room for pub_log's error (1e-12)
     const bool holds = itr3 >= (double)bnd[j].y && klo >= (double)bnd[j].x + 1e-9;
     // the verdict (pub_keysN's round): certain on either side of the strip 1489 ... 1491.5, which the usual body evaluates exactly
@@ -594,14 +592,14 @@ __device__ __forceinline__ void pub_keysN(PubSlotsT<SL> (&q)[N], const Landmark<
     // kbase + |d|^2 / rowmax, and a blob whose bound lies beyond the underflow edge has probability 0 whatever the rest
     // says.  Once a landmark has been seen a few times its colour block is tight and every look-alike's blob ends here:
     // when that holds for all lanes of the wave the round's arithmetic is skipped
-    // (both blocks positive definite: adj3.f = crr cgg - crg^2, the determinants > 0 are part of sane)
-    pd3[j] = sane[j] && lm.crr > 0.0 && adj3[j].f > 0.0 && lm.pxx > 0.0;
-    if constexpr (PRE)
+    // (both blocks CERTAINLY positive definite: pub_far_slope, pk_pub_math.hpp -- the one statement of it; the caller's value
+    // came from there too, through pub_far_bound)
+    if constexpr (PRE) {
       itr3[j] = pre_itr3[j];
-    else
-      itr3[j] = pd3[j] ? pub_recip(fmax(fmax(lm.crr + (fabs(lm.crg) + fabs(lm.crb)), lm.cgg + (fabs(lm.crg) + fabs(lm.cgb))),
-                                         lm.cbb + (fabs(lm.crb) + fabs(lm.cgb))))
-                       : 0.0;
+      pd3[j] = itr3[j] > 0.0;
+    } else {
+      itr3[j] = pub_far_slope(lm, sane[j], det2[j], det3[j], adj3[j].f, pd3[j]);
+    }
   }
   if constexpr (CHK) {
     bool viol[N];

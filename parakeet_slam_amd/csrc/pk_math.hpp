@@ -116,8 +116,9 @@ __device__ __forceinline__ double fma_k(double a, double b, double k) {
 }
 
 // atan2 for the EXPECTED BEARING of a landmark (prkt_core_v2.py:408, :473, :871: math.atan2(fy - sy, fx - sx)), within
-// 2 ulp, in ~47 float64 instructions against the library's ~100 + 40 constant moves (every particle x landmark pays
-// one, in the issue-bound gates phase of the one-pass kernels).  ONE division for both range reductions:
+// 2.3 ulp (measured on the device against mpmath over 1.1e6 points: 2.2974 just above the tan(pi / 8) switch, where
+// pi / 4 is added to a small negative atan; tests/test_gpu_math_probe.py asserts 1.5 times that), in ~47 float64
+// instructions against the library's ~100 + 40 constant moves (every particle x landmark pays one, in the issue-bound gates phase of the one-pass kernels).  ONE division for both range reductions:
 //   t = min(|x|, |y|) / max(|x|, |y|) in [0, 1];  beyond tan(pi / 8):  atan t = pi / 4 + atan((t - 1) / (t + 1)), and
 //   (t - 1) / (t + 1) = (mn - mx) / (mn + mx) -- the same quotient with another numerator and denominator --
 // so r = num / den lies in [-tan(pi / 8), tan(pi / 8)] and atan r = r + r s Q(s), s = r^2, Q of degree 10 (coefficients:
@@ -227,7 +228,9 @@ __device__ __forceinline__ T probability_of_match(const Landmark<T>& f, T sx, T 
 }
 
 // Natural logarithm accurate to 2 ulp (checked on the host against logl over 2e7 arguments from
-// 1e-304 to 1e304 and around 1): log(x) = e ln 2 + 2 atanh(s), s = (m - 1) / (m + 1), with x = m 2^e
+// 1e-304 to 1e304 and around 1; on the device, with fma_k's inline v_fma_f64, against mpmath / longdouble over 7.7e5
+// arguments that aim at 1, at the mantissa switch and at the powers of two: worst 1.9956,
+// tests/test_gpu_math_probe.py): log(x) = e ln 2 + 2 atanh(s), s = (m - 1) / (m + 1), with x = m 2^e
 // and m in [sqrt(1/2), sqrt(2)) so that s^2 <= 0.0295 and eleven terms of the atanh series leave
 // < 1e-18.  About 45 float64 instructions against ~95 for the library log.  Used for the importance
 // factor (:844-849) and for the probabilities of contested pairs (:439, :446) -- quantities whose

@@ -19,32 +19,13 @@ import sys
 import numpy as np
 import pytest
 
-from oracle.fastslam_oracle import low_variance_ancestors, synthetic_scan, synthetic_world, truth_step
+from oracle.fastslam_oracle import synthetic_scan, synthetic_world, truth_step
+from resample_reference import ancestors_match_oracle
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P2, L2 = 100000, 2000
-
-
-def ancestors_match_oracle(anc, w, u):
-    """Device ancestors == the oracle's on the same weights.  Ancestors are discrete: the device sums
-    the weights in 1024-blocks (Kogge-Stone inside a wave), the reference sequentially, so a comb point
-    u r + k r that lies within a few ulp of a cumulative sum may legitimately fall on either side of it
-    (expected rate ~ P^2 eps per resample: 1e-6 at P = 1e5).  Anything else is an error."""
-    ref = low_variance_ancestors(w, u)
-    bad = np.flatnonzero(anc != ref)
-    if bad.size == 0:
-        return True
-    c = np.cumsum(w)
-    r = c[-1] / float(len(w))
-    for k in bad:
-        t = u * r + k * r
-        j = min(anc[k], ref[k])
-        assert abs(anc[k] - ref[k]) == 1 and abs(t - c[j]) <= 8 * np.finfo(float).eps * c[j], \
-            "slot %d: device ancestor %d, oracle %d, comb point %.17g vs cumulative sum %.17g" % (k, anc[k], ref[k], t, c[j])
-    assert bad.size <= 2
-    return True
 
 
 @pytest.mark.parametrize("P", [10000, 100000])

@@ -65,7 +65,7 @@ def kernels():
 def test_the_library_holds_the_kernels_of_the_path(kernels):
     names = " ".join(k["symbol"] for k in kernels)
     for needle in ("k_motion", "k_step_pub", "k_step_regs", "k_step_fused", "k_observe", "k_assoc_grid", "k_candidates", "k_cand_entries",
-                   "k_scan_local", "k_ancestors", "k_summary"):
+                   "k_scan_local", "k_ancestors", "k_summary", "k_probe_math"):
         assert needle in names, needle
     assert len(kernels) >= 50
 
