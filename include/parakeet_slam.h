@@ -272,6 +272,42 @@ int pk_map_moments(pk_filter* f, int32_t weighting, double gmax, double wsum[2],
  * update_count[L], n_eff[1].  Any output may be NULL. */
 int pk_map_summary(pk_filter* f, int32_t weighting, double* mean, double* cov_within, double* cov_between, double* update_count, double* n_eff);
 
+/* ---- the path estimate: lineages recorded at every resample, traced back ("The path estimate") --------
+ * FastSLAM factors the posterior over the robot's PATH; pk_resample overwrites the generation it resamples, so without a record
+ * the filter knows the end of the path only (the reference keeps no more either: prkt_core_v2.py:210-252 replaces
+ * self.particles).  pk_path_enable(capacity > 0) allocates a ring of the last `capacity` generations -- counted in
+ * pk_device_bytes -- and from then on every pk_resample (those of pk_step included) records one ROW behind its own kernels:
+ *   poses      x, y, heading of all P particles of the generation that was just resampled (the pose at which the scan was
+ *              applied, after every motion update since the last resample), float64;
+ *   ancestors  anc[k] = the index IN THAT GENERATION of the parent of particle k of the new generation, int32.
+ * A full ring overwrites its oldest row; `recorded` counts the rows ever recorded.  capacity 0 switches recording off and
+ * releases the memory; any pk_path_enable starts from an empty ring.  Off is the default: a step then launches what it always did.
+ * Row convention everywhere: rows 0 .. held - 1 are the recorded steps, oldest first; row `held` is the CURRENT generation.
+ * The lineage of a current particle k: j_held = k, j_t = anc_t[j_{t + 1}]; its path is pose_t[j_t], then its current pose.
+ * pk_upload_poses empties the ring (a replaced population has no lineage); pk_upload_pose does not (only the present changes).
+ * While recording is on, the sharded protocol (pk_pack_particles, pk_adopt_particles, every pk_shard_* adoption,
+ * pk_shard_state_dev) and the split step (pk_observe_staged_range) are refused with PK_ERR_STATE: lineages across ranks are
+ * not recorded.  Every call below except pk_path_enable is PK_ERR_STATE while recording is off.
+ *   pk_path_shape     capacity, rows held, rows ever recorded since pk_path_enable.  Any output may be NULL.
+ *   pk_path_download  rows [t0, t1) of the held ones, n = t1 - t0: poses[n][P][3], ancestors[n][P].  Either may be NULL.
+ *   pk_path_upload    replaces the ring by n <= capacity rows (snapshot restore, tests); recorded >= n is the counter to go on
+ *                     from.  Any map is taken (ancestors need not be sorted); one outside [0, P) is PK_ERR_INVALID.
+ *   pk_path_trace     the paths of the n listed current particles: out[n][held + 1][3].  Pure gathers: bit for bit what was
+ *                     recorded.  n == 0 is fine.
+ *   pk_path_summary   the smoothed path over the P lineages, every current particle counting once (pk_summary's convention:
+ *                     behind a resample the population is the estimate).  Per row: mean[3] = mean x, mean y, circular mean
+ *                     heading; spread[4] = var x, cov xy, var y, mean resultant length of the headings; survivors = the
+ *                     number of distinct ancestors j_t the population still has in that row (exact).  The position moments
+ *                     are taken about particle 0's lineage, so a row with ONE survivor has its recorded pose as mean, bit for
+ *                     bit, and exactly zero spread.  Integer atomics and fixed-order sums only: the same bits on every call.
+ *                     Any output may be NULL. */
+int pk_path_enable(pk_filter* f, int32_t capacity);
+int pk_path_shape(const pk_filter* f, int32_t* capacity, int32_t* held, int64_t* recorded);
+int pk_path_download(pk_filter* f, int32_t t0, int32_t t1, double* poses, int32_t* ancestors);
+int pk_path_upload(pk_filter* f, int32_t n, int64_t recorded, const double* poses, const int32_t* ancestors);
+int pk_path_trace(pk_filter* f, const int64_t* particles, int64_t n, double* out);
+int pk_path_summary(pk_filter* f, double* mean, double* spread, int64_t* survivors);
+
 /* One whole cam_cb without host synchronisation: reset weights, motion, observe,
  * resample.  Arguments as in the calls above. */
 int pk_step(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed,

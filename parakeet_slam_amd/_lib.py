@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from . import mapsum
+from . import mapsum, path
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libparakeet_slam.so")
@@ -70,6 +70,12 @@ SIGNATURES = {
     "pk_pose_sums": (C.c_int, [_h, _dp]),
     "pk_map_moments": (C.c_int, [_h, C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "pk_map_summary": (C.c_int, [_h, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
+    "pk_path_enable": (C.c_int, [_h, C.c_int32]),
+    "pk_path_shape": (C.c_int, [_h, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "pk_path_download": (C.c_int, [_h, C.c_int32, C.c_int32, _dp, _ip]),
+    "pk_path_upload": (C.c_int, [_h, C.c_int32, C.c_int64, _dp, _ip]),
+    "pk_path_trace": (C.c_int, [_h, _lp, C.c_int64, _dp]),
+    "pk_path_summary": (C.c_int, [_h, _dp, _dp, _lp]),
     "pk_step": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32,
                           _ip, C.c_double, C.c_int32]),
     "pk_shard_max_logw": (C.c_int, [_h, _dp]),
@@ -344,6 +350,47 @@ class DeviceFilter(object):
         count, n_eff = np.empty(L), np.empty(1)
         check(self._lib.pk_map_summary(self._h, int(weighting), dptr(mean), dptr(within), dptr(between), dptr(count), dptr(n_eff)))
         return mapsum.MapSummary(mean, within, between, count, n_eff[0])
+
+    # -- the path estimate (pk_path_*): rows 0 .. held - 1 are the recorded steps, oldest first; row held is the current generation
+    def path_enable(self, capacity):
+        """A ring of the last ``capacity`` resampled generations (0: off, memory released); every resample records a row."""
+        check(self._lib.pk_path_enable(self._h, int(capacity)))
+
+    def path_shape(self):
+        """(capacity, rows held, rows ever recorded)."""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int64()
+        check(self._lib.pk_path_shape(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def path_download(self, t0=0, t1=None):
+        """(poses (n, P, 3), ancestors (n, P) int32) of the held rows [t0, t1)."""
+        t1 = self.path_shape()[1] if t1 is None else int(t1)
+        n = max(t1 - int(t0), 0)
+        poses, anc = np.empty((n, self.P, 3), dtype=np.float64), np.empty((n, self.P), dtype=np.int32)
+        check(self._lib.pk_path_download(self._h, int(t0), t1, dptr(poses), iptr(anc)))
+        return poses, anc
+
+    def path_upload(self, poses, ancestors, recorded=None):
+        """Replaces the ring by n rows (snapshot restore, tests); recorded: the counter to go on from (default n)."""
+        a = np.ascontiguousarray(ancestors, dtype=np.int32).reshape(-1, self.P)
+        n = a.shape[0]
+        p = f64(poses, (n, self.P, 3))
+        check(self._lib.pk_path_upload(self._h, n, n if recorded is None else int(recorded), dptr(p), iptr(a)))
+
+    def path_trace(self, particles):
+        """The paths of the listed current particles, (len, held + 1, 3): bit for bit what was recorded."""
+        idx = np.ascontiguousarray(particles, dtype=np.int64).reshape(-1)
+        out = np.empty((idx.size, self.path_shape()[1] + 1, 3), dtype=np.float64)
+        check(self._lib.pk_path_trace(self._h, lptr(idx), idx.size, dptr(out)))
+        return out
+
+    def path_summary(self):
+        """The smoothed path over the P lineages as ``path.PathSummary``: per row mean (x, y, circular mean heading), spread
+        (var x, cov xy, var y, mean resultant length) and the number of distinct ancestors the population still has there."""
+        _, held, recorded = self.path_shape()
+        mean, spread, surv = np.empty((held + 1, 3)), np.empty((held + 1, 4)), np.empty(held + 1, dtype=np.int64)
+        check(self._lib.pk_path_summary(self._h, dptr(mean), dptr(spread), lptr(surv)))
+        return path.PathSummary(mean, spread, surv, recorded - held)
 
     def step(self, v, w, dt, blobs, u, z=None, seed=0, draw=0, ids=None, domain=PK_WEIGHTS_LINEAR):
         b = f64(blobs).reshape(-1, 4)

@@ -545,6 +545,11 @@ class FastSLAM(object):
     readings in HBM, ``readings_dropped()`` counts what did not fit) -- nothing per particle crosses to the host in a step;
     bookkeeping="host" is the per-particle host loop of the reference (and the only one on the dense layout).
     ``record_ids`` (default: only with bookkeeping="host"): keep ``last_ids`` / ``last_ancestors`` of every step.
+
+    record_path=T (default 0: off): every resample records the generation it worked on and its ancestors in a ring of the last
+    T steps on the device (pk_path_enable: 28 bytes per particle and step); ``path_summary()`` is the smoothed path over the
+    surviving lineages with the number of distinct ancestors left per step, ``particle_paths(indices)`` the paths of single
+    particles.  One GPU only: with devices=[several] it is refused.
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -570,6 +575,9 @@ class FastSLAM(object):
                                  "(bookkeeping='device'): host lists cannot follow a particle from one GPU to another")
             if a["device"] not in (0, list(devices)[0]):
                 raise ValueError("FastSLAM: give either device= or devices=, not both")
+            if a["record_path"]:
+                raise ValueError("FastSLAM(devices=[...], record_path=...): the path is recorded on one GPU only -- lineages "
+                                 "across ranks are out of scope (the sharded resample is refused on a recording filter)")
             return ShardedFastSLAM(a["preset_features"], num_particles=a["num_particles"], devices=list(devices),
                                    weight_domain=a["weight_domain"], rng=a["rng"], seed=a["seed"],
                                    publish_debug=a["publish_debug"], new_landmarks=a["new_landmarks"],
@@ -581,7 +589,7 @@ class FastSLAM(object):
 
     def __init__(self, preset_features=[], num_particles=50, device=0, weight_domain="linear", rng="global",
                  seed=0, publish_debug=None, new_landmarks=False, spare_landmarks=0, pair_threshold=30.0, devices=None,
-                 bookkeeping="device", reading_capacity=64, record_ids=None):
+                 bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0):
         if devices is not None and len(list(devices)) == 1:
             device = list(devices)[0]
         self._lock = threading.RLock()
@@ -629,6 +637,12 @@ class FastSLAM(object):
                 used=[0] * P,                        # spare slots in use
                 slot_id=[dict() for _ in range(P)])  # spare slot -> feature id
         self.record_ids = (not self._nl_device) if record_ids is None else bool(record_ids)
+        self._record_path = int(record_path)
+        if self._record_path < 0:
+            self._filter.close()
+            raise ValueError("record_path must be a number of steps >= 0")
+        if self._record_path:
+            self._filter.path_enable(self._record_path)
         self.Qt = _default_Qt()
         self._domain = {"linear": _lib.PK_WEIGHTS_LINEAR, "log": _lib.PK_WEIGHTS_LOG}[weight_domain]
         if rng not in ("global", "device"):
@@ -921,6 +935,24 @@ class FastSLAM(object):
         with self._lock:
             return self._filter.map_summary(code)
 
+    def _need_path(self, who):
+        if not self._record_path:
+            raise ValueError("%s: this filter does not record its path (FastSLAM(..., record_path=T))" % who)
+
+    def path_summary(self):
+        """The path estimate (``path.PathSummary``): per step of the ring, oldest first, and for the current generation last, the
+        mean pose over the lineages of the current particles, their spread, and how many distinct ancestors they still have
+        there -- the trajectory the filter NOW believes in, not the string of per-step summary() values."""
+        self._need_path("path_summary")
+        with self._lock:
+            return self._filter.path_summary()
+
+    def particle_paths(self, indices):
+        """The paths of the listed current particles, array (len, held + 1, 3) of (x, y, heading); the last row is particles[i]."""
+        self._need_path("particle_paths")
+        with self._lock:
+            return self._filter.path_trace(indices)
+
     # ------------------------------------------------------------------ snapshot / restore
     def save_state(self, path):
         """Whole filter state -> .npz (poses, weights, every particle's landmark means /
@@ -934,6 +966,9 @@ class FastSLAM(object):
                 extra = _nl_snapshot_arrays(*self._filter.grow_download(), L0=self._L0)
             elif self._grow:
                 extra = _nl_snapshot(self._nl())
+            if self._record_path:
+                extra["path_poses"], extra["path_ancestors"] = self._filter.path_download()
+                extra["path_recorded"] = np.int64(self._filter.path_shape()[2])
             np.savez_compressed(
                 path, poses=poses, means=m, covs=c, counts=k, Qt=np.asarray(self.Qt, dtype=np.float64),
                 immutable=np.array([bool(f.__immutable__) for f in self._features], dtype=np.uint8),
@@ -953,6 +988,12 @@ class FastSLAM(object):
                 raise ValueError("snapshot: no new-landmark bookkeeping (nl_* arrays) for a filter with new_landmarks=True%s"
                                  % ("; it was written in the old pickled format" if "new_landmarks" in d.files else ""))
             have_nl = "nl_offsets" in d.files and self._grow
+            have_path = self._record_path and "path_ancestors" in d.files
+            if have_path:
+                n = d["path_ancestors"].shape[0]
+                if d["path_ancestors"].shape != (n, P) or d["path_poses"].shape != (n, P, 3) or n > self._record_path:
+                    raise ValueError("snapshot: a path of %s x %s does not fit this filter's ring of %d steps x %d particles"
+                                     % (d["path_ancestors"].shape[0], d["path_ancestors"].shape[1:], self._record_path, P))
             if have_nl:  # everything is checked before anything is assigned
                 _nl_check_snapshot(d, P, self._L0, L, self._spare, self._filter.grow_shape()[2] if self._nl_device else None)
 
@@ -968,6 +1009,8 @@ class FastSLAM(object):
                 self._filter.grow_upload(0, P, *_nl_arrays_from_snapshot(d, P, self._L0, S, R))
             elif have_nl:
                 self._nl_assign(*_nl_restore(d, P))
+            if have_path:  # (behind upload_poses, which empties the ring; a snapshot without a path leaves it empty)
+                self._filter.path_upload(d["path_poses"], d["path_ancestors"], int(d["path_recorded"]))
             self._touch()
 
     def close(self):

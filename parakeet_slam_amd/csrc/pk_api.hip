@@ -5,7 +5,8 @@
 // (summary's division and atan2, prkt_core_v2.py:273-275) and the per-blob unit ray
 // direction cos/sin (prkt_core_v2.py:510), which are O(B), not O(P*L).
 // This file: the filter's lifecycle and transfers, motion, resample, the step, the new-landmark bookkeeping, options, timing and
-// the probe.  The observe pipeline is pk_api_observe.hip, the multi-GPU protocol pk_api_shard.hip; pk_filter.hpp is what they share.
+// the probe.  The observe pipeline is pk_api_observe.hip, the multi-GPU protocol pk_api_shard.hip, the path estimate pk_api_path.hip;
+// pk_filter.hpp is what they share.
 #include "pk_filter.hpp"
 
 extern "C" {
@@ -424,6 +425,7 @@ int pk_upload_poses(pk_filter* f, const double* xyhw) {
   PK_HIP(hipMemcpyAsync(f->d.logw[c], soa.data() + 3 * P, P * 8, hipMemcpyHostToDevice, f->stream));
   PK_HIP(hipStreamSynchronize(f->stream));
   f->gmax_fused = false;
+  path_clear(f);  // a replaced population has no lineage
   return PK_OK;
 }
 
@@ -696,6 +698,7 @@ int pk_resample(pk_filter* f, double u, int32_t weight_domain, int64_t* ancestor
     }
   }
   if (f->grow_on) launch_grow_gather(f->stream, f->grow, f->anc, d.P);  // the bookkeeping follows the particles (:243)
+  if (f->path.cap && (rc = path_record(f))) return rc;  // the generation that was resampled and its ancestors, into the ring
   PK_LAUNCH_CHECK("pk_resample");
   f->src_identity = false;
   f->gmax_fused = false;

@@ -932,6 +932,7 @@ int pk_staged_takes_regs(pk_filter* f) {
 
 int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1, int32_t first, int32_t last) {
   if (!f) return fail(PK_ERR_INVALID, "pk_observe_staged_range: NULL handle");
+  if (int rc = refuse_path(f, "pk_observe_staged_range")) return rc;
   if (p0 < 0 || p1 < p0 || p1 > f->d.P) return fail(PK_ERR_INVALID, "pk_observe_staged_range: bad particle range [%lld, %lld)", (long long)p0, (long long)p1);
   if (f->grow_on) return fail(PK_ERR_STATE, "pk_observe_staged_range: the new-landmark bookkeeping (pk_grow_enable) runs behind whole observes (pk_observe / pk_observe_staged)");
   int rc;

@@ -67,6 +67,15 @@ int refuse_balanced(const pk_filter* f, const char* who) {
   return PK_OK;
 }
 
+// The path ring (pk_path_enable) records the lineages of ONE filter's pk_resample: what builds a generation any other way -- the
+// exchange of the sharded filter, the balanced placement, the split step -- is refused while it is on, ahead of everything else
+// the entry point does (a NULL handle passes: the check that follows refuses it).
+int refuse_path(const pk_filter* f, const char* who) {
+  if (f && f->path.cap)
+    return fail(PK_ERR_STATE, "%s: the path is being recorded (pk_path_enable): lineages across ranks and split steps are not; switch it off with pk_path_enable(f, 0) first", who);
+  return PK_OK;
+}
+
 extern "C" {
 
 // ---- sharded resampling ---------------------------------------
@@ -129,6 +138,7 @@ static size_t record_stride(const pk_filter* f) { return kPoseRecordBytes + f->d
 int64_t pk_particle_bytes(const pk_filter* f) { return f ? (int64_t)record_stride(f) : -1; }
 
 int pk_pack_particles(pk_filter* f, const int64_t* local_idx, int64_t n, void* dev_buf) {
+  if (int rc = refuse_path(f, "pk_pack_particles")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (!f || n < 0 || (n > 0 && (!local_idx || !dev_buf))) return fail(PK_ERR_INVALID, "pk_pack_particles: bad argument");
   // (pk_particle_bytes() counts the bookkeeping's tail, k_pack writes records without one -- and pk_adopt_particles
@@ -151,6 +161,7 @@ int pk_pack_particles(pk_filter* f, const int64_t* local_idx, int64_t n, void* d
 }
 
 int pk_adopt_particles(pk_filter* f, const int64_t* src, const void* dev_buf, int64_t n_received) {
+  if (int rc = refuse_path(f, "pk_adopt_particles")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   poses_change(f);
   if (!f || !src || n_received < 0 || (n_received > 0 && !dev_buf)) return fail(PK_ERR_INVALID, "pk_adopt_particles: bad argument");
@@ -314,6 +325,7 @@ int pk_shard_pack_slots_dev(pk_filter* f, int64_t j0, int64_t j1, int64_t slot_l
 }
 
 int pk_shard_adopt_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t n_received) {
+  if (int rc = refuse_path(f, "pk_shard_adopt_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (int rc = refuse_grow(f, "pk_shard_adopt_dev")) return rc;
   poses_change(f);
@@ -333,6 +345,7 @@ int pk_shard_adopt_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t
 }
 
 int pk_shard_adopt_local_dev(pk_filter* f, int32_t rank) {
+  if (int rc = refuse_path(f, "pk_shard_adopt_local_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (int rc = refuse_grow(f, "pk_shard_adopt_local_dev")) return rc;
   poses_change(f);
@@ -353,6 +366,7 @@ int pk_shard_adopt_local_dev(pk_filter* f, int32_t rank) {
 }
 
 int pk_shard_adopt_remote_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t n_received) {
+  if (int rc = refuse_path(f, "pk_shard_adopt_remote_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (int rc = refuse_grow(f, "pk_shard_adopt_remote_dev")) return rc;
   poses_change(f);
@@ -456,6 +470,7 @@ int pk_shard_download_balanced_plan(pk_filter* f, int64_t* rel, int64_t* Hl, int
 }
 
 int pk_shard_state_dev(pk_filter* f, double* dev_out) {
+  if (int rc = refuse_path(f, "pk_shard_state_dev")) return rc;
   if (!f || !dev_out) return fail(PK_ERR_INVALID, "pk_shard_state_dev: NULL argument");
   int rc;
   if ((rc = use_device(f))) return rc;
@@ -578,6 +593,7 @@ int pk_shard_pack_balanced_loop_dev(pk_filter* f, int64_t keep, int64_t a0, int6
 
 int pk_shard_adopt_balanced_dev(pk_filter* f, const int64_t* table, int32_t world, int32_t rank, const void* dev_recv,
                                 int64_t n_received, int32_t mode) {
+  if (int rc = refuse_path(f, "pk_shard_adopt_balanced_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   poses_change(f);
   if (!f || !table || world < 1 || world > 64 || rank < 0 || rank >= world || n_received < 0 || mode < 0 || mode > 2 ||

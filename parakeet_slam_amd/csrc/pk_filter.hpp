@@ -3,6 +3,7 @@
 //   pk_api.hip          lifecycle, transfers, motion, resample, the step, new-landmark bookkeeping, options, timing, the probe
 //   pk_api_observe.hip  the observe pipeline: staging, routing, association, the one-pass stages, the colour table's host side
 //   pk_api_shard.hip    the multi-GPU protocol: host-side, device-resident and balanced
+//   pk_api_path.hip     the path estimate: the ring of resampled generations, its transfers, trace and summary
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -321,6 +322,16 @@ struct pk_filter {
   double* ms_part = nullptr;     // [groups][kMapSums][tiles x kMapSumLanes] k_map_partials' sums
   double* ms_res = nullptr;      // the handle's own maximum log-weight (2 words) | [kMapSumMaxGroups][2] the groups' weight sums | [2 + 30 L] the moments
   size_t ms_cap = 0;             // doubles of ms_part
+  // the path estimate (pk_path_enable; pk_api_path.hip): the ring, and pk_path_trace's / pk_path_summary's scratch -- nothing until first asked for
+  PathRing path{};
+  int64_t* pt_idx = nullptr;     // [pt_cap] the particles of one pk_path_trace chunk
+  double* pt_out = nullptr;      // [pt_cap][rows][3] their paths
+  int64_t pt_cap = 0, pt_out_cap = 0;
+  unsigned* ps_cnt = nullptr;    // [3][P] descendant counts of three consecutive rows
+  double* ps_ref = nullptr;      // [ps_rows][3] particle 0's lineage
+  double* ps_part = nullptr;     // [ps_rows][path_blocks(P)][kPathSums]
+  double* ps_res = nullptr;      // [ps_rows][kPathSums]
+  int64_t ps_rows = 0;
   GrowState grow{};                 // section 8(f4) on the device (pk_grow_enable): per-particle new-landmark bookkeeping
   bool grow_on = false;
   int32_t* anc = nullptr;           // P
@@ -441,3 +452,9 @@ int stage_ml_scan(pk_filter* f, const double* blobs, int B);
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out, bool reset);
 // pk_api_shard.hip
 int refuse_balanced(const pk_filter* f, const char* who);
+int refuse_path(const pk_filter* f, const char* who);
+// pk_api_path.hip
+int path_record(pk_filter* f);  // behind pk_resample's kernels while the ring is on
+inline void path_clear(pk_filter* f) {  // the history ends: the population was replaced
+  if (f) f->path.held = f->path.first = 0;
+}

@@ -362,6 +362,33 @@ int map_sum_groups(int64_t P, int Ls, int forced);  // a function of (P, Ls) alo
 inline size_t map_sum_part_doubles(int Ls, int groups) { return (size_t)groups * kMapSums * map_sum_tiles(Ls) * kMapSumLanes; }
 void launch_map_moments(hipStream_t s, const DeviceState& d, int Ls, int weighted, double gmax, int groups, double* part_dev,
                         double* wpart_dev, double* res_dev);
+// The path estimate (pk_k_path.hip): a ring of the last `cap` resampled generations.  Row r of the ring:
+// pose[r][3][P] (x, y, heading, structure of arrays like the live poses) and anc[r][P]; the held rows are first, first + 1, ...
+// modulo cap, oldest first.
+struct PathRing {
+  double* pose = nullptr;  // [cap][3][P]
+  int32_t* anc = nullptr;  // [cap][P]
+  int cap = 0;             // rows (0: recording is off)
+  int held = 0;            // rows in use
+  int first = 0;           // ring row of the oldest one
+  int64_t recorded = 0;    // rows ever recorded
+  int row(int t) const { return (int)(((int64_t)first + t) % cap); }  // ring row of held row t
+};
+constexpr int kPathLanes = 256;
+constexpr int kPathMaxBlocks = 256;  // workgroups of a summary launch: the partials of a row are this many at most
+constexpr int kPathSums = 10;        // per (row, workgroup): n, mean dx, mean dy, centred xx, xy, yy, sum c sin h, sum c cos h, lineages alive, 0
+constexpr int kPathRes = 8;          // per row: mean x, mean y, sum sin h, sum cos h, var x, cov xy, var y, survivors
+inline int path_blocks(int64_t P) { const int64_t nb = (P + kPathLanes - 1) / kPathLanes; return nb > kPathMaxBlocks ? kPathMaxBlocks : (int)nb; }
+// behind k_ancestors' gather (d.cur is the NEW generation): the old half of the pose buffers and anc_dev into ring row `row`
+void launch_path_record(hipStream_t s, const DeviceState& d, const int32_t* anc_dev, const PathRing& ring, int row);
+// out[n][held + 1][3]: the lineages of particles_dev[0 .. n) (NULL: of the particles 0 .. n - 1)
+void launch_path_trace(hipStream_t s, const DeviceState& d, const PathRing& ring, const int64_t* particles_dev, int64_t n, double* out_dev);
+// held + 3 launches: particle 0's lineage into ref_dev[held + 1][3]; one launch per row, newest first, that reduces the finished
+// row about its reference pose into part_dev[row][path_blocks(P)][kPathSums], scatters its descendant counts (cnt_dev[3][P], integer
+// atomics) into the row before it and zeroes the buffer of the row before that; one fold, a workgroup per row, into
+// res_dev[held + 1][kPathRes]
+void launch_path_summary(hipStream_t s, const DeviceState& d, const PathRing& ring, unsigned* cnt_dev, double* ref_dev, double* part_dev,
+                         double* res_dev);
 // map maintenance
 void launch_materialise(hipStream_t s, DeviceState& d);
 void launch_broadcast_slot(hipStream_t s, DeviceState& d, const unsigned char* slot_dev);
