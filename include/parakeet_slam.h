@@ -178,6 +178,9 @@ int pk_upload_pose(pk_filter* f, int64_t particle, const double xyhw[4]);
 /* The natural logarithms of the particle weights (the quantity the filter keeps: with B >~ 1000
  * blobs per scan the weights themselves underflow float64, prkt_core_v2.py:95,124). */
 int pk_download_log_weights(pk_filter* f, double* logw);
+/* ... and back, bit for bit (pk_upload_poses takes log(weight), and exp / log do not round-trip): what a snapshot of a filter whose
+ * weights carry over between resamples (pk_resample_adaptive) restores.  -inf is a weight of zero; NaN and +inf are refused. */
+int pk_upload_log_weights(pk_filter* f, const double* logw);
 
 /* Landmark state of particles [p0, p1): means (n*L*5), covs (n*L*25 dense 5x5),
  * counts (n*L) = Feature.update_count.  Any output/input pointer may be NULL. */
@@ -295,7 +298,8 @@ int pk_map_summary(pk_filter* f, int32_t weighting, double* mean, double* cov_wi
  *   pk_path_trace     the paths of the n listed current particles: out[n][held + 1][3].  Pure gathers: bit for bit what was
  *                     recorded.  n == 0 is fine.
  *   pk_path_summary   the smoothed path over the P lineages, every current particle counting once (pk_summary's convention:
- *                     behind a resample the population is the estimate).  Per row: mean[3] = mean x, mean y, circular mean
+ *                     behind a resample the population is the estimate; the weights are not read, so between two resamples of
+ *                     an adaptively resampled filter it describes the population, not the posterior).  Per row: mean[3] = mean x, mean y, circular mean
  *                     heading; spread[4] = var x, cov xy, var y, mean resultant length of the headings; survivors = the
  *                     number of distinct ancestors j_t the population still has in that row (exact).  The position moments
  *                     are taken about particle 0's lineage, so a row with ONE survivor has its recorded pose as mean, bit for
@@ -313,6 +317,46 @@ int pk_path_summary(pk_filter* f, double* mean, double* spread, int64_t* survivo
 int pk_step(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed,
             uint64_t draw, const double* blobs, int32_t num_blobs, const int32_t* ids, double u,
             int32_t weight_domain);
+
+/* ---- adaptive (selective) resampling: resample only when the weights have degenerated ("Adaptive
+ * resampling").  The reference resamples behind every scan (prkt_core_v2.py:137); so do pk_resample and pk_step.  The calls below
+ * decide on the device, so nothing crosses to the host in a step:
+ *   shift  what the weight scan subtracts: the maximum log-weight in PK_WEIGHTS_LOG, 0 in PK_WEIGHTS_LINEAR, 0 when no weight is finite;
+ *   w_p = exp(logw_p - shift),  S1 = sum w_p,  S2 = sum w_p^2,  n_eff = (S1 / S2) * S1  (that one float64 expression).
+ *   S1 is the very sum pk_resample divides by P: the totals of the 1 024-particle scan blocks added in block order.  S2: per scan
+ *   block four particles of a lane in order (fused multiply-adds), the wave by the xor butterfly, the four waves in order; then the
+ *   blocks in block order.  No floating-point atomics: the same state gives the same bits on every call.
+ *   KEEP iff n_eff >= threshold * (double)P, in float64.  NaN (every weight zero) fails the comparison: the call resamples, as
+ *   pk_resample does.  threshold: finite and >= 0 (else PK_ERR_INVALID); 0 never resamples, anything above 1 always does.
+ *   Resampled: ancestors, poses and map sources exactly pk_resample(u, weight_domain)'s from the same state; the new generation's
+ *              log-weights are 0 (pk_resample itself carries the old ones along for the next observe to reset; the adaptive caller
+ *              observes WITHOUT the reset -- pk_observe, not pk_observe_fresh).
+ *   Kept:      poses and map sources carried over bit for bit, ancestor[k] = k, logw'_k = logw_k - shift (one rounded
+ *              subtraction: a long run without a resample does not drive the linear weights of pk_download_poses to zero).
+ *   Either way the ancestors are in place for the new-landmark bookkeeping (gathered by them) and, while pk_path_enable is on, ONE
+ *   ring row is recorded per call -- a kept step records identity ancestors, so a row of the ring is then one call, not one resample.
+ *   pk_path_summary still counts every current particle once: between two resamples it describes the population, not the posterior.
+ * pk_resample_adaptive  pk_resample's arguments, refusals and ancestors_out, plus the threshold.
+ * pk_step_adaptive      pk_step with the weights carried over (no reset) and the gated resample: no host synchronisation.
+ * pk_resample_stats     what the last gated call decided: out[4] = n_eff, S1, S2, shift; resampled = 1 / 0; counts[2] = gated calls,
+ *                       resamples among them, since pk_create (kept on the device; this call reads them).  Any output may be NULL.
+ *                       PK_ERR_STATE before the first gated call.
+ * pk_weight_sums        out[2] = S1, S2 of the CURRENT weights, summed as above -- what the shards of a filter would add (as
+ *                       pk_pose_sums is to pk_summary).  gmax: the filter-wide maximum log-weight for PK_WEIGHTS_LOG, NaN = this
+ *                       handle's own; ignored for PK_WEIGHTS_LINEAR.  Changes no filter state (it scans in the resample's
+ *                       workspace: not between pk_shard_block_totals and the pk_shard_offspring that reads that scan).
+ * pk_summary_weighted   pk_summary by the weights: mean[3] = weighted mean x, mean y, circular mean heading; spread[4] = var x, cov xy,
+ *                       var y (over S1) and the mean resultant length of the headings -- pk_path_summary's figures; n_eff.  The
+ *                       position moments are taken about particle 0's pose and merged pairwise in a fixed order: particles that all
+ *                       share a pose give it back bit for bit with exactly zero variances.  Weights that sum to zero or to a
+ *                       non-finite value: PK_ERR_STATE.  Any output may be NULL.  Changes no filter state. */
+int pk_resample_adaptive(pk_filter* f, double u, int32_t weight_domain, double threshold, int64_t* ancestors_out);
+int pk_step_adaptive(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw,
+                     const double* blobs, int32_t num_blobs, const int32_t* ids, double u, int32_t weight_domain,
+                     double threshold);
+int pk_resample_stats(pk_filter* f, double out[4], int32_t* resampled, int64_t counts[2]);
+int pk_weight_sums(pk_filter* f, int32_t weight_domain, double gmax, double out[2]);
+int pk_summary_weighted(pk_filter* f, int32_t weight_domain, double mean[3], double spread[4], double* n_eff);
 
 /* ---- sharded (multi-GPU) resampling: see DESIGN.md section 6 -------------------
  * Particles are sharded contiguously over one process per GPU; global particle index =

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from . import mapsum, path
+from . import adaptive, mapsum, path
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libparakeet_slam.so")
@@ -60,6 +60,7 @@ SIGNATURES = {
     "pk_reset_weights": (C.c_int, [_h]),
     "pk_motion": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64]),
     "pk_download_log_weights": (C.c_int, [_h, _dp]),
+    "pk_upload_log_weights": (C.c_int, [_h, _dp]),
     "pk_observe": (C.c_int, [_h, _dp, C.c_int32, _ip, _ip]),
     "pk_observe_fresh": (C.c_int, [_h, _dp, C.c_int32, _ip, _ip]),
     "pk_stage_scan": (C.c_int, [_h, _dp, C.c_int32]),
@@ -78,6 +79,12 @@ SIGNATURES = {
     "pk_path_summary": (C.c_int, [_h, _dp, _dp, _lp]),
     "pk_step": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32,
                           _ip, C.c_double, C.c_int32]),
+    "pk_resample_adaptive": (C.c_int, [_h, C.c_double, C.c_int32, C.c_double, _lp]),
+    "pk_step_adaptive": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32,
+                                   _ip, C.c_double, C.c_int32, C.c_double]),
+    "pk_resample_stats": (C.c_int, [_h, _dp, C.POINTER(C.c_int32), _lp]),
+    "pk_weight_sums": (C.c_int, [_h, C.c_int32, C.c_double, _dp]),
+    "pk_summary_weighted": (C.c_int, [_h, C.c_int32, _dp, _dp, _dp]),
     "pk_shard_max_logw": (C.c_int, [_h, _dp]),
     "pk_shard_num_blocks": (C.c_int64, [_h]),
     "pk_shard_block_totals": (C.c_int, [_h, C.c_double, C.c_int32, _dp]),
@@ -292,6 +299,11 @@ class DeviceFilter(object):
         check(self._lib.pk_download_log_weights(self._h, dptr(out)))
         return out
 
+    def upload_log_weights(self, logw):
+        """Every particle's log-weight, bit for bit (upload_poses takes log(weight): exp and log do not round-trip)."""
+        a = f64(logw, (self.P,))
+        check(self._lib.pk_upload_log_weights(self._h, dptr(a)))
+
     def observe(self, blobs, ids=None, return_ids=False, fresh=False):
         """fresh: the weights restart from 1 first (prkt_core_v2.py:73), fused into the same kernels."""
         b = f64(blobs).reshape(-1, 4)
@@ -399,6 +411,47 @@ class DeviceFilter(object):
         i = np.ascontiguousarray(ids, dtype=np.int32).reshape(B) if ids is not None else None
         check(self._lib.pk_step(self._h, float(v), float(w), float(dt), dptr(zz), int(seed), int(draw), dptr(b), B,
                                 iptr(i), float(u), int(domain)))
+
+    # -- adaptive resampling (pk_resample_adaptive ...): the device decides, the host asks when it wants to know
+    def resample_adaptive(self, u, threshold, domain=PK_WEIGHTS_LINEAR, return_ancestors=False):
+        """Resamples iff n_eff < threshold * P (decided on the device); else the particles stay and the ancestors are arange(P)."""
+        out = np.empty(self.P, dtype=np.int64) if return_ancestors else None
+        check(self._lib.pk_resample_adaptive(self._h, float(u), int(domain), float(threshold), lptr(out)))
+        return out
+
+    def step_adaptive(self, v, w, dt, blobs, u, threshold, z=None, seed=0, draw=0, ids=None, domain=PK_WEIGHTS_LINEAR):
+        """motion, observe with the weights carried over, resample_adaptive: no host synchronisation."""
+        b = f64(blobs).reshape(-1, 4)
+        B = b.shape[0]
+        zz = f64(z, (self.P, 3)) if z is not None else None
+        i = np.ascontiguousarray(ids, dtype=np.int32).reshape(B) if ids is not None else None
+        check(self._lib.pk_step_adaptive(self._h, float(v), float(w), float(dt), dptr(zz), int(seed), int(draw), dptr(b), B,
+                                         iptr(i), float(u), int(domain), float(threshold)))
+
+    def resample_stats(self):
+        """What the last gated call decided and the counters so far, as ``adaptive.ResampleStats``."""
+        out, flag, counts = np.empty(4, dtype=np.float64), C.c_int32(), np.empty(2, dtype=np.int64)
+        check(self._lib.pk_resample_stats(self._h, dptr(out), C.byref(flag), lptr(counts)))
+        return adaptive.ResampleStats(out[0], out[1], out[2], out[3], flag.value != 0, counts[0], counts[1])
+
+    def weight_sums(self, domain=PK_WEIGHTS_LINEAR, gmax=None):
+        """(S1, S2) of this handle's current weights, summed as the gate sums them: what the shards of a filter would add.
+        gmax: the whole filter's maximum log-weight for PK_WEIGHTS_LOG (None: this handle's own)."""
+        out = np.empty(2, dtype=np.float64)
+        check(self._lib.pk_weight_sums(self._h, int(domain), float("nan") if gmax is None else float(gmax), dptr(out)))
+        return float(out[0]), float(out[1])
+
+    def n_eff(self, domain=PK_WEIGHTS_LINEAR):
+        """The effective sample size of the current weights: the gate's expression on weight_sums()."""
+        s1, s2 = self.weight_sums(domain)
+        with np.errstate(invalid="ignore", divide="ignore"):  # (every weight zero: NaN, as on the device)
+            return float(np.float64(s1) / np.float64(s2) * np.float64(s1))
+
+    def summary_weighted(self, domain=PK_WEIGHTS_LINEAR):
+        """The pose estimate by the weights (pk_summary_weighted) as ``adaptive.PoseSummary``."""
+        mean, spread, n_eff = np.empty(3), np.empty(4), np.empty(1)
+        check(self._lib.pk_summary_weighted(self._h, int(domain), dptr(mean), dptr(spread), dptr(n_eff)))
+        return adaptive.PoseSummary(mean, spread, n_eff[0])
 
     # -- sharded resample (see sharded.py) ---------------------------------------
     def set_shard(self, global_offset):

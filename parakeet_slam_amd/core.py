@@ -25,7 +25,7 @@ import threading
 
 import numpy as np
 
-from . import _lib, mapsum, msgs
+from . import _lib, adaptive, mapsum, msgs
 from .msgs import Blob, Odometry, Twist, heading_to_quaternion, quaternion_to_heading
 
 NO_MATCH_WEIGHT = 0.1  # prkt_core_v2.py:851-857
@@ -550,6 +550,13 @@ class FastSLAM(object):
     T steps on the device (pk_path_enable: 28 bytes per particle and step); ``path_summary()`` is the smoothed path over the
     surviving lineages with the number of distinct ancestors left per step, ``particle_paths(indices)`` the paths of single
     particles.  One GPU only: with devices=[several] it is refused.
+
+    resample_threshold=theta (default None: resample behind every scan, as the reference does): adaptive resampling -- the
+    filter resamples only when the effective sample size of its weights falls below theta * num_particles, decided on the device
+    (pk_resample_adaptive); otherwise the particles stay and their weights carry over into the next scan.  ``summary()`` is
+    then the WEIGHTED pose, ``pose_summary()`` its full form, ``map_summary()`` weights by default, ``resample_stats()`` says
+    what the last step decided, and ``last_ancestors`` is the identity on a kept step.  The resample draw is taken at every
+    step, kept or not, so the random stream does not depend on the decisions.  One GPU only, as record_path.
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -578,6 +585,9 @@ class FastSLAM(object):
             if a["record_path"]:
                 raise ValueError("FastSLAM(devices=[...], record_path=...): the path is recorded on one GPU only -- lineages "
                                  "across ranks are out of scope (the sharded resample is refused on a recording filter)")
+            if a["resample_threshold"] is not None:
+                raise ValueError("FastSLAM(devices=[...], resample_threshold=...): adaptive resampling is for one GPU -- the "
+                                 "verdict of a sharded filter needs its weight sums all-reduced, which is out of scope")
             return ShardedFastSLAM(a["preset_features"], num_particles=a["num_particles"], devices=list(devices),
                                    weight_domain=a["weight_domain"], rng=a["rng"], seed=a["seed"],
                                    publish_debug=a["publish_debug"], new_landmarks=a["new_landmarks"],
@@ -589,9 +599,10 @@ class FastSLAM(object):
 
     def __init__(self, preset_features=[], num_particles=50, device=0, weight_domain="linear", rng="global",
                  seed=0, publish_debug=None, new_landmarks=False, spare_landmarks=0, pair_threshold=30.0, devices=None,
-                 bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0):
+                 bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None):
         if devices is not None and len(list(devices)) == 1:
             device = list(devices)[0]
+        self._threshold = None if resample_threshold is None else adaptive.threshold_value(resample_threshold)
         self._lock = threading.RLock()
         self.last_control = Twist()
         self.last_update = msgs.now()
@@ -793,15 +804,17 @@ class FastSLAM(object):
             self._filter.set_measurement_noise(self.Qt)
             # :73 weight = 1 (the reset is fused into the observe kernels: pk_observe_fresh; the motion
             # update in between does not read the weights), :84-124 association + EKF + weights
+            # (adaptive resampling: no reset -- the weights carry over from a kept step, and a resample leaves them at 1)
+            fresh = self._threshold is None
             if self._grow and len(blobs) and not self._nl_device:
-                self.last_ids = self._filter.observe(blobs, fresh=True, return_ids=True)
+                self.last_ids = self._filter.observe(blobs, fresh=fresh, return_ids=True)
                 self._touch()
                 self._new_landmarks(blobs, self.last_ids)  # :92-95 for every particle's unmatched blobs
             elif self._nl_device and len(blobs):
                 # :92-95 on the device, behind the association and the updates (k_new_landmarks)
-                self.last_ids = self._filter.observe(blobs, fresh=True, return_ids=self.record_ids)
+                self.last_ids = self._filter.observe(blobs, fresh=fresh, return_ids=self.record_ids)
             else:
-                self._filter.observe(blobs, fresh=True)
+                self._filter.observe(blobs, fresh=fresh)
             self._touch()
             if self._publish:
                 self._publish_all(self.particle_track_pub, self._poses())  # :126-127
@@ -910,8 +923,11 @@ class FastSLAM(object):
                 self._publish_all(self.aged_particles_pub, self._poses())  # :237
             u = _pyrandom.random()  # :226
             host_nl = self._grow and not self._nl_device
-            self.last_ancestors = self._filter.resample(u, domain=self._domain,
-                                                        return_ancestors=self._publish or host_nl or (self._grow and self.record_ids))
+            want = self._publish or host_nl or (self._grow and self.record_ids)
+            if self._threshold is None:
+                self.last_ancestors = self._filter.resample(u, domain=self._domain, return_ancestors=want)
+            else:  # decided on the device; a kept step's ancestors are the identity, so the gather below holds either way
+                self.last_ancestors = self._filter.resample_adaptive(u, self._threshold, domain=self._domain, return_ancestors=want)
             if host_nl:  # (device mode: pk_resample gathers the bookkeeping with the particles)
                 anc = [int(a) for a in self.last_ancestors]
                 h = self._nl_host
@@ -923,14 +939,36 @@ class FastSLAM(object):
 
     # ------------------------------------------------------------------ a14
     def summary(self):
+        """(x, y, heading): the particles' mean pose (:254-276) -- by their weights on a filter that resamples adaptively."""
         with self._lock:
+            if self._threshold is not None:
+                return self._filter.summary_weighted(self._domain).pose()
             return self._filter.summary()
 
-    def map_summary(self, weighting="uniform"):
+    def pose_summary(self):
+        """The pose estimate by the particles' weights (``adaptive.PoseSummary``: mean, spread, n_eff) of a filter that resamples
+        adaptively.  (One that resamples behind every scan keeps the weights its particles were chosen by until the next scan
+        resets them: weighting the chosen particles by them again would count them twice -- summary() is its estimate.)"""
+        if self._threshold is None:
+            raise ValueError("pose_summary: this filter resamples at every step (FastSLAM(..., resample_threshold=theta)); its estimate is summary()")
+        with self._lock:
+            return self._filter.summary_weighted(self._domain)
+
+    def resample_stats(self):
+        """What the last step's gate decided and how many steps resampled so far (``adaptive.ResampleStats``)."""
+        if self._threshold is None:
+            raise ValueError("resample_stats: this filter resamples at every step (FastSLAM(..., resample_threshold=theta))")
+        with self._lock:
+            return self._filter.resample_stats()
+
+    def map_summary(self, weighting=None):
         """The map estimate, reduced over the particles on the device (``mapsum.MapSummary``; the sibling of summary(),
         prkt_core_v2.py:254-276, which stops at the pose).  weighting "uniform": every particle counts once, as in summary() --
         behind a resample the population is the estimate; "weights": by the particles' weights, for use between an observe
-        and a resample.  A growing filter's spare landmarks are NaN rows (``as_features()`` leaves them out)."""
+        and a resample -- the default on a filter that resamples adaptively, whose weights carry over.  A growing filter's
+        spare landmarks are NaN rows (``as_features()`` leaves them out)."""
+        if weighting is None:
+            weighting = "uniform" if self._threshold is None else "weights"
         code = mapsum.weighting_code(weighting)
         with self._lock:
             return self._filter.map_summary(code)
@@ -966,6 +1004,8 @@ class FastSLAM(object):
                 extra = _nl_snapshot_arrays(*self._filter.grow_download(), L0=self._L0)
             elif self._grow:
                 extra = _nl_snapshot(self._nl())
+            if self._threshold is not None:  # the weights carry over: bit for bit, not through exp and log
+                extra["log_weights"] = self._filter.download_log_weights()
             if self._record_path:
                 extra["path_poses"], extra["path_ancestors"] = self._filter.path_download()
                 extra["path_recorded"] = np.int64(self._filter.path_shape()[2])
@@ -994,10 +1034,15 @@ class FastSLAM(object):
                 if d["path_ancestors"].shape != (n, P) or d["path_poses"].shape != (n, P, 3) or n > self._record_path:
                     raise ValueError("snapshot: a path of %s x %s does not fit this filter's ring of %d steps x %d particles"
                                      % (d["path_ancestors"].shape[0], d["path_ancestors"].shape[1:], self._record_path, P))
+            have_logw = self._threshold is not None and "log_weights" in d.files
+            if have_logw and (d["log_weights"].shape != (P,) or not np.all(d["log_weights"] < np.inf)):
+                raise ValueError("snapshot: log_weights must be %d numbers below +inf" % P)
             if have_nl:  # everything is checked before anything is assigned
                 _nl_check_snapshot(d, P, self._L0, L, self._spare, self._filter.grow_shape()[2] if self._nl_device else None)
 
             self._filter.upload_poses(d["poses"])
+            if have_logw:  # (a snapshot without them: log(weight), as upload_poses took it)
+                self._filter.upload_log_weights(d["log_weights"])
             if L:
                 self._filter.upload_landmarks(0, P, d["means"], d["covs"].reshape(P, L, 25), d["counts"])
             self.Qt = d["Qt"].copy()

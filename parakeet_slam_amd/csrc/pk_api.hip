@@ -5,8 +5,8 @@
 // (summary's division and atan2, prkt_core_v2.py:273-275) and the per-blob unit ray
 // direction cos/sin (prkt_core_v2.py:510), which are O(B), not O(P*L).
 // This file: the filter's lifecycle and transfers, motion, resample, the step, the new-landmark bookkeeping, options, timing and
-// the probe.  The observe pipeline is pk_api_observe.hip, the multi-GPU protocol pk_api_shard.hip, the path estimate pk_api_path.hip;
-// pk_filter.hpp is what they share.
+// the probe.  The observe pipeline is pk_api_observe.hip, the multi-GPU protocol pk_api_shard.hip, the path estimate pk_api_path.hip,
+// adaptive resampling pk_api_adaptive.hip; pk_filter.hpp is what they share.
 #include "pk_filter.hpp"
 
 extern "C" {
@@ -481,6 +481,20 @@ int pk_download_log_weights(pk_filter* f, double* logw) {
   return PK_OK;
 }
 
+/* The log-weights of every particle, bit for bit (pk_upload_poses takes log(w): exp and log do not round-trip): what a snapshot
+ * of a filter whose weights carry over between resamples restores.  -inf is a weight of zero; NaN and +inf are refused. */
+int pk_upload_log_weights(pk_filter* f, const double* logw) {
+  if (!f || !logw) return fail(PK_ERR_INVALID, "pk_upload_log_weights: NULL argument");
+  for (int64_t i = 0; i < f->d.P; ++i)
+    if (!(logw[i] < INFINITY)) return fail(PK_ERR_INVALID, "pk_upload_log_weights: the log-weight of particle %lld is +inf or NaN", (long long)i);
+  int rc;
+  if ((rc = use_device(f))) return rc;
+  PK_HIP(hipMemcpyAsync(f->d.logw[f->d.cur], logw, (size_t)f->d.P * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  PK_HIP(hipStreamSynchronize(f->stream));
+  f->gmax_fused = false;
+  return PK_OK;
+}
+
 int pk_download_landmarks(pk_filter* f, int64_t p0, int64_t p1, double* means, double* covs, int32_t* counts) {
   if (!f) return fail(PK_ERR_INVALID, "pk_download_landmarks: NULL handle");
   if (p0 < 0 || p1 < p0 || p1 > f->d.P) return fail(PK_ERR_INVALID, "pk_download_landmarks: bad particle range");
@@ -835,6 +849,17 @@ int pk_map_summary(pk_filter* f, int32_t weighting, double* mean, double* cov_wi
 
 int pk_step(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw,
             const double* blobs, int32_t B, const int32_t* ids, double u, int32_t weight_domain) {
+  return step_impl(f, v, w, dt, z, seed, draw, blobs, B, ids, u, weight_domain, nullptr);
+}
+
+}  // extern "C"
+
+int step_impl(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
+              int32_t B, const int32_t* ids, double u, int32_t weight_domain, const double* gate) {
+  const bool reset = gate == nullptr;
+  auto resample = [&]() {
+    return gate ? pk_resample_adaptive(f, u, weight_domain, *gate, nullptr) : pk_resample(f, u, weight_domain, nullptr);  // :137
+  };
   int rc;
   // Throughput mode with ML association: the host half of the scan upload first, then ONE launch
   // for the motion update and the upload of the scan block, then the observe kernels.
@@ -857,16 +882,18 @@ int pk_step(pk_filter* f, double v, double w, double dt, const double* z, uint64
         f->gmax_fused = false;
         if ((rc = note_upload(f, sg.slot))) return rc;
         const double* staged_blobs = reinterpret_cast<const double*>(sg.st + kCtlBytes);
-        if ((rc = observe_impl(f, staged_blobs, B, nullptr, nullptr, true))) return rc;  // :73 (reset fused) + :82-124
-        return pk_resample(f, u, weight_domain, nullptr);                                // :137
+        if ((rc = observe_impl(f, staged_blobs, B, nullptr, nullptr, reset))) return rc;  // :73 (reset fused) + :82-124
+        return resample();
       }
       (void)hipGetLastError();
     }
   }
   if ((rc = pk_motion(f, v, w, dt, z, seed, draw))) return rc;              // :75-77
-  if ((rc = observe_impl(f, blobs, B, ids, nullptr, true))) return rc;    // :73 (reset fused) + :82-124
-  return pk_resample(f, u, weight_domain, nullptr);                         // :137
+  if ((rc = observe_impl(f, blobs, B, ids, nullptr, reset))) return rc;   // :73 (reset fused) + :82-124
+  return resample();
 }
+
+extern "C" {
 
 // ---- section 8(f4) on the device: the new-landmark bookkeeping (pk_k_grow.hip) -------
 int pk_grow_enable(pk_filter* f, int32_t preset_landmarks, int32_t reading_capacity, double pair_threshold) {

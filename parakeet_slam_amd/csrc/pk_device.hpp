@@ -95,6 +95,73 @@ __host__ __device__ inline double key_to_double(unsigned long long k) {
   return x;
 }
 
+// ------------------------------------------------------------------ systematic resampling
+// Ancestor of output slot `slot`: first particle j whose inclusive cumulative weight C_j is
+// >= u*r + slot*r, r = sum/P  (equivalent to the walk at prkt_core_v2.py:233-250, '<=' at :239).
+// C_j = offsets[block of j] + clocal[j]; every operation is a named rounding, so each kernel that
+// calls this (k_ancestors, k_ancestors_gated) picks the same ancestor from the same scan.
+__device__ __forceinline__ int64_t comb_ancestor(const double* __restrict__ clocal, const double* __restrict__ totals,
+                                                 const double* offsets, double sum, int64_t nb, int64_t Pg, int64_t Pscan,
+                                                 double u, int64_t slot) {
+  const double r = __ddiv_rn(sum, (double)Pg);                                  // range_ :225
+  const double t = __dadd_rn(__dmul_rn(u, r), __dmul_rn((double)slot, r));  // step :226 + k*range_
+  // block: first b with offsets[b] + totals[b] >= t
+  int64_t lo = 0, hi = nb - 1;
+  while (lo < hi) {
+    int64_t mid = (lo + hi) >> 1;
+    if (__dadd_rn(offsets[mid], totals[mid]) >= t)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  const int64_t b = lo;
+  const double off = offsets[b];
+  int64_t j0 = b * kScanBlock, j1 = j0 + kScanBlock - 1;
+  if (j1 > Pscan - 1) j1 = Pscan - 1;
+  while (j0 < j1) {
+    int64_t mid = (j0 + j1) >> 1;
+    if (__dadd_rn(off, clocal[mid]) >= t)
+      j1 = mid;
+    else
+      j0 = mid + 1;
+  }
+  return j0;
+}
+
+// ------------------------------------------------------------------ weighted moments
+// Weighted position moments about a reference pose, kept as (n, mean, centred second moments) and merged pairwise (Chan et
+// al.): every term of a merge is a square or a product of the same sign as the result, so nothing cancels however far the
+// reference lies from the mean -- the shifted raw moments sum c d d - (sum c d)^2 / n lose a factor n once the reference
+// sits where few others do.  Elements that all sit ON the reference merge zeros: the sums stay exactly zero.
+struct PathMoments {
+  double n, mx, my, xx, xy, yy;
+};
+__device__ __forceinline__ PathMoments path_merge(const PathMoments& a, const PathMoments& b) {
+  const double n = a.n + b.n;
+  if (!(b.n > 0.0)) return a;
+  if (!(a.n > 0.0)) return b;
+  const double f = b.n / n, g = a.n * f;
+  const double dx = b.mx - a.mx, dy = b.my - a.my;
+  PathMoments m;
+  m.n = n;
+  m.mx = a.mx + dx * f;
+  m.my = a.my + dy * f;
+  m.xx = a.xx + b.xx + dx * dx * g;
+  m.xy = a.xy + b.xy + dx * dy * g;
+  m.yy = a.yy + b.yy + dy * dy * g;
+  return m;
+}
+__device__ __forceinline__ PathMoments path_shfl_down(const PathMoments& m, int off) {
+  PathMoments o;
+  o.n = __shfl_down(m.n, off, kWave);
+  o.mx = __shfl_down(m.mx, off, kWave);
+  o.my = __shfl_down(m.my, off, kWave);
+  o.xx = __shfl_down(m.xx, off, kWave);
+  o.xy = __shfl_down(m.xy, off, kWave);
+  o.yy = __shfl_down(m.yy, off, kWave);
+  return o;
+}
+
 // ------------------------------------------------------------------ landmark slot access
 __device__ __forceinline__ Landmark<double> load_landmark(const double* f, const int* cnt, int Lp, int l) {
   Landmark<double> m;

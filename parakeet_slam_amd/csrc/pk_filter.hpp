@@ -4,6 +4,7 @@
 //   pk_api_observe.hip  the observe pipeline: staging, routing, association, the one-pass stages, the colour table's host side
 //   pk_api_shard.hip    the multi-GPU protocol: host-side, device-resident and balanced
 //   pk_api_path.hip     the path estimate: the ring of resampled generations, its transfers, trace and summary
+//   pk_api_adaptive.hip adaptive resampling: the gated resample and step, the weight sums, the weighted pose summary
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -332,6 +333,12 @@ struct pk_filter {
   double* ps_part = nullptr;     // [ps_rows][path_blocks(P)][kPathSums]
   double* ps_res = nullptr;      // [ps_rows][kPathSums]
   int64_t ps_rows = 0;
+  // adaptive resampling and the weighted pose summary (pk_api_adaptive.hip): nothing until one of its entry points is first called
+  double* ad_s2 = nullptr;          // [nblocks] sum w^2 of every scan block
+  double* ad_words = nullptr;       // [kAdWords] the scan's shift | the plan beyond kAncestorsScanMaxBlocks blocks | a maximum log-weight | the pose summary
+  double* ad_part = nullptr;        // [path_blocks(P)][kPathSums] k_pose_moments' partials
+  GateOutcome* ad_out = nullptr;    // what the last gated call decided, and the counters since pk_create
+  int64_t ad_calls = 0;             // gated calls enqueued (pk_resample_stats: 0 -> nothing to report)
   GrowState grow{};                 // section 8(f4) on the device (pk_grow_enable): per-particle new-landmark bookkeeping
   bool grow_on = false;
   int32_t* anc = nullptr;           // P
@@ -442,6 +449,10 @@ inline unsigned* ctl_pub_stats(pk_filter* f) { return reinterpret_cast<unsigned*
 // ---- helpers that more than one file calls
 // pk_api.hip
 int materialise(pk_filter* f);
+// the body of pk_step and pk_step_adaptive.  gate == NULL: the weights restart from 1 and pk_resample ends the step; else they
+// carry over and pk_resample_adaptive ends it with the threshold *gate
+int step_impl(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
+              int32_t B, const int32_t* ids, double u, int32_t weight_domain, const double* gate);
 // pk_api_observe.hip
 int note_upload(pk_filter* f, int slot);
 int colour_rows_for_download(pk_filter* f, int64_t p0, int64_t p1);

@@ -56,39 +56,9 @@ void launch_path_trace(hipStream_t s, const DeviceState& d, const PathRing& ring
                      ring.pose, ring.anc, d.P, ring.cap, ring.first, ring.held, particles_dev, n, out_dev);
 }
 
-// Weighted position moments about a row's reference pose, kept as (n, mean, centred second moments) and merged pairwise (Chan et
-// al.): every term of a merge is a square or a product of the same sign as the result, so nothing cancels however far the
-// reference lies from the mean -- the shifted raw moments sum c d d - (sum c d)^2 / n lose a factor n once particle 0 descends
-// from a lineage few others share.  Lineages that all sit ON the reference merge zeros: the sums stay exactly zero.
-struct PathMoments {
-  double n, mx, my, xx, xy, yy;
-};
-__device__ __forceinline__ PathMoments path_merge(const PathMoments& a, const PathMoments& b) {
-  const double n = a.n + b.n;
-  if (!(b.n > 0.0)) return a;
-  if (!(a.n > 0.0)) return b;
-  const double f = b.n / n, g = a.n * f;
-  const double dx = b.mx - a.mx, dy = b.my - a.my;
-  PathMoments m;
-  m.n = n;
-  m.mx = a.mx + dx * f;
-  m.my = a.my + dy * f;
-  m.xx = a.xx + b.xx + dx * dx * g;
-  m.xy = a.xy + b.xy + dx * dy * g;
-  m.yy = a.yy + b.yy + dy * dy * g;
-  return m;
-}
-__device__ __forceinline__ PathMoments path_shfl_down(const PathMoments& m, int off) {
-  PathMoments o;
-  o.n = __shfl_down(m.n, off, kWave);
-  o.mx = __shfl_down(m.mx, off, kWave);
-  o.my = __shfl_down(m.my, off, kWave);
-  o.xx = __shfl_down(m.xx, off, kWave);
-  o.xy = __shfl_down(m.xy, off, kWave);
-  o.yy = __shfl_down(m.yy, off, kWave);
-  return o;
-}
-
+// The position moments of a row about its reference pose are PathMoments triples merged with path_merge (pk_device.hpp): the
+// reference is particle 0's lineage, which few others may share.
+//
 // part[block][kPathSums]: n, mean dx, mean dy, xx, xy, yy (centred, weighted), sum c sin h, sum c cos h, lineages alive, 0
 //
 // The launch of row t (t = held: the current generation, every count 1 -- cnt == NULL):

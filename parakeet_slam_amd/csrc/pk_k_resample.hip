@@ -161,28 +161,7 @@ __global__ void __launch_bounds__(256) k_ancestors(const double* __restrict__ cl
   }
   int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  const double r = __ddiv_rn(sum[0], (double)Pg);                  // range_ :225
-  const double t = __dadd_rn(__dmul_rn(u, r), __dmul_rn((double)(slot0 + k), r));  // step :226 + k*range_
-  // block: first b with offsets[b] + totals[b] >= t
-  int64_t lo = 0, hi = nb - 1;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (__dadd_rn(offsets[mid], totals[mid]) >= t)
-      hi = mid;
-    else
-      lo = mid + 1;
-  }
-  const int64_t b = lo;
-  const double off = offsets[b];
-  int64_t j0 = b * kScanBlock, j1 = j0 + kScanBlock - 1;
-  if (j1 > Pscan - 1) j1 = Pscan - 1;
-  while (j0 < j1) {
-    int64_t mid = (j0 + j1) >> 1;
-    if (__dadd_rn(off, clocal[mid]) >= t)
-      j1 = mid;
-    else
-      j0 = mid + 1;
-  }
+  const int64_t j0 = comb_ancestor(clocal, totals, offsets, sum[0], nb, Pg, Pscan, u, slot0 + k);
   anc[k] = (int32_t)j0;
   if (gx) {  // fused k_gather_poses (single-GPU resample)
     const int32_t a = (int32_t)j0;

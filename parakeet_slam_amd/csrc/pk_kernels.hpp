@@ -389,6 +389,33 @@ void launch_path_trace(hipStream_t s, const DeviceState& d, const PathRing& ring
 // res_dev[held + 1][kPathRes]
 void launch_path_summary(hipStream_t s, const DeviceState& d, const PathRing& ring, unsigned* cnt_dev, double* ref_dev, double* part_dev,
                          double* res_dev);
+// Adaptive resampling (pk_k_adaptive.hip; DESIGN.md section 4, "Adaptive resampling"): the effective sample size of the weights
+// k_scan_local has just scanned, and the resample that declines when it is large enough -- decided on the device.
+// What a gated call leaves for the host to read when it asks (pk_resample_stats); one thread writes it.
+struct GateOutcome {
+  double n_eff, s1, s2, shift;          // of the call: S1 / S2 * S1, sum w, sum w^2, what k_scan_local subtracted
+  unsigned long long resampled;         // 1: it resampled, 0: it kept
+  unsigned long long calls, resamples;  // since pk_create
+};
+constexpr int kGatePlan = 4;  // S1, S2, n_eff, keep (1.0 / 0.0)
+// sum w^2 per scan block (w as k_scan_local takes it: the same shift), s2tot_dev[nb]; block 0 leaves the shift in shift_dev[0]
+void launch_weight_sq(hipStream_t s, const DeviceState& d, const double* gmax_dev, int domain, const unsigned long long* gmax_key_dev,
+                      double* s2tot_dev, double* shift_dev);
+// one workgroup: the exclusive scan of the block totals (offsets_dev[nb], or NULL: not wanted) with k_scan_blocks' additions, then
+// plan_dev[kGatePlan] -- S1 (the sum k_scan_blocks leaves), S2 over the blocks in order, n_eff, keep = n_eff >= threshold * P
+void launch_gate_plan(hipStream_t s, const double* totals_dev, const double* s2tot_dev, int64_t nb, double* offsets_dev,
+                      double* plan_dev, double threshold, int64_t P);
+// launch_ancestors with the gather, behind the gate.  offsets_dev == plan_dev == NULL (nb <= kAncestorsScanMaxBlocks): every
+// workgroup derives offsets, S1, S2 and the verdict from the block totals itself.  Resampled: pk_resample's ancestors and gather,
+// log-weights 0; kept: anc[k] = k, the poses and sources copied, logw - shift.  The pose buffers flip either way.
+void launch_ancestors_gated(hipStream_t s, const double* clocal_dev, const double* totals_dev, const double* s2tot_dev,
+                            const double* offsets_dev, const double* plan_dev, int64_t nb, double u, double threshold,
+                            const double* shift_dev, int32_t* anc_dev, DeviceState& d, GateOutcome* outcome_dev);
+// The weighted pose summary: w = exp(logw - shift) (shift = gmax_dev[0] in the log domain, 0 where that is not finite or in the
+// linear one), moments of (x, y) - particle 0's as k_path_row takes them, sum w sin h, sum w cos h, sum w^2.
+// part_dev[path_blocks(P)][kPathSums]; res_dev[kPoseRes] = mean x, mean y, sum w sin h, sum w cos h, var x, cov xy, var y, S1, S2
+constexpr int kPoseRes = 9;
+void launch_pose_moments(hipStream_t s, const DeviceState& d, const double* gmax_dev, int domain, double* part_dev, double* res_dev);
 // map maintenance
 void launch_materialise(hipStream_t s, DeviceState& d);
 void launch_broadcast_slot(hipStream_t s, DeviceState& d, const unsigned char* slot_dev);

@@ -195,18 +195,22 @@ class ShardedFastSLAM(object):
     every rank's device (pk_grow_enable); a particle that migrates in the resample takes its orphaned readings, id counter and
     spare-slot ids along behind its map, so the filter grows the same maps whatever the number of GPUs.
 
-    record_path (the path estimate of ``FastSLAM``) is refused: lineages across ranks are not recorded.
+    record_path (the path estimate of ``FastSLAM``) is refused: lineages across ranks are not recorded.  So is
+    resample_threshold (adaptive resampling): the ranks would have to all-reduce their weight sums for one verdict.
 
     (``FastSLAM(..., devices=[...])`` arrives here with FastSLAM's OWN defaults -- weight_domain "linear", rng "global".)"""
 
     def __init__(self, preset_features=[], num_particles=50, devices=(0, 1), weight_domain="log", rng="device", seed=0,
                  backend="nccl", publish_debug=None, _shard_factory=None, new_landmarks=False, spare_landmarks=0,
-                 pair_threshold=30.0, reading_capacity=64, record_path=0):
+                 pair_threshold=30.0, reading_capacity=64, record_path=0, resample_threshold=None):
         from . import _lib  # constants only; loads nothing
 
         if record_path:  # (before any process starts)
             raise ValueError("ShardedFastSLAM: record_path is for one GPU -- the lineages of particles that migrate between ranks "
                              "are not recorded (the sharded resample is refused on a recording filter)")
+        if resample_threshold is not None:
+            raise ValueError("ShardedFastSLAM: resample_threshold is for one GPU -- the verdict of a sharded filter needs its "
+                             "weight sums (pk_weight_sums) all-reduced between the ranks, which is not built")
         self._lock = threading.RLock()
         self.last_control = Twist()
         self.last_update = msgs.now()
