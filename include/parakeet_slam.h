@@ -299,18 +299,35 @@ int pk_map_summary(pk_filter* f, int32_t weighting, double* mean, double* cov_wi
  *                     recorded.  n == 0 is fine.
  *   pk_path_summary   the smoothed path over the P lineages, every current particle counting once (pk_summary's convention:
  *                     behind a resample the population is the estimate; the weights are not read, so between two resamples of
- *                     an adaptively resampled filter it describes the population, not the posterior).  Per row: mean[3] = mean x, mean y, circular mean
+ *                     an adaptively resampled filter it describes the population, not the posterior: pk_path_summary_weighted does).  Per row: mean[3] = mean x, mean y, circular mean
  *                     heading; spread[4] = var x, cov xy, var y, mean resultant length of the headings; survivors = the
  *                     number of distinct ancestors j_t the population still has in that row (exact).  The position moments
  *                     are taken about particle 0's lineage, so a row with ONE survivor has its recorded pose as mean, bit for
  *                     bit, and exactly zero spread.  Integer atomics and fixed-order sums only: the same bits on every call.
- *                     Any output may be NULL. */
+ *                     Any output may be NULL.
+ *   pk_path_summary_weighted  the same path by the WEIGHTS of the current particles, w_k = exp(logw_k - shift) as
+ *                     pk_summary_weighted takes them (weight_domain, shift: see adaptive resampling below): the estimate
+ *                     between an observe and a resample.  mean[held + 1][3] and spread[held + 1][4] carry pk_path_summary's
+ *                     figures and row convention; the variances are over S1 = sum w, the mean resultant length is hypot / S1;
+ *                     n_eff = (S1 / S2) * S1 is ONE number, that of the current weights.  Row `held` is pk_summary_weighted's
+ *                     estimate.  A particle of weight 0 contributes nothing.  Five launches whatever the ring holds (ONE
+ *                     walks all rows): every thread walks its own particles' lineages back, so nothing is scattered -- no atomics at all, every sum in a
+ *                     fixed order, the same bits on every call; a row all of whose lineages share one ancestor has its recorded
+ *                     pose as mean, bit for bit, and exactly zero variances.  PK_ERR_INVALID for a bad domain; weights that sum to
+ *                     zero or to a non-finite value: PK_ERR_STATE.  Any output may be NULL.  Changes no filter state; its
+ *                     scratch (12 bytes per particle, the rows' partial sums) is allocated by the first call and released with
+ *                     the ring.
+ * pk_best_particle (needs no ring) hands out the index of the particle with the largest log-weight and that log-weight: the
+ * lowest index among equals, a log-weight that is not a number never; PK_ERR_STATE when every one is.  All at -inf: index 0.
+ * Deterministic, no atomics; either output may be NULL.  pk_path_trace of that index is the most likely particle's path. */
 int pk_path_enable(pk_filter* f, int32_t capacity);
 int pk_path_shape(const pk_filter* f, int32_t* capacity, int32_t* held, int64_t* recorded);
 int pk_path_download(pk_filter* f, int32_t t0, int32_t t1, double* poses, int32_t* ancestors);
 int pk_path_upload(pk_filter* f, int32_t n, int64_t recorded, const double* poses, const int32_t* ancestors);
 int pk_path_trace(pk_filter* f, const int64_t* particles, int64_t n, double* out);
 int pk_path_summary(pk_filter* f, double* mean, double* spread, int64_t* survivors);
+int pk_path_summary_weighted(pk_filter* f, int32_t weight_domain, double* mean, double* spread, double* n_eff);
+int pk_best_particle(pk_filter* f, int64_t* index, double* log_weight);
 
 /* One whole cam_cb without host synchronisation: reset weights, motion, observe,
  * resample.  Arguments as in the calls above. */
@@ -335,7 +352,8 @@ int pk_step(pk_filter* f, double v, double w, double dt, const double* z, uint64
  *              subtraction: a long run without a resample does not drive the linear weights of pk_download_poses to zero).
  *   Either way the ancestors are in place for the new-landmark bookkeeping (gathered by them) and, while pk_path_enable is on, ONE
  *   ring row is recorded per call -- a kept step records identity ancestors, so a row of the ring is then one call, not one resample.
- *   pk_path_summary still counts every current particle once: between two resamples it describes the population, not the posterior.
+ *   pk_path_summary still counts every current particle once: between two resamples it describes the population, not the posterior
+ *   -- pk_path_summary_weighted is the path estimate by the weights.
  * pk_resample_adaptive  pk_resample's arguments, refusals and ancestors_out, plus the threshold.
  * pk_step_adaptive      pk_step with the weights carried over (no reset) and the gated resample: no host synchronisation.
  * pk_resample_stats     what the last gated call decided: out[4] = n_eff, S1, S2, shift; resampled = 1 / 0; counts[2] = gated calls,

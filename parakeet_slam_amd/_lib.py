@@ -77,6 +77,8 @@ SIGNATURES = {
     "pk_path_upload": (C.c_int, [_h, C.c_int32, C.c_int64, _dp, _ip]),
     "pk_path_trace": (C.c_int, [_h, _lp, C.c_int64, _dp]),
     "pk_path_summary": (C.c_int, [_h, _dp, _dp, _lp]),
+    "pk_path_summary_weighted": (C.c_int, [_h, C.c_int32, _dp, _dp, _dp]),
+    "pk_best_particle": (C.c_int, [_h, _lp, _dp]),
     "pk_step": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32,
                           _ip, C.c_double, C.c_int32]),
     "pk_resample_adaptive": (C.c_int, [_h, C.c_double, C.c_int32, C.c_double, _lp]),
@@ -403,6 +405,20 @@ class DeviceFilter(object):
         mean, spread, surv = np.empty((held + 1, 3)), np.empty((held + 1, 4)), np.empty(held + 1, dtype=np.int64)
         check(self._lib.pk_path_summary(self._h, dptr(mean), dptr(spread), lptr(surv)))
         return path.PathSummary(mean, spread, surv, recorded - held)
+
+    def path_summary_weighted(self, domain=PK_WEIGHTS_LINEAR):
+        """The smoothed path by the weights of the current particles (pk_path_summary_weighted) as ``path.WeightedPathSummary``:
+        path_summary's mean and spread per row, and the n_eff of the current weights."""
+        _, held, recorded = self.path_shape()
+        mean, spread, n_eff = np.empty((held + 1, 3)), np.empty((held + 1, 4)), np.empty(1)
+        check(self._lib.pk_path_summary_weighted(self._h, int(domain), dptr(mean), dptr(spread), dptr(n_eff)))
+        return path.WeightedPathSummary(mean, spread, n_eff[0], recorded - held)
+
+    def best_particle(self):
+        """(index, log-weight) of the particle with the largest log-weight: the lowest index among equals, NaN never."""
+        i, v = C.c_int64(), C.c_double()
+        check(self._lib.pk_best_particle(self._h, C.byref(i), C.byref(v)))
+        return int(i.value), float(v.value)
 
     def step(self, v, w, dt, blobs, u, z=None, seed=0, draw=0, ids=None, domain=PK_WEIGHTS_LINEAR):
         b = f64(blobs).reshape(-1, 4)

@@ -549,7 +549,8 @@ class FastSLAM(object):
     record_path=T (default 0: off): every resample records the generation it worked on and its ancestors in a ring of the last
     T steps on the device (pk_path_enable: 28 bytes per particle and step); ``path_summary()`` is the smoothed path over the
     surviving lineages with the number of distinct ancestors left per step, ``particle_paths(indices)`` the paths of single
-    particles.  One GPU only: with devices=[several] it is refused.
+    particles, ``path_summary(weighting="weights")`` the path by the particles' weights (between the resamples of an adaptively
+    resampled filter) and ``best_path()`` that of the most likely particle.  One GPU only: with devices=[several] it is refused.
 
     resample_threshold=theta (default None: resample behind every scan, as the reference does): adaptive resampling -- the
     filter resamples only when the effective sample size of its weights falls below theta * num_particles, decided on the device
@@ -977,13 +978,31 @@ class FastSLAM(object):
         if not self._record_path:
             raise ValueError("%s: this filter does not record its path (FastSLAM(..., record_path=T))" % who)
 
-    def path_summary(self):
+    def path_summary(self, weighting="uniform"):
         """The path estimate (``path.PathSummary``): per step of the ring, oldest first, and for the current generation last, the
         mean pose over the lineages of the current particles, their spread, and how many distinct ancestors they still have
-        there -- the trajectory the filter NOW believes in, not the string of per-step summary() values."""
+        there -- the trajectory the filter NOW believes in, not the string of per-step summary() values.  weighting "uniform"
+        (the default, on every filter): every current particle counts once; "weights": by the particles' weights in the filter's
+        weight domain (``path.WeightedPathSummary``: mean, spread and n_eff), the estimate between an observe and a resample of a
+        filter that resamples adaptively."""
         self._need_path("path_summary")
+        if weighting not in ("uniform", "weights"):
+            raise ValueError('path_summary: weighting must be "uniform" or "weights", not %r' % (weighting,))
         with self._lock:
+            if weighting == "weights":
+                return self._filter.path_summary_weighted(self._domain)
             return self._filter.path_summary()
+
+    def best_particle(self):
+        """The index of the particle with the largest weight (the lowest one among equals)."""
+        with self._lock:
+            return self._filter.best_particle()[0]
+
+    def best_path(self):
+        """The path of the most likely particle, array (held + 1, 3) of (x, y, heading): ``particle_paths([best_particle()])[0]``."""
+        self._need_path("best_path")
+        with self._lock:
+            return self._filter.path_trace([self._filter.best_particle()[0]])[0]
 
     def particle_paths(self, indices):
         """The paths of the listed current particles, array (len, held + 1, 3) of (x, y, heading); the last row is particles[i]."""

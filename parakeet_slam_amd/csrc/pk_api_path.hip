@@ -1,5 +1,6 @@
 // The path estimate behind the C ABI (pk_filter.hpp; DESIGN.md section 4, "The path estimate"): the ring of resampled generations,
-// its transfers, the trace and the summary.  Host orchestration only; the kernels are pk_k_path.hip.  pk_resample (pk_api.hip)
+// its transfers, the trace, the summary, the summary by the weights and the most likely particle.  Host orchestration only; the
+// kernels are pk_k_path.hip and pk_k_path_weighted.hip.  pk_resample (pk_api.hip)
 // records through path_record; what refuses a recording filter says so through refuse_path (pk_api_shard.hip).
 #include "pk_filter.hpp"
 
@@ -22,7 +23,12 @@ void path_release(pk_filter* f) {
   dev_free(f, &f->ps_ref);
   dev_free(f, &f->ps_part);
   dev_free(f, &f->ps_res);
-  f->pt_cap = f->pt_out_cap = f->ps_rows = 0;
+  dev_free(f, &f->pw_idx);
+  dev_free(f, &f->pw_wgt);
+  dev_free(f, &f->pw_ref);
+  dev_free(f, &f->pw_part);
+  dev_free(f, &f->pw_res);
+  f->pt_cap = f->pt_out_cap = f->ps_rows = f->pw_rows = 0;
   f->path = PathRing();
 }
 
@@ -210,6 +216,79 @@ int pk_path_summary(pk_filter* f, double* mean, double* spread, int64_t* survivo
     }
     if (survivors) survivors[t] = (int64_t)s[7];
   }
+  return PK_OK;
+}
+
+int pk_path_summary_weighted(pk_filter* f, int32_t weight_domain, double* mean, double* spread, double* n_eff) {
+  int rc;
+  if ((rc = need_ring(f, "pk_path_summary_weighted"))) return rc;
+  if (weight_domain != PK_WEIGHTS_LINEAR && weight_domain != PK_WEIGHTS_LOG)
+    return fail(PK_ERR_INVALID, "pk_path_summary_weighted: weight_domain %d", weight_domain);
+  if ((rc = use_device(f))) return rc;
+  const PathRing& r = f->path;
+  const int64_t P = f->d.P, rows = (int64_t)r.held + 1;
+  const size_t nb = (size_t)path_blocks(P);
+  // (sized for the whole ring at once, as pk_path_summary's)
+  const int64_t rows_cap = (int64_t)r.cap + 1;
+  if ((rc = dev_reserve_group(f, &f->pw_rows, rows, rows_cap, want(&f->pw_idx, (size_t)P), want(&f->pw_wgt, (size_t)P),
+                              want(&f->pw_ref, (size_t)rows_cap * 3), want(&f->pw_part, (size_t)rows_cap * nb * kPathSums),
+                              want(&f->pw_res, (size_t)rows_cap * kPathWRes + 1))))
+    return rc;
+  double* const gmax = f->pw_res + (size_t)rows_cap * kPathWRes;
+  std::vector<double> h;
+  try {
+    h.resize((size_t)rows * kPathWRes);
+  } catch (const std::bad_alloc&) {
+    return fail(PK_ERR_NOMEM, "pk_path_summary_weighted: no host memory for %lld rows", (long long)rows);
+  }
+  {
+    Span t(f, PK_T_SUMMARY);
+    if (weight_domain == PK_WEIGHTS_LOG) launch_block_max(f->stream, f->d, f->partial, gmax);  // (f->partial: a workspace, no filter state)
+    launch_path_weighted(f->stream, f->d, r, gmax, weight_domain, f->pw_idx, f->pw_wgt, f->pw_ref, f->pw_part,
+                         f->pw_res);
+  }
+  PK_LAUNCH_CHECK("pk_path_summary_weighted");
+  PK_HIP(hipMemcpyAsync(h.data(), f->pw_res, h.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  PK_HIP(hipStreamSynchronize(f->stream));
+  const double* cur = h.data() + (size_t)r.held * kPathWRes;  // the weights are the current particles': one S1, one S2
+  const double S1 = cur[7], S2 = cur[8];
+  if (!(S1 > 0.0) || !std::isfinite(S1) || !std::isfinite(S2))
+    return fail(PK_ERR_STATE, "pk_path_summary_weighted: the weights sum to %g: not positive and finite", S1);
+  for (int64_t t = 0; t < rows; ++t) {
+    const double* s = h.data() + (size_t)t * kPathWRes;
+    if (mean) {
+      mean[3 * t] = s[0];
+      mean[3 * t + 1] = s[1];
+      mean[3 * t + 2] = std::atan2(s[2], s[3]);  // as pk_summary: prkt_core_v2.py:275
+    }
+    if (spread) {
+      spread[4 * t] = s[4];
+      spread[4 * t + 1] = s[5];
+      spread[4 * t + 2] = s[6];
+      spread[4 * t + 3] = std::hypot(s[2], s[3]) / S1;
+    }
+  }
+  if (n_eff) *n_eff = S1 / S2 * S1;
+  return PK_OK;
+}
+
+int pk_best_particle(pk_filter* f, int64_t* index, double* log_weight) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_best_particle: NULL handle");
+  int rc;
+  if ((rc = use_device(f))) return rc;
+  // f->partial (4 096 doubles, a workspace): the workgroups' pairs, then the result
+  double* const out = f->partial + 2 * kPathMaxBlocks;
+  {
+    Span t(f, PK_T_SUMMARY);
+    launch_best_particle(f->stream, f->d, f->partial, out);
+  }
+  PK_LAUNCH_CHECK("pk_best_particle");
+  double h[2];
+  PK_HIP(hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, f->stream));
+  PK_HIP(hipStreamSynchronize(f->stream));
+  if (h[1] < 0.0) return fail(PK_ERR_STATE, "pk_best_particle: every log-weight is NaN");
+  if (index) *index = (int64_t)h[1];
+  if (log_weight) *log_weight = h[0];
   return PK_OK;
 }
 

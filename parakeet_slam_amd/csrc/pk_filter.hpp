@@ -3,7 +3,7 @@
 //   pk_api.hip          lifecycle, transfers, motion, resample, the step, new-landmark bookkeeping, options, timing, the probe
 //   pk_api_observe.hip  the observe pipeline: staging, routing, association, the one-pass stages, the colour table's host side
 //   pk_api_shard.hip    the multi-GPU protocol: host-side, device-resident and balanced
-//   pk_api_path.hip     the path estimate: the ring of resampled generations, its transfers, trace and summary
+//   pk_api_path.hip     the path estimate: the ring of resampled generations, its transfers, trace and summaries, the best particle
 //   pk_api_adaptive.hip adaptive resampling: the gated resample and step, the weight sums, the weighted pose summary
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
 #pragma once
@@ -333,6 +333,13 @@ struct pk_filter {
   double* ps_part = nullptr;     // [ps_rows][path_blocks(P)][kPathSums]
   double* ps_res = nullptr;      // [ps_rows][kPathSums]
   int64_t ps_rows = 0;
+  // pk_path_summary_weighted's scratch (nothing until it is first called; path_release gives it back with the ring)
+  int32_t* pw_idx = nullptr;     // [P] every current particle's lineage index in the row being reduced
+  double* pw_wgt = nullptr;      // [P] its weight
+  double* pw_ref = nullptr;      // [pw_rows][3] particle 0's lineage
+  double* pw_part = nullptr;     // [pw_rows][path_blocks(P)][kPathSums]
+  double* pw_res = nullptr;      // [pw_rows][kPathWRes], then the call's own maximum log-weight (1 word)
+  int64_t pw_rows = 0;
   // adaptive resampling and the weighted pose summary (pk_api_adaptive.hip): nothing until one of its entry points is first called
   double* ad_s2 = nullptr;          // [nblocks] sum w^2 of every scan block
   double* ad_words = nullptr;       // [kAdWords] the scan's shift | the plan beyond kAncestorsScanMaxBlocks blocks | a maximum log-weight | the pose summary

@@ -389,6 +389,28 @@ void launch_path_trace(hipStream_t s, const DeviceState& d, const PathRing& ring
 // res_dev[held + 1][kPathRes]
 void launch_path_summary(hipStream_t s, const DeviceState& d, const PathRing& ring, unsigned* cnt_dev, double* ref_dev, double* part_dev,
                          double* res_dev);
+// The path estimate by the weights of the current particles (pk_k_path_weighted.hip; DESIGN.md section 4, "The weighted path
+// estimate"): three launches whatever the ring holds -- particle 0's lineage into ref_dev[held + 1][3]; ONE launch of path_blocks(P)
+// workgroups in which every thread walks its own particles' lineages back through rows held .. 0 (w = exp(logw - shift) as
+// launch_pose_moments takes it, into wgt_dev[P]; the lineage indices in idx_dev[P]) and reduces each row about its reference pose
+// into part_dev[row][path_blocks(P)][kPathSums]; one fold, a workgroup per row, into res_dev[held + 1][kPathWRes] = mean x, mean y,
+// sum w sin h, sum w cos h, var x, cov xy, var y, S1, S2 (row `held`'s).
+struct PathWeightedArgs {
+  const double *x, *y, *h, *logw;  // the live generation
+  const double* pose;              // the ring
+  const int32_t* anc;
+  const double *gmax, *ref;
+  int32_t* idx;
+  double *wgt, *part;
+  int64_t P;
+  int cap, first, held, domain;
+};
+constexpr int kPathWRes = 9;
+void launch_path_weighted(hipStream_t s, const DeviceState& d, const PathRing& ring, const double* gmax_dev, int domain,
+                          int32_t* idx_dev, double* wgt_dev, double* ref_dev, double* part_dev, double* res_dev);
+// The particle with the largest log-weight, the lowest index among equals, NaN never: part_dev[path_blocks(P)][2], then one fold
+// in workgroup order into out_dev[2] = the log-weight, the index as a double (-1: every log-weight is NaN)
+void launch_best_particle(hipStream_t s, const DeviceState& d, double* part_dev, double* out_dev);
 // Adaptive resampling (pk_k_adaptive.hip; DESIGN.md section 4, "Adaptive resampling"): the effective sample size of the weights
 // k_scan_local has just scanned, and the resample that declines when it is large enough -- decided on the device.
 // What a gated call leaves for the host to read when it asks (pk_resample_stats); one thread writes it.
