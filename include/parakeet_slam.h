@@ -275,6 +275,43 @@ int pk_map_moments(pk_filter* f, int32_t weighting, double gmax, double wsum[2],
  * update_count[L], n_eff[1].  Any output may be NULL. */
 int pk_map_summary(pk_filter* f, int32_t weighting, double* mean, double* cov_within, double* cov_between, double* update_count, double* n_eff);
 
+/* The DISCOVERED landmarks of a growing filter (pk_grow_enable): the spare slots, which pk_map_summary leaves NaN because slot j of
+ * one particle and slot j of another need not hold the same feature (only the children of one ancestor agree slot by slot, and the
+ * feature ids are per particle).  The correspondence is geometric.  For every reference feature r = (x, y, r, g, b) and every
+ * particle, among the particle's spare slots in use (its counter word 1, at most S), a slot with mean mu is a candidate when
+ *   dpos2 = (mu_x - r_x)^2 + (mu_y - r_y)^2 <= radius^2   and   dcol2 = ((mu_r - r_r)^2 + (mu_g - r_g)^2) + (mu_b - r_b)^2 <= colour_radius^2
+ * (evaluated exactly so, in double, without fused multiply-adds; a NaN mean fails), and the match is the candidate with the strictly
+ * smallest score dpos2 / radius^2 + dcol2 / colour_radius^2 (the reciprocals formed once; 0 for an infinite radius), the lowest
+ * slot among equals.  Matches are taken independently per reference feature: they are NOT one-to-one, two reference features
+ * closer than the radii can claim one slot -- keep radius below half the smallest separation of the landmarks.  radius and
+ * colour_radius must be > 0 (+inf is allowed).  Per reference feature the matched slots are reduced as pk_map_moments reduces a
+ * preset landmark, with w_p as there; the sums are shifted by the reference feature, which the radii bound.  No float atomics, every
+ * sum in a fixed order: the same state gives the same bits on every call.  Nothing is moved, no filter state changes, and there is
+ * no host round trip between the launches; the scratch is allocated by the first call.
+ * PK_ERR_STATE: pk_grow_enable was not called, no map, no finite maximum log-weight (weighted), weights that do not sum to a positive
+ * finite value; PK_ERR_UNSUPPORTED: the dense layout; PK_ERR_INVALID: the arguments.
+ *
+ * pk_map_match_moments: the unfinished moments about ANY reference points (0 <= n_ref <= 4096; what shards would combine).  gmax as
+ * for pk_map_moments.  wsum[2] = sum w, sum w^2 over ALL particles; support[n_ref*3] = per feature W_j = sum w, sum w^2, sum w over
+ * the matches whose count word carries PK_LANDMARK_POTENTIAL; mean[n_ref*5] = r_j + sum w (mu - r_j) / W_j; m2[n_ref*15] = sum w
+ * (mu - mean)(mu - mean)^T, upper triangle row-major; within[n_ref*9] = sum w Sigma; counts[n_ref] = sum w update_count;
+ * matches[P*n_ref] = the spare slot matched (0 .. S - 1, landmark preset + slot of the particle), -1 = none.  A feature nobody
+ * matched: W_j = 0, mean and m2 NaN.  Any output may be NULL. */
+int pk_map_match_moments(pk_filter* f, int32_t weighting, double gmax, const double* ref_means, int32_t n_ref, double radius,
+                         double colour_radius, double wsum[2], double* support, double* mean, double* m2, double* within, double* counts,
+                         int32_t* matches);
+/* The finished estimate about ONE particle's own features: the reference features are the spare slots in use of particle
+ * reference_particle, -1 = pk_best_particle's choice (taken on the device).  reference_out[1] = that particle, n_out[1] = its
+ * features n <= S; per spare slot (S rows): ids = the reference particle's feature ids, ref_counts = its count words, mean[S*5],
+ * cov_within[S*25], cov_between[S*25] (dense 5x5 as pk_map_summary), update_count[S], support[S] = W_j / W, the share of the
+ * population that holds the feature, potential_fraction[S] = the share of those that still hold it as a potential feature,
+ * n_eff[S] = W_j^2 / sum_j w^2, n_eff_all[1] = W^2 / sum w^2.  A feature nobody matched (a reference particle of weight 0 alone
+ * holds it): support 0, NaN elsewhere; rows n .. S - 1: ids and ref_counts 0, support 0, NaN elsewhere.  Any output may be NULL. */
+int pk_map_discovered(pk_filter* f, int32_t weighting, int64_t reference_particle, double radius, double colour_radius,
+                      int64_t* reference_out, int32_t* n_out, int32_t* ids, int32_t* ref_counts, double* mean, double* cov_within,
+                      double* cov_between, double* update_count, double* support, double* potential_fraction, double* n_eff,
+                      double* n_eff_all);
+
 /* ---- the path estimate: lineages recorded at every resample, traced back ("The path estimate") --------
  * FastSLAM factors the posterior over the robot's PATH; pk_resample overwrites the generation it resamples, so without a record
  * the filter knows the end of the path only (the reference keeps no more either: prkt_core_v2.py:210-252 replaces

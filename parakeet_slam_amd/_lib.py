@@ -71,6 +71,9 @@ SIGNATURES = {
     "pk_pose_sums": (C.c_int, [_h, _dp]),
     "pk_map_moments": (C.c_int, [_h, C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "pk_map_summary": (C.c_int, [_h, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
+    "pk_map_match_moments": (C.c_int, [_h, C.c_int32, C.c_double, _dp, C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "pk_map_discovered": (C.c_int, [_h, C.c_int32, C.c_int64, C.c_double, C.c_double, _lp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
+                                    _dp, _dp]),
     "pk_path_enable": (C.c_int, [_h, C.c_int32]),
     "pk_path_shape": (C.c_int, [_h, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "pk_path_download": (C.c_int, [_h, C.c_int32, C.c_int32, _dp, _ip]),
@@ -364,6 +367,40 @@ class DeviceFilter(object):
         count, n_eff = np.empty(L), np.empty(1)
         check(self._lib.pk_map_summary(self._h, int(weighting), dptr(mean), dptr(within), dptr(between), dptr(count), dptr(n_eff)))
         return mapsum.MapSummary(mean, within, between, count, n_eff[0])
+
+    def map_match_moments(self, ref_means, radius, colour_radius, weighting=PK_MAP_UNIFORM, gmax=None, matches=False):
+        """The moments of the particles' spare slots matched against the reference features ``ref_means`` (n, 5)
+        (pk_map_match_moments) as ``mapsum.MatchedMoments``; matches=True: also the match table (P, n) int32, the spare slot of
+        every particle matched to every feature or -1.  A slot matches a feature inside both radii, the smallest normalised
+        distance wins; the matches are taken per feature, NOT one-to-one: keep ``radius`` below half the smallest landmark
+        separation.  gmax as for map_moments."""
+        ref = f64(ref_means).reshape(-1, 5)
+        n = ref.shape[0]
+        wsum, support, mean, m2 = np.empty(2), np.empty((n, 3)), np.empty((n, 5)), np.empty((n, 15))
+        within, counts = np.empty((n, 9)), np.empty(n)
+        table = np.empty((self.P, n), dtype=np.int32) if matches else None
+        check(self._lib.pk_map_match_moments(self._h, int(weighting), float("nan") if gmax is None else float(gmax), dptr(ref), n,
+                                             float(radius), float(colour_radius), dptr(wsum), dptr(support), dptr(mean), dptr(m2),
+                                             dptr(within), dptr(counts), iptr(table)))
+        return mapsum.MatchedMoments(wsum, support, mean, m2, within, counts, table)
+
+    def map_discovered(self, radius, colour_radius, weighting=PK_MAP_UNIFORM, reference=None):
+        """The estimate of the discovered landmarks (pk_map_discovered) as ``mapsum.DiscoveredMap``: the spare slots in use of
+        the reference particle (None: the most likely one, ``best_particle()``'s) matched in every particle, and per feature the
+        mean, the covariances and the share of the population that holds it.  The matches are NOT one-to-one: keep ``radius``
+        below half the smallest landmark separation."""
+        L0, S, _ = self.grow_shape()
+        who, n = C.c_int64(-1), C.c_int32(0)
+        ids, ref_counts = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+        mean, within, between = np.empty((S, 5)), np.empty((S, 5, 5)), np.empty((S, 5, 5))
+        count, support, potential, n_eff, n_eff_all = np.empty(S), np.empty(S), np.empty(S), np.empty(S), np.empty(1)
+        check(self._lib.pk_map_discovered(self._h, int(weighting), -1 if reference is None else int(reference), float(radius),
+                                          float(colour_radius), C.byref(who), C.byref(n), iptr(ids), iptr(ref_counts), dptr(mean),
+                                          dptr(within), dptr(between), dptr(count), dptr(support), dptr(potential), dptr(n_eff),
+                                          dptr(n_eff_all)))
+        k = int(n.value)
+        return mapsum.DiscoveredMap(mean[:k], within[:k], between[:k], count[:k], support[:k], potential[:k], n_eff[:k], n_eff_all[0],
+                                    reference_particle=int(who.value), ids=ids[:k], slots=L0 + np.arange(k), ref_counts=ref_counts[:k])
 
     # -- the path estimate (pk_path_*): rows 0 .. held - 1 are the recorded steps, oldest first; row held is the current generation
     def path_enable(self, capacity):

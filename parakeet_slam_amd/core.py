@@ -974,6 +974,26 @@ class FastSLAM(object):
         with self._lock:
             return self._filter.map_summary(code)
 
+    def discovered_landmarks(self, weighting=None, reference=None, radius=3.0, colour_radius=None):
+        """The estimate of the landmarks the filter DISCOVERED (new_landmarks=True), which map_summary() leaves NaN: spare slot
+        j of one particle and of another need not hold the same feature, so the features of one reference particle (None: the
+        most likely one, best_particle()) are matched in every particle by position and colour and reduced over the particles
+        that hold them, on the device (``mapsum.DiscoveredMap``: per feature the mean, the covariances, the share of the
+        population that holds it).  weighting as for map_summary().  A slot matches inside ``radius`` (3.0: three standard
+        deviations of the identity position covariance a new feature is born with) and ``colour_radius`` (None: the filter's
+        pair_threshold, the colour distance under which two readings already count as one landmark); the nearest wins.  The
+        matches are taken per feature, NOT one-to-one: keep ``radius`` below half the smallest landmark separation."""
+        if not self._grow:
+            raise ValueError("discovered_landmarks: this filter discovers no landmarks (FastSLAM(..., new_landmarks=True, spare_landmarks=S))")
+        if not self._nl_device:
+            raise ValueError("discovered_landmarks: the match reads the bookkeeping on the device (bookkeeping='device' and spare_landmarks > 0)")
+        if weighting is None:
+            weighting = "uniform" if self._threshold is None else "weights"
+        code = mapsum.weighting_code(weighting)
+        kappa = self._pair_threshold if colour_radius is None else float(colour_radius)
+        with self._lock:
+            return self._filter.map_discovered(float(radius), kappa, code, reference)
+
     def _need_path(self, who):
         if not self._record_path:
             raise ValueError("%s: this filter does not record its path (FastSLAM(..., record_path=T))" % who)

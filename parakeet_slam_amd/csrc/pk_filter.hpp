@@ -5,6 +5,7 @@
 //   pk_api_shard.hip    the multi-GPU protocol: host-side, device-resident and balanced
 //   pk_api_path.hip     the path estimate: the ring of resampled generations, its transfers, trace and summaries, the best particle
 //   pk_api_adaptive.hip adaptive resampling: the gated resample and step, the weight sums, the weighted pose summary
+//   pk_api_mapmatch.hip the discovered landmarks: the matched moments and the finished estimate
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -146,6 +147,7 @@ struct Options {
   int colour_table_margin = -1;   // option: the host leaves the mode this many levels short of the table's end; -1: min(16, depth / 2); 0: never
   int colour_table = -1;          // option: -1 auto, 0 off, 1 as auto
   int map_sum_groups = 0;         // the map estimate's particle groups: 0 = map_sum_groups(P, Ls) (pk_kernels.hpp), else forced (tests: many particles per group, ragged last groups)
+  int map_match_groups = 0;       // the discovered landmarks' particle groups: 0 = map_match_groups(P, rows), else forced (tests)
 };
 
 // One row per knob: the name a caller gives, the member, how the value is taken, the inclusive range, the refusal outside it.
@@ -188,6 +190,7 @@ inline constexpr OptionRow kOptionTable[] = {
     {"colour_table_margin", &Options::colour_table_margin, Take::Range, -1, 32768,
      "colour_table_margin: -1 (auto), 0 (the host never leaves the mode for the table's end) or levels"},
     {"map_sum_groups", &Options::map_sum_groups, Take::Range, 0, 1024, "map_sum_groups: 0 (chosen from the shape) .. 1024"},
+    {"map_match_groups", &Options::map_match_groups, Take::Range, 0, 1024, "map_match_groups: 0 (chosen from the shape) .. 1024"},
     // "colour_table" itself is taken by pk_set_option in code: switching it off in mid-run gives the slots their colour rows back
 };
 
@@ -323,6 +326,15 @@ struct pk_filter {
   double* ms_part = nullptr;     // [groups][kMapSums][tiles x kMapSumLanes] k_map_partials' sums
   double* ms_res = nullptr;      // the handle's own maximum log-weight (2 words) | [kMapSumMaxGroups][2] the groups' weight sums | [2 + 30 L] the moments
   size_t ms_cap = 0;             // doubles of ms_part
+  // the discovered landmarks (pk_map_match_moments / pk_map_discovered; pk_api_mapmatch.hip): nothing until the first call
+  double* mm_ref = nullptr;      // [mm_rows][5] the reference features
+  int32_t* mm_refi = nullptr;    // [4 + 2 mm_rows] launch_match_reference's integers
+  double* mm_res = nullptr;      // a maximum log-weight (2 words) | [kMatchMaxGroups][2] the groups' weight sums | k_match_finish's result
+  size_t mm_rows = 0;
+  double* mm_part = nullptr;     // k_match_partials' sums
+  size_t mm_part_cap = 0;        // doubles of mm_part
+  int32_t* mm_match = nullptr;   // [P][n_ref] the match table, for the calls that ask for it
+  size_t mm_match_cap = 0;
   // the path estimate (pk_path_enable; pk_api_path.hip): the ring, and pk_path_trace's / pk_path_summary's scratch -- nothing until first asked for
   PathRing path{};
   int64_t* pt_idx = nullptr;     // [pt_cap] the particles of one pk_path_trace chunk

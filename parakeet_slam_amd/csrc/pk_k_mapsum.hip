@@ -174,6 +174,12 @@ __global__ void __launch_bounds__(kMapSumLanes) k_map_finish(SlotSource ss, cons
   counts[0] = s[29];
 }
 
+// n: doubles of one group's partials
+void launch_map_fold(hipStream_t s, int groups, size_t n, double* part_dev, double* wpart_dev) {
+  hipLaunchKernelGGL(k_map_fold, dim3((unsigned)((n + kMapSumLanes - 1) / kMapSumLanes) + 1), dim3(kMapSumLanes), 0, s, groups, n, part_dev,
+                     wpart_dev);
+}
+
 void launch_map_moments(hipStream_t s, const DeviceState& d, int Ls, int weighted, double gmax, int groups, double* part_dev,
                         double* wpart_dev, double* res_dev) {
   const int tiles = map_sum_tiles(Ls);
@@ -182,9 +188,7 @@ void launch_map_moments(hipStream_t s, const DeviceState& d, int Ls, int weighte
   const SlotSource ss = slot_source(d);
   hipLaunchKernelGGL(k_map_partials, dim3((unsigned)tiles, (unsigned)groups), dim3(kMapSumLanes), 0, s, ss, d.src[d.cur],
                      weighted ? d.logw[d.cur] : nullptr, gmax, d.P, chunk, d.lay.Lp, Ls, d.lay.count_off, Lq, part_dev, wpart_dev);
-  const size_t n = (size_t)kMapSums * Lq;  // doubles of one group's partials
-  hipLaunchKernelGGL(k_map_fold, dim3((unsigned)((n + kMapSumLanes - 1) / kMapSumLanes) + 1), dim3(kMapSumLanes), 0, s, groups, n, part_dev,
-                     wpart_dev);
+  launch_map_fold(s, groups, (size_t)kMapSums * Lq, part_dev, wpart_dev);
   const int L = d.lay.L;
   hipLaunchKernelGGL(k_map_finish, dim3((unsigned)map_sum_tiles(L)), dim3(kMapSumLanes), 0, s, ss, d.src[d.cur],
                      d.lay.Lp, L, Ls, Lq, part_dev, wpart_dev, res_dev);

@@ -362,6 +362,43 @@ int map_sum_groups(int64_t P, int Ls, int forced);  // a function of (P, Ls) alo
 inline size_t map_sum_part_doubles(int Ls, int groups) { return (size_t)groups * kMapSums * map_sum_tiles(Ls) * kMapSumLanes; }
 void launch_map_moments(hipStream_t s, const DeviceState& d, int Ls, int weighted, double gmax, int groups, double* part_dev,
                         double* wpart_dev, double* res_dev);
+// k_map_fold alone: part_dev[groups][n] added in group order into group 0's, wpart_dev[groups][2] into wpart_dev[0 .. 1]
+void launch_map_fold(hipStream_t s, int groups, size_t n, double* part_dev, double* wpart_dev);
+// The discovered landmarks (pk_k_mapmatch.hip): per reference feature the spare slot of every particle that
+// holds it (inside both radii, the smallest score, the lowest slot among equals) and the moments of the matched slots about the
+// reference feature.  k_match_partials, grid (tiles of kMatchLanes features, particle groups), one wave a workgroup, leaves
+// part[groups][kMatchSums][tiles x kMatchLanes] (sum w, sum w^2, sum w[potential] of the matches | 5 first, 15 second moments of
+// mu - r | 9 within | 1 count) and wpart[groups][2]; k_map_fold adds them; k_match_finish un-shifts by every feature's own sum w into
+// res[2 + kMatchSums rows + 3 + 2 rows]: wsum[2] | support[rows][3] | mean[rows][5] | m2[rows][15] | within[rows][9] | counts[rows] |
+// the maximum log-weight used, the number of reference features, the reference particle | its count words [rows] | its ids [rows].
+constexpr int kMatchLanes = 64;
+constexpr int kMatchSums = 33;
+constexpr int kMatchMaxGroups = 1024;
+constexpr int kMatchMaxRef = 4096;
+inline int map_match_tiles(int rows) { return rows > 0 ? (rows + kMatchLanes - 1) / kMatchLanes : 1; }
+int map_match_groups(int64_t P, int rows, int forced);  // a function of (P, rows) alone unless forced (option "map_match_groups") > 0
+inline size_t map_match_part_doubles(int rows, int groups) { return (size_t)groups * kMatchSums * map_match_tiles(rows) * kMatchLanes; }
+inline size_t map_match_res_doubles(int rows) { return 2 + (size_t)kMatchSums * rows + 3 + 2 * (size_t)rows; }
+struct MatchJob {
+  int rows = 0;                      // rows of the result: the reference features (pk_map_match_moments) or the spare slots (pk_map_discovered)
+  int nref = 0;                      // reference features when refi_dev == NULL, else word 0 of refi_dev says
+  int groups = 1;
+  int weighted = 0;
+  double gmax = 0.0;                 // the shift of the log-weights when gmax_dev == NULL
+  const double* gmax_dev = nullptr;
+  double rho2 = 0.0, kap2 = 0.0, irho2 = 0.0, ikap2 = 0.0;  // squared radii and their reciprocals (0 for an infinite radius)
+  const double* ref_dev = nullptr;   // [rows][5]
+  const int32_t* refi_dev = nullptr; // launch_match_reference's integers, or NULL
+  double* part_dev = nullptr;
+  double* wpart_dev = nullptr;
+  double* res_dev = nullptr;
+  int32_t* matches_dev = nullptr;    // [P][nref] or NULL
+};
+// the reference particle's (best_dev != NULL: k_best_particle_fold's out[2], else `particle`) spare slots in use into ref_dev[S][5]
+// and refi_dev[4 + 2 S] = their number, the particle, 0, 0 | count words | feature ids
+void launch_match_reference(hipStream_t s, const DeviceState& d, const GrowState& g, const double* best_dev, int64_t particle,
+                            double* ref_dev, int32_t* refi_dev);
+void launch_map_match(hipStream_t s, const DeviceState& d, const GrowState& g, const MatchJob& m);
 // The path estimate (pk_k_path.hip): a ring of the last `cap` resampled generations.  Row r of the ring:
 // pose[r][3][P] (x, y, heading, structure of arrays like the live poses) and anc[r][P]; the held rows are first, first + 1, ...
 // modulo cap, oldest first.
