@@ -572,7 +572,18 @@ int pk_probe(int32_t device, const double pose[3], const double mean[5], const d
  *   PK_MATH_KEY               double_to_key(x), key_to_double of it    1 -> 2  (both as 64 raw bits in a double's place)
  *   PK_MATH_FAR_BOUND         pub_far_bound(landmark)                  14 -> 2 (mean x y r g b, pxx pxy pyy, crr crg crb cgg cgb
  *                                                                               cbb -> fk, fi)
- *   PK_MATH_PR_FROM_PARTS     pr_from_parts(det2, det3, num2, num3)    4 -> 1 */
+ *   PK_MATH_PR_FROM_PARTS     pr_from_parts(det2, det3, num2, num3)    4 -> 1
+ *   PK_MATH_EKF_UPDATE        ekf_update(landmark, pose, blob, Qt)     31 -> 17
+ *       in:  sx sy | the 14 landmark fields as above | count (an integer-valued double, PK_LANDMARK_POTENTIAL included) |
+ *            blob bearing r g b | Qt as q00 rr rg rb gg gb bb | zhat0 | flags | prod_in
+ *            flags (an integer-valued double): bit 0 immutable, bit 1 zhat0 is passed as the known expected bearing, bit 2 the
+ *            colour block is left as it was (the table mode's call), bit 3 the one-logarithm-per-lane form (the squared
+ *            Frobenius norm is multiplied into prod, its logarithm left out of the returned value)
+ *       out: the returned log weight | the 14 fields afterwards | the count afterwards | prod afterwards
+ *   PK_MATH_MATCH             the match probabilities                  23 -> 5
+ *       in:  sx sy heading | the 14 landmark fields | blob bearing r g b | ux uy (the blob's unit ray)
+ *       out: probability_of_match | prob_position_match (pse = pk_atan2 of the offset) | prob_color_match | closest_point x y
+ * The last two are held to an exact dense reference by tests/test_gpu_ekf_reference.py (record: profiles/r10/ekf_errors.json). */
 enum {
   PK_MATH_LOG_FEW_ULP = 0,
   PK_MATH_PUB_LOG = 1,
@@ -582,7 +593,12 @@ enum {
   PK_MATH_KEY = 5,
   PK_MATH_FAR_BOUND = 6,
   PK_MATH_PR_FROM_PARTS = 7,
-  PK_MATH_COUNT = 8
+  /* 8 is no op and never will be: the call carries no buffer lengths, and callers written while 8 was the first
+   * unknown op pass it with buffers of a few doubles to see it refused -- an op there would write 17 doubles a row
+   * past the end of theirs */
+  PK_MATH_EKF_UPDATE = 9,
+  PK_MATH_MATCH = 10,
+  PK_MATH_COUNT = 11 /* one past the last op */
 };
 int pk_probe_math(int32_t device, int32_t op, int64_t n, const double* in, double* out);
 

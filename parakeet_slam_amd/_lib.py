@@ -26,8 +26,10 @@ PK_T_COUNT = len(PK_T_NAMES)
 PK_PROBE_LEN = 79
 (PK_MATH_LOG_FEW_ULP, PK_MATH_PUB_LOG, PK_MATH_PUB_RECIP, PK_MATH_ATAN2, PK_MATH_ROUND_DOWN_F32, PK_MATH_KEY, PK_MATH_FAR_BOUND,
  PK_MATH_PR_FROM_PARTS) = range(8)
+PK_MATH_EKF_UPDATE, PK_MATH_MATCH = 9, 10  # (8 stays refused: parakeet_slam.h)
 PK_MATH_SHAPES = {PK_MATH_LOG_FEW_ULP: (1, 1), PK_MATH_PUB_LOG: (1, 1), PK_MATH_PUB_RECIP: (1, 1), PK_MATH_ATAN2: (2, 1),
-                  PK_MATH_ROUND_DOWN_F32: (1, 1), PK_MATH_KEY: (1, 2), PK_MATH_FAR_BOUND: (14, 2), PK_MATH_PR_FROM_PARTS: (4, 1)}  # op -> (arity, outputs)
+                  PK_MATH_ROUND_DOWN_F32: (1, 1), PK_MATH_KEY: (1, 2), PK_MATH_FAR_BOUND: (14, 2), PK_MATH_PR_FROM_PARTS: (4, 1),
+                  PK_MATH_EKF_UPDATE: (31, 17), PK_MATH_MATCH: (23, 5)}  # op -> (arity, outputs)
 PK_ABI_VERSION = 1
 
 _dp = C.POINTER(C.c_double)

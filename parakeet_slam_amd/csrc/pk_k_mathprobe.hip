@@ -1,6 +1,7 @@
 // The math probe (pk_probe_math): the float64 primitives of pk_math.hpp, pk_pub_math.hpp and pk_device.hpp on arrays of
 // arguments, one element per thread, so that the tests can hold each of them to an exact reference over its whole domain
-// (tests/test_gpu_math_probe.py).  The kernels CALL the functions of the three headers -- nothing is restated here: what is
+// (tests/test_gpu_math_probe.py) -- and the algebra built from them, ekf_update in each of its variants and the match densities
+// (tests/test_gpu_ekf_reference.py).  The kernels CALL the functions of the three headers -- nothing is restated here: what is
 // measured is what the observe kernels run, inline assembly and all.  Diagnostic only; no kernel of the step is in this file,
 // and the entry point lives here beside its kernels.
 #include "pk_device.hpp"
@@ -13,6 +14,53 @@ __device__ __forceinline__ double bits_to_double(unsigned long long b) {
   double x;
   memcpy(&x, &b, 8);
   return x;
+}
+
+// one landmark from 14 doubles in the compact row order of pk_layout.hpp
+__device__ __forceinline__ Landmark<double> landmark_of_row(const double* __restrict__ r, int count) {
+  Landmark<double> lm;
+  lm.mx = r[F_MX];
+  lm.my = r[F_MY];
+  lm.mr = r[F_MR];
+  lm.mg = r[F_MG];
+  lm.mb = r[F_MB];
+  lm.pxx = r[F_PXX];
+  lm.pxy = r[F_PXY];
+  lm.pyy = r[F_PYY];
+  lm.crr = r[F_CRR];
+  lm.crg = r[F_CRG];
+  lm.crb = r[F_CRB];
+  lm.cgg = r[F_CGG];
+  lm.cgb = r[F_CGB];
+  lm.cbb = r[F_CBB];
+  lm.count = count;
+  return lm;
+}
+__device__ __forceinline__ void row_of_landmark(const Landmark<double>& lm, double* __restrict__ r) {
+  r[F_MX] = lm.mx;
+  r[F_MY] = lm.my;
+  r[F_MR] = lm.mr;
+  r[F_MG] = lm.mg;
+  r[F_MB] = lm.mb;
+  r[F_PXX] = lm.pxx;
+  r[F_PXY] = lm.pxy;
+  r[F_PYY] = lm.pyy;
+  r[F_CRR] = lm.crr;
+  r[F_CRG] = lm.crg;
+  r[F_CRB] = lm.crb;
+  r[F_CGG] = lm.cgg;
+  r[F_CGB] = lm.cgb;
+  r[F_CBB] = lm.cbb;
+}
+
+constexpr int kEkfIn = 31, kEkfOut = 17, kMatchIn = 23, kMatchOut = 5;
+
+// ekf_update with the expected bearing supplied (KNOWN) or not, the colour block updated (COLOUR) or not, the logarithm of the
+// norm left to the caller (FRO) or not
+template <bool COLOUR, bool KNOWN, bool FRO>
+__device__ __forceinline__ double ekf_variant(Landmark<double>& lm, double sx, double sy, const BlobT<double>& z,
+                                              const Noise<double>& qt, bool immutable, double zhat0, double& prod) {
+  return ekf_update<double, COLOUR>(lm, sx, sy, z, qt, immutable, nullptr, KNOWN ? &zhat0 : nullptr, FRO ? &prod : nullptr);
 }
 
 // in[n][arity(OP)] -> out[n][outputs(OP)], row-major
@@ -34,31 +82,56 @@ __global__ void __launch_bounds__(256) k_probe_math(const double* __restrict__ i
     const unsigned long long k = double_to_key(in[i]);
     out[2 * i] = bits_to_double(k);
     out[2 * i + 1] = key_to_double(k);
-  } else if constexpr (OP == PK_MATH_FAR_BOUND) {  // the compact row order of pk_layout.hpp
-    const double* r = in + (int64_t)F_COUNT_FIELDS * i;
-    Landmark<double> lm;
-    lm.mx = r[F_MX];
-    lm.my = r[F_MY];
-    lm.mr = r[F_MR];
-    lm.mg = r[F_MG];
-    lm.mb = r[F_MB];
-    lm.pxx = r[F_PXX];
-    lm.pxy = r[F_PXY];
-    lm.pyy = r[F_PYY];
-    lm.crr = r[F_CRR];
-    lm.crg = r[F_CRG];
-    lm.crb = r[F_CRB];
-    lm.cgg = r[F_CGG];
-    lm.cgb = r[F_CGB];
-    lm.cbb = r[F_CBB];
-    lm.count = 0;
+  } else if constexpr (OP == PK_MATH_FAR_BOUND) {
+    Landmark<double> lm = landmark_of_row(in + (int64_t)F_COUNT_FIELDS * i, 0);
     double fk, fi;
     pub_far_bound(lm, fk, fi);
     out[2 * i] = fk;
     out[2 * i + 1] = fi;
-  } else {
-    static_assert(OP == PK_MATH_PR_FROM_PARTS, "unknown op");
+  } else if constexpr (OP == PK_MATH_PR_FROM_PARTS) {
     out[i] = pr_from_parts(in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3]);
+  } else if constexpr (OP == PK_MATH_EKF_UPDATE) {
+    // sx sy | 14 fields | count | bearing r g b | q00 rr rg rb gg gb bb | zhat0 | flags | prod_in
+    const double* r = in + (int64_t)kEkfIn * i;
+    Landmark<double> lm = landmark_of_row(r + 2, (int)r[16]);
+    const BlobT<double> z{r[17], r[18], r[19], r[20]};
+    const Noise<double> qt = make_noise(r[21], r[22], r[23], r[24], r[25], r[26], r[27]);
+    const double zhat0 = r[28];
+    const int flags = (int)r[29];  // 1 immutable, 2 zhat0_known, 4 COLOUR = false, 8 fro_prod
+    double prod = r[30];
+    const bool immutable = (flags & 1) != 0;
+    double logw;
+    switch ((flags >> 1) & 7) {  // every variant with its pointers known at compile time, as the step kernels call it
+      case 0: logw = ekf_variant<true, false, false>(lm, r[0], r[1], z, qt, immutable, zhat0, prod); break;
+      case 1: logw = ekf_variant<true, true, false>(lm, r[0], r[1], z, qt, immutable, zhat0, prod); break;
+      case 2: logw = ekf_variant<false, false, false>(lm, r[0], r[1], z, qt, immutable, zhat0, prod); break;
+      case 3: logw = ekf_variant<false, true, false>(lm, r[0], r[1], z, qt, immutable, zhat0, prod); break;
+      case 4: logw = ekf_variant<true, false, true>(lm, r[0], r[1], z, qt, immutable, zhat0, prod); break;
+      case 5: logw = ekf_variant<true, true, true>(lm, r[0], r[1], z, qt, immutable, zhat0, prod); break;
+      case 6: logw = ekf_variant<false, false, true>(lm, r[0], r[1], z, qt, immutable, zhat0, prod); break;
+      default: logw = ekf_variant<false, true, true>(lm, r[0], r[1], z, qt, immutable, zhat0, prod); break;
+    }
+    double* o = out + (int64_t)kEkfOut * i;  // logw | 14 fields | count | prod
+    o[0] = logw;
+    row_of_landmark(lm, o + 1);
+    o[15] = (double)lm.count;
+    o[16] = prod;
+  } else {
+    static_assert(OP == PK_MATH_MATCH, "unknown op");
+    // sx sy heading | 14 fields | bearing r g b | ux uy
+    const double* r = in + (int64_t)kMatchIn * i;
+    const double sx = r[0], sy = r[1], heading = r[2], ux = r[21], uy = r[22];
+    const Landmark<double> lm = landmark_of_row(r + 3, 0);
+    const BlobT<double> z{r[17], r[18], r[19], r[20]};
+    const double pse = pk_atan2(lm.my - sy, lm.mx - sx);  // as probability_of_match forms it
+    double nx, ny;
+    closest_point(lm.mx, lm.my, sx, sy, ux, uy, nx, ny);
+    double* o = out + (int64_t)kMatchOut * i;  // probability_of_match | position | colour | closest point
+    o[0] = probability_of_match(lm, sx, sy, heading, z, ux, uy);
+    o[1] = prob_position_match(lm, sx, sy, pse, z.bearing, ux, uy);
+    o[2] = prob_color_match(lm, z.r, z.g, z.b);
+    o[3] = nx;
+    o[4] = ny;
   }
 }
 
@@ -80,10 +153,20 @@ int math_probe_arity(int op) {
     case PK_MATH_ATAN2: return 2;
     case PK_MATH_FAR_BOUND: return F_COUNT_FIELDS;
     case PK_MATH_PR_FROM_PARTS: return 4;
+    case PK_MATH_EKF_UPDATE: return kEkfIn;
+    case PK_MATH_MATCH: return kMatchIn;
     default: return 0;
   }
 }
-int math_probe_outputs(int op) { return op == PK_MATH_KEY || op == PK_MATH_FAR_BOUND ? 2 : 1; }
+int math_probe_outputs(int op) {
+  switch (op) {
+    case PK_MATH_KEY:
+    case PK_MATH_FAR_BOUND: return 2;
+    case PK_MATH_EKF_UPDATE: return kEkfOut;
+    case PK_MATH_MATCH: return kMatchOut;
+    default: return 1;
+  }
+}
 
 void launch_probe_math(hipStream_t s, int op, const double* in_dev, double* out_dev, int64_t n) {
   switch (op) {
@@ -95,6 +178,8 @@ void launch_probe_math(hipStream_t s, int op, const double* in_dev, double* out_
     case PK_MATH_KEY: return launch_one<PK_MATH_KEY>(s, in_dev, out_dev, n);
     case PK_MATH_FAR_BOUND: return launch_one<PK_MATH_FAR_BOUND>(s, in_dev, out_dev, n);
     case PK_MATH_PR_FROM_PARTS: return launch_one<PK_MATH_PR_FROM_PARTS>(s, in_dev, out_dev, n);
+    case PK_MATH_EKF_UPDATE: return launch_one<PK_MATH_EKF_UPDATE>(s, in_dev, out_dev, n);
+    case PK_MATH_MATCH: return launch_one<PK_MATH_MATCH>(s, in_dev, out_dev, n);
     default: return;
   }
 }

@@ -297,6 +297,14 @@ struct EkfAux {
 // I - C (C + Qc)^-1 = Qc (C + Qc)^-1), six products instead of eighteen and without the
 // subtraction; the Mahalanobis term is d'v with v = (C + Qc)^-1 d in both forms.
 //
+// DOMAIN.  Held to an exact dense reference (mpmath; tests/test_gpu_ekf_reference.py through PK_MATH_EKF_UPDATE, figures in
+// profiles/r10/ekf_errors.json), every output stays within (32 + kappa^2 / 8) 2^-53 of the sum of the absolute values of its
+// terms, kappa = cond_2(C + Qc): 1e-10 of its terms while kappa <~ 2.7e3.  (C + Qc)^-1 is adjugate / determinant, which loses
+// kappa^2 in the colour mean and the weight where the reference's LAPACK inverse loses kappa: at kappa up to 1e3 the worst
+// measured is 9.9e3 units (log weight; the float64 reference 1.5e2), at kappa up to 1e5 2.5e7 units (colour mean, 2.8e-9 of its
+// terms; the reference 6.8e3).  A colour block whose brightness variance is far above its chroma variance on a landmark's first
+// update is such a block.  Elsewhere (ranges 1e-6 .. 1e4, P 1e-16 .. 1e12, C 1e-6 .. 1e6, q == 0, a full Qc) the worst is 14 units.
+//
 // The colour block's step depends on C and Qt alone -- not on the pose, not on the blob: colour_block_update, one function for
 // every caller (ekf_update; the colour table of pk_k_colour.hip), so that -ffp-contract=on rounds it the same way everywhere.
 // qci = (C + Qc)^-1 as sym3_inverse gives it.

@@ -30,12 +30,13 @@ def _card():
         return os.environ.get("PK_FIGURES_CARD", "unknown")
 
 
-def record(section, name, **figures):
+def record(section, name, _what=None, **figures):
+    """_what: what a record of its own says of itself (profiles/r10/ekf_errors.json), where it is not the one above"""
     path = os.environ.get("PK_FIGURES_JSON")
     if not path:
         return
     doc = json.load(open(path)) if os.path.exists(path) else {}
-    doc.setdefault("what", "worst errors of the float64 device primitives against mpmath / numpy.longdouble "
+    doc.setdefault("what", _what or "worst errors of the float64 device primitives against mpmath / numpy.longdouble "
                            "(tests/test_gpu_math_probe.py) and the resampler / pose sums at large particle counts "
                            "(tests/test_gpu_particle_edges.py), written by the tests: PK_FIGURES_JSON=<this file> pytest -m gpu <both>")
     doc["library_revision"], doc["host"], doc["card"] = _revision(), platform.node(), _card()

@@ -545,6 +545,7 @@ def test_probe_math_refusals(lib):
         ((0, lib.PK_MATH_PUB_RECIP, 3, None, op), lib.PK_ERR_INVALID, "NULL"),
         ((0, lib.PK_MATH_PUB_RECIP, 3, xp, None), lib.PK_ERR_INVALID, "NULL"),
         ((0, 8, 3, xp, op), lib.PK_ERR_INVALID, "unknown op"),
+        ((0, 11, 3, xp, op), lib.PK_ERR_INVALID, "unknown op"),  # PK_MATH_COUNT: the first op beyond the last
         ((0, -1, 3, xp, op), lib.PK_ERR_INVALID, "unknown op"),
         ((0, lib.PK_MATH_PUB_RECIP, -1, xp, op), lib.PK_ERR_INVALID, "n = -1"),
         ((-1, lib.PK_MATH_PUB_RECIP, 3, xp, op), lib.PK_ERR_INVALID, "device -1"),
@@ -563,6 +564,9 @@ def test_probe_math_refusals(lib):
     assert np.all(out == 7.0)
     assert lib.probe_math(lib.PK_MATH_KEY, np.zeros(0))[0].shape == (0,)
     assert lib.probe_math(lib.PK_MATH_FAR_BOUND, np.zeros((0, 14))).shape == (0, 2)
+    assert sorted(lib.PK_MATH_SHAPES) == [0, 1, 2, 3, 4, 5, 6, 7, 9, 10]  # (8 is refused for good, 11 is the first beyond the last)
+    assert lib.probe_math(lib.PK_MATH_EKF_UPDATE, np.zeros((0, 31))).shape == (0, 17)
+    assert lib.probe_math(lib.PK_MATH_MATCH, np.zeros((0, 23))).shape == (0, 5)
     with pytest.raises(lib.PkError) as ei:
         lib.probe_math(lib.PK_MATH_ATAN2, np.zeros((2, 2)), device=ndev)
     assert ei.value.status == lib.PK_ERR_INVALID

@@ -202,6 +202,28 @@ def test_device_noise_matches_numpy_philox_and_is_shard_invariant(lib):
     f.close()
 
 
+def test_device_noise_with_counters_beyond_32_bits(lib):
+    """The high counter words: a global particle index past 2^33 (word 1) and a draw index past 2^40 (word 3, whose top bit
+    tells the two Philox calls of one particle apart) -- the case above leaves both words 0."""
+    from oracle.fastslam_oracle import OracleFilter
+
+    P, seed, draw, offset = 300, 0x9E3779B97F4A7C15, 2 ** 40 + 3, 2 ** 33 + 5
+    f = lib.DeviceFilter(P, 1)
+    f.set_shard(offset)
+    f.motion(0.7, -0.3, 0.2, seed=seed, draw=draw)
+    got = f.download_poses()
+    f.close()
+    z = device_normals(P, seed, draw, offset=offset)
+    o = OracleFilter(P, [[1, 1, 1, 1, 1.0]], [np.identity(5)])
+    o.motion(0.7, -0.3, 0.2, z)
+    assert np.allclose(got[:, 0], o.x, rtol=1e-12, atol=1e-15)
+    assert np.allclose(got[:, 1], o.y, rtol=1e-12, atol=1e-15)
+    assert np.allclose(got[:, 2], o.h, rtol=1e-12, atol=1e-15)
+    # each high word matters: the same draws with either of them dropped are other numbers
+    for other in (device_normals(P, seed, draw, offset=5), device_normals(P, seed, 3, offset=offset), device_normals(P, seed, draw + 2 ** 32, offset=offset)):
+        assert not np.any(other == z)
+
+
 @pytest.mark.parametrize("ids_given", [False, True])
 def test_observe_fresh_equals_reset_then_observe(lib, ids_given):
     """pk_observe_fresh = pk_reset_weights + pk_observe (prkt_core_v2.py:73 fused into the kernels)."""
