@@ -247,6 +247,34 @@ int pk_grow_enable(pk_filter* f, int32_t preset_landmarks, int32_t reading_capac
 int pk_grow_download(pk_filter* f, int64_t p0, int64_t p1, int32_t* counters, double* readings, int32_t* slot_ids);
 int pk_grow_upload(pk_filter* f, int64_t p0, int64_t p1, const int32_t* counters, const double* readings, const int32_t* slot_ids);
 int pk_grow_shape(const pk_filter* f, int32_t* preset_landmarks, int32_t* spare_slots, int32_t* reading_capacity);
+/* Growing maps that also shrink (the reference's hypothesis_set and potential_features only grow; off by default, and a filter
+ * that never calls this does and holds what it did without it).  While a threshold is non-zero, one more kernel runs behind the
+ * bookkeeping of every non-empty maximum-likelihood scan.  t counts those scans (uint32, wrapping; ages are differences modulo 2^32).
+ * Per particle, in this order: (1) every spare slot the last pass knew whose count word changed since -- a match, a promotion --
+ * restarts its idle count, the others add one to it (saturating); (2) slots and readings that are new since the last pass, or were
+ * written by pk_grow_upload, are stamped: idle 0, scan t; (3) reading_max_age A > 0: the longest PREFIX of the ring whose readings
+ * are A scans old or older goes -- the ring is filled in time order; a stale reading behind a fresh one stays -- and the rest moves
+ * down to index 0; (4) potential_max_idle M > 0: the slots whose word carries PK_LANDMARK_POTENTIAL and that were idle for M passes
+ * go; the survivors move down in their order (rows, count word, slot id, clocks), and every vacated slot returns to the state of a
+ * spare slot that never held anything: mean (0, 0, 2^100, 2^100, 2^100), identity covariance, count word 0.  A promoted feature is
+ * never retired; next_id is untouched.  A feature made by scan t0 and never matched is gone at the end of scan t0 + M.
+ * 0 for a threshold: never.  The first call with a non-zero value allocates the clocks (pk_device_bytes) with nothing covered, so
+ * the next pass stamps what is there as new; later calls only change the thresholds, from the next pass on; (0, 0) frees the clocks.
+ * PK_ERR_STATE without pk_grow_enable; PK_ERR_INVALID for a negative value or one above 2^30.  While it is on, what moves particles
+ * between filters (pk_pack_particles, pk_adopt_particles, pk_shard_pack_* / pk_shard_adopt_*, the balanced ones included, and
+ * pk_shard_state_dev) returns PK_ERR_STATE: a record carries no clocks.  pk_resample and pk_resample_adaptive carry them along. */
+int pk_grow_retire(pk_filter* f, int32_t reading_max_age, int32_t potential_max_idle);
+/* The clocks of particles [p0, p1) while retirement is on (PK_ERR_STATE otherwise; any pointer may be NULL): counters[n][4] =
+ * readings covered by the last pass, spare slots covered, readings retired, features retired; reading_scan[n][reading_capacity] =
+ * the scan each stored reading was filed at; slot_seen[n][spare] / slot_idle[n][spare] = the count word of each spare slot in use at
+ * the last pass and the passes it has not changed for (rows beyond what is covered are undefined); *scan_now = t.  The upload
+ * takes the same (scan_now: the new t, NULL leaves it) and returns PK_ERR_INVALID where a particle's covered readings / slots exceed
+ * what it stores / uses.  pk_grow_upload on particles while retirement is on sets their two covered counts to 0: their clocks
+ * restart at the next pass, their retired counters stay. */
+int pk_grow_clocks_download(pk_filter* f, int64_t p0, int64_t p1, int32_t* counters, uint32_t* reading_scan, int32_t* slot_seen,
+                            int32_t* slot_idle, uint32_t* scan_now);
+int pk_grow_clocks_upload(pk_filter* f, int64_t p0, int64_t p1, const int32_t* counters, const uint32_t* reading_scan,
+                          const int32_t* slot_seen, const int32_t* slot_idle, const uint32_t* scan_now);
 
 /* FastSLAM.low_variance_resample (prkt_core_v2.py:210-252) with step = u * sum/P, u in
  * [0,1) standing for random.random() (:226).  ancestors_out: NULL or P int64. */

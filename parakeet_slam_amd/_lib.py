@@ -36,6 +36,7 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
 _bp = C.POINTER(C.c_uint8)
+_up = C.POINTER(C.c_uint32)
 _h = C.c_void_p
 
 # name -> (restype, argtypes); mirrors include/parakeet_slam.h one to one
@@ -144,6 +145,9 @@ SIGNATURES = {
     "pk_grow_download": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _dp, _ip]),
     "pk_grow_upload": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _dp, _ip]),
     "pk_grow_shape": (C.c_int, [_h, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pk_grow_retire": (C.c_int, [_h, C.c_int32, C.c_int32]),
+    "pk_grow_clocks_download": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _up, _ip, _ip, _up]),
+    "pk_grow_clocks_upload": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _up, _ip, _ip, _up]),
     "pk_observe_published": (C.c_int, [_h, C.POINTER(C.c_int32)]),
     "pk_observe_flags": (C.c_int, [_h, _bp]),
     "pk_observe_pub_stats": (C.c_int, [_h, _lp]),
@@ -695,6 +699,34 @@ class DeviceFilter(object):
         r = None if readings is None else f64(readings, (n, R, 8))
         s = None if slot_ids is None else np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(n, S)
         check(self._lib.pk_grow_upload(self._h, int(p0), int(p1), iptr(c), dptr(r), iptr(s)))
+
+    def grow_retire(self, reading_max_age=0, potential_max_idle=0):
+        """Retire readings older than ``reading_max_age`` scans and potential features unmatched for ``potential_max_idle`` scans,
+        behind every scan's bookkeeping (0: never; both 0: off, and the clocks' memory goes back)."""
+        check(self._lib.pk_grow_retire(self._h, int(reading_max_age), int(potential_max_idle)))
+
+    def grow_clocks_download(self, p0=0, p1=None):
+        """(counters (n, 4) int32: readings covered / slots covered / readings retired / features retired, reading_scan (n, R) uint32,
+        slot_seen (n, S) int32, slot_idle (n, S) int32, scan_now) while retirement is on."""
+        p1 = self.P if p1 is None else p1
+        _, S, R = self.grow_shape()
+        n = p1 - p0
+        c, sc = np.empty((n, 4), dtype=np.int32), np.empty((n, R), dtype=np.uint32)
+        se, si = np.empty((n, S), dtype=np.int32), np.empty((n, S), dtype=np.int32)
+        now = C.c_uint32(0)
+        check(self._lib.pk_grow_clocks_download(self._h, int(p0), int(p1), iptr(c), sc.ctypes.data_as(_up), iptr(se), iptr(si), C.byref(now)))
+        return c, sc, se, si, int(now.value)
+
+    def grow_clocks_upload(self, p0, p1, counters=None, reading_scan=None, slot_seen=None, slot_idle=None, scan_now=None):
+        _, S, R = self.grow_shape()
+        n = p1 - p0
+        c = None if counters is None else np.ascontiguousarray(counters, dtype=np.int32).reshape(n, 4)
+        sc = None if reading_scan is None else np.ascontiguousarray(reading_scan, dtype=np.uint32).reshape(n, R)
+        se = None if slot_seen is None else np.ascontiguousarray(slot_seen, dtype=np.int32).reshape(n, S)
+        si = None if slot_idle is None else np.ascontiguousarray(slot_idle, dtype=np.int32).reshape(n, S)
+        now = None if scan_now is None else C.byref(C.c_uint32(int(scan_now) & 0xFFFFFFFF))
+        check(self._lib.pk_grow_clocks_upload(self._h, int(p0), int(p1), iptr(c), None if sc is None else sc.ctypes.data_as(_up), iptr(se),
+                                              iptr(si), now))
 
     def observe_retry_rows(self):
         """(second-chance rows the last scan wanted, rows the next scan will find) -- pk_observe_retry_rows."""

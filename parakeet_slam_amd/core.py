@@ -544,6 +544,9 @@ class FastSLAM(object):
     the default: one kernel behind every observe, pk_grow_enable; each particle keeps up to ``reading_capacity`` orphaned
     readings in HBM, ``readings_dropped()`` counts what did not fit) -- nothing per particle crosses to the host in a step;
     bookkeeping="host" is the per-particle host loop of the reference (and the only one on the dense layout).
+    ``reading_max_age=A`` / ``potential_max_idle=M`` (device bookkeeping, one GPU; 0: never, the default): behind every scan's
+    bookkeeping each particle drops the readings at the head of its ring that are A scans old or older and retires the potential
+    features that went unmatched for M scans, whose spare slots are free again (pk_grow_retire); ``retired()`` counts both.
     ``record_ids`` (default: only with bookkeeping="host"): keep ``last_ids`` / ``last_ancestors`` of every step.
 
     record_path=T (default 0: off): every resample records the generation it worked on and its ancestors in a ring of the last
@@ -589,6 +592,9 @@ class FastSLAM(object):
             if a["resample_threshold"] is not None:
                 raise ValueError("FastSLAM(devices=[...], resample_threshold=...): adaptive resampling is for one GPU -- the "
                                  "verdict of a sharded filter needs its weight sums all-reduced, which is out of scope")
+            if a["reading_max_age"] or a["potential_max_idle"]:
+                raise ValueError("FastSLAM(devices=[...], reading_max_age=... / potential_max_idle=...): readings and features are "
+                                 "retired on one GPU only -- a particle's record carries no clocks from one rank to another")
             return ShardedFastSLAM(a["preset_features"], num_particles=a["num_particles"], devices=list(devices),
                                    weight_domain=a["weight_domain"], rng=a["rng"], seed=a["seed"],
                                    publish_debug=a["publish_debug"], new_landmarks=a["new_landmarks"],
@@ -600,9 +606,17 @@ class FastSLAM(object):
 
     def __init__(self, preset_features=[], num_particles=50, device=0, weight_domain="linear", rng="global",
                  seed=0, publish_debug=None, new_landmarks=False, spare_landmarks=0, pair_threshold=30.0, devices=None,
-                 bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None):
+                 bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
+                 reading_max_age=0, potential_max_idle=0):
         if devices is not None and len(list(devices)) == 1:
             device = list(devices)[0]
+        self._retire = (int(reading_max_age), int(potential_max_idle))
+        if min(self._retire) < 0:
+            raise ValueError("reading_max_age and potential_max_idle must be numbers of scans >= 0")
+        if any(self._retire) and not (new_landmarks and int(spare_landmarks) > 0 and bookkeeping == "device"):
+            raise ValueError("FastSLAM(reading_max_age=... / potential_max_idle=...): readings and features are retired by the device "
+                             "bookkeeping of a growing map (new_landmarks=True, spare_landmarks > 0, bookkeeping='device'), not by "
+                             "bookkeeping='host'")
         self._threshold = None if resample_threshold is None else adaptive.threshold_value(resample_threshold)
         self._lock = threading.RLock()
         self.last_control = Twist()
@@ -642,6 +656,8 @@ class FastSLAM(object):
                     raise
                 self._filter.close()
                 raise ValueError("%s -- FastSLAM(..., bookkeeping='host') keeps the new-landmark bookkeeping on the host, on any layout" % e)
+            if any(self._retire):
+                self._filter.grow_retire(*self._retire)
         else:
             self._nl_host = dict(
                 hyp=[[] for _ in range(P)],          # orphaned readings: (id, x, y, heading, bearing, r, g, b)  (:739-746)
@@ -721,6 +737,14 @@ class FastSLAM(object):
         if not self._nl_device:
             return 0
         return int(self._filter.grow_download(readings=False, slot_ids=False)[0][:, 3].sum())
+
+    def retired(self):
+        """(readings, features) retired so far, summed over the particles (reading_max_age / potential_max_idle; (0, 0) without)."""
+        if not any(self._retire):
+            return 0, 0
+        with self._lock:
+            c = self._filter.grow_clocks_download()[0]
+        return int(c[:, 2].sum()), int(c[:, 3].sum())
 
     def _poses(self):
         if self._pose_cache is None:
@@ -1041,6 +1065,12 @@ class FastSLAM(object):
             extra = {}
             if self._nl_device:
                 extra = _nl_snapshot_arrays(*self._filter.grow_download(), L0=self._L0)
+                if any(self._retire):  # the clocks of the retirement rule, whole (rows beyond what a particle holds: zeroed)
+                    kc, sc, se, si, now = self._filter.grow_clocks_download()
+                    sc[np.arange(sc.shape[1])[None, :] >= kc[:, :1]] = 0
+                    se[np.arange(se.shape[1])[None, :] >= kc[:, 1:2]] = 0
+                    si[np.arange(si.shape[1])[None, :] >= kc[:, 1:2]] = 0
+                    extra.update(nl_clock_counters=kc,nl_clock_scan=sc, nl_clock_seen=se, nl_clock_idle=si, nl_clock_now=np.uint32(now))
             elif self._grow:
                 extra = _nl_snapshot(self._nl())
             if self._threshold is not None:  # the weights carry over: bit for bit, not through exp and log
@@ -1078,6 +1108,16 @@ class FastSLAM(object):
                 raise ValueError("snapshot: log_weights must be %d numbers below +inf" % P)
             if have_nl:  # everything is checked before anything is assigned
                 _nl_check_snapshot(d, P, self._L0, L, self._spare, self._filter.grow_shape()[2] if self._nl_device else None)
+            # (a snapshot without the clocks, or a filter that retires nothing: pk_grow_upload restarts them / they are not read)
+            have_clocks = have_nl and self._nl_device and any(self._retire) and "nl_clock_counters" in d.files
+            if have_clocks:
+                _, S, R = self._filter.grow_shape()
+                kc = d["nl_clock_counters"]
+                if (kc.shape != (P, 4) or d["nl_clock_scan"].shape != (P, R) or d["nl_clock_seen"].shape != (P, S)
+                        or d["nl_clock_idle"].shape != (P, S) or (kc < 0).any()
+                        or (kc[:, 0] > np.diff(d["nl_offsets"])).any() or (kc[:, 1] > d["nl_used"]).any()):
+                    raise ValueError("snapshot: the retirement clocks (nl_clock_*) do not fit this filter's %d particles, rings of %d "
+                                     "readings and %d spare slots, or cover more than a particle holds" % (P, R, S))
 
             self._filter.upload_poses(d["poses"])
             if have_logw:  # (a snapshot without them: log(weight), as upload_poses took it)
@@ -1091,6 +1131,9 @@ class FastSLAM(object):
             if have_nl and self._nl_device:
                 _, S, R = self._filter.grow_shape()
                 self._filter.grow_upload(0, P, *_nl_arrays_from_snapshot(d, P, self._L0, S, R))
+                if have_clocks:
+                    self._filter.grow_clocks_upload(0, P, d["nl_clock_counters"], d["nl_clock_scan"], d["nl_clock_seen"],
+                                                    d["nl_clock_idle"], int(d["nl_clock_now"]))
             elif have_nl:
                 self._nl_assign(*_nl_restore(d, P))
             if have_path:  # (behind upload_poses, which empties the ring; a snapshot without a path leaves it empty)

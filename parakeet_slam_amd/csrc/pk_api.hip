@@ -711,6 +711,7 @@ int pk_resample(pk_filter* f, double u, int32_t weight_domain, int64_t* ancestor
       launch_ancestors(f->stream, f->clocal, f->totals, f->offsets, f->sum, f->nblocks, d.P, d.P, u, 0, d.P, f->anc, &d);
     }
   }
+  if (f->retire.on()) launch_retire_gather(f->stream, f->grow, f->retire, f->anc, d.P);  // (pk_grow_retire: the clocks too)
   if (f->grow_on) launch_grow_gather(f->stream, f->grow, f->anc, d.P);  // the bookkeeping follows the particles (:243)
   if (f->path.cap && (rc = path_record(f))) return rc;  // the generation that was resampled and its ancestors, into the ring
   PK_LAUNCH_CHECK("pk_resample");
@@ -964,6 +965,7 @@ int pk_grow_upload(pk_filter* f, int64_t p0, int64_t p1, const int32_t* counters
   if (counters) PK_HIP(hipMemcpyAsync(g.cnt[g.cur] + 4 * p0, counters, n * 16, hipMemcpyHostToDevice, f->stream));
   if (readings) PK_HIP(hipMemcpyAsync(g.hyp[g.cur] + (size_t)p0 * g.R * 8, readings, n * g.R * 64, hipMemcpyHostToDevice, f->stream));
   if (slot_ids) PK_HIP(hipMemcpyAsync(g.slot_id[g.cur] + (size_t)p0 * g.S, slot_ids, n * g.S * 4, hipMemcpyHostToDevice, f->stream));
+  if (f->retire.on() && (rc = retire_restart(f, p0, p1))) return rc;  // (pk_grow_retire: what was written is new to the next pass)
   PK_HIP(hipStreamSynchronize(f->stream));
   return PK_OK;
 }

@@ -79,6 +79,7 @@ int pk_resample_adaptive(pk_filter* f, double u, int32_t weight_domain, double t
                            f->nblocks, u, threshold, words + kAdShift, f->anc, d, f->ad_out);
   }
   ++f->ad_calls;
+  if (f->retire.on()) launch_retire_gather(f->stream, f->grow, f->retire, f->anc, d.P);  // (pk_grow_retire: the clocks too)
   if (f->grow_on) launch_grow_gather(f->stream, f->grow, f->anc, d.P);  // by the ancestors: the identity when the call kept
   if (f->path.cap && (rc = path_record(f))) return rc;                   // one ring row per call, kept or not
   PK_LAUNCH_CHECK("pk_resample_adaptive");

@@ -76,6 +76,14 @@ int refuse_path(const pk_filter* f, const char* who) {
   return PK_OK;
 }
 
+// The clocks of the retirement rule (pk_grow_retire) do not travel in a record's tail: whatever moves particles between filters is
+// refused while it is on, ahead of every other step (a NULL handle passes: the check that follows refuses it).
+int refuse_retire(const pk_filter* f, const char* who) {
+  if (f && f->retire.on())
+    return fail(PK_ERR_STATE, "%s: readings and features are being retired (pk_grow_retire): the record carries no clocks; switch it off with pk_grow_retire(f, 0, 0) first", who);
+  return PK_OK;
+}
+
 extern "C" {
 
 // ---- sharded resampling ---------------------------------------
@@ -138,6 +146,7 @@ static size_t record_stride(const pk_filter* f) { return kPoseRecordBytes + f->d
 int64_t pk_particle_bytes(const pk_filter* f) { return f ? (int64_t)record_stride(f) : -1; }
 
 int pk_pack_particles(pk_filter* f, const int64_t* local_idx, int64_t n, void* dev_buf) {
+  if (int rc = refuse_retire(f, "pk_pack_particles")) return rc;
   if (int rc = refuse_path(f, "pk_pack_particles")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (!f || n < 0 || (n > 0 && (!local_idx || !dev_buf))) return fail(PK_ERR_INVALID, "pk_pack_particles: bad argument");
@@ -161,6 +170,7 @@ int pk_pack_particles(pk_filter* f, const int64_t* local_idx, int64_t n, void* d
 }
 
 int pk_adopt_particles(pk_filter* f, const int64_t* src, const void* dev_buf, int64_t n_received) {
+  if (int rc = refuse_retire(f, "pk_adopt_particles")) return rc;
   if (int rc = refuse_path(f, "pk_adopt_particles")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   poses_change(f);
@@ -288,6 +298,7 @@ int pk_shard_download_offspring(pk_filter* f, int64_t* slot_hi) {
 }
 
 int pk_shard_pack_dev(pk_filter* f, const int64_t* ranges, int32_t world, int32_t rank, void* dev_buf) {
+  if (int rc = refuse_retire(f, "pk_shard_pack_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (int rc = refuse_grow(f, "pk_shard_pack_dev")) return rc;
   if (!f || !ranges || world < 1 || rank < 0 || rank >= world) return fail(PK_ERR_INVALID, "pk_shard_pack_dev: bad argument");
@@ -311,6 +322,7 @@ int pk_shard_pack_dev(pk_filter* f, const int64_t* ranges, int32_t world, int32_
 }
 
 int pk_shard_pack_slots_dev(pk_filter* f, int64_t j0, int64_t j1, int64_t slot_lo, int64_t slot_hi, void* dev_buf) {
+  if (int rc = refuse_retire(f, "pk_shard_pack_slots_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (int rc = refuse_grow(f, "pk_shard_pack_slots_dev")) return rc;
   if (!f || j0 < 0 || j1 < j0 || j1 > f->d.P || slot_hi < slot_lo) return fail(PK_ERR_INVALID, "pk_shard_pack_slots_dev: bad argument");
@@ -325,6 +337,7 @@ int pk_shard_pack_slots_dev(pk_filter* f, int64_t j0, int64_t j1, int64_t slot_l
 }
 
 int pk_shard_adopt_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t n_received) {
+  if (int rc = refuse_retire(f, "pk_shard_adopt_dev")) return rc;
   if (int rc = refuse_path(f, "pk_shard_adopt_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (int rc = refuse_grow(f, "pk_shard_adopt_dev")) return rc;
@@ -345,6 +358,7 @@ int pk_shard_adopt_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t
 }
 
 int pk_shard_adopt_local_dev(pk_filter* f, int32_t rank) {
+  if (int rc = refuse_retire(f, "pk_shard_adopt_local_dev")) return rc;
   if (int rc = refuse_path(f, "pk_shard_adopt_local_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (int rc = refuse_grow(f, "pk_shard_adopt_local_dev")) return rc;
@@ -366,6 +380,7 @@ int pk_shard_adopt_local_dev(pk_filter* f, int32_t rank) {
 }
 
 int pk_shard_adopt_remote_dev(pk_filter* f, int32_t rank, const void* dev_recv, int64_t n_received) {
+  if (int rc = refuse_retire(f, "pk_shard_adopt_remote_dev")) return rc;
   if (int rc = refuse_path(f, "pk_shard_adopt_remote_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (int rc = refuse_grow(f, "pk_shard_adopt_remote_dev")) return rc;
@@ -470,6 +485,7 @@ int pk_shard_download_balanced_plan(pk_filter* f, int64_t* rel, int64_t* Hl, int
 }
 
 int pk_shard_state_dev(pk_filter* f, double* dev_out) {
+  if (int rc = refuse_retire(f, "pk_shard_state_dev")) return rc;
   if (int rc = refuse_path(f, "pk_shard_state_dev")) return rc;
   if (!f || !dev_out) return fail(PK_ERR_INVALID, "pk_shard_state_dev: NULL argument");
   int rc;
@@ -546,6 +562,7 @@ static int balanced_row_check(const int64_t* table, int world, int64_t P, const 
 }
 
 int pk_shard_pack_balanced_dev(pk_filter* f, const int64_t* table, int32_t world, int32_t rank, void* dev_buf) {
+  if (int rc = refuse_retire(f, "pk_shard_pack_balanced_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (!f || !table || world < 1 || world > 64 || rank < 0 || rank >= world) return fail(PK_ERR_INVALID, "pk_shard_pack_balanced_dev: bad argument");
   if (int rc = need_balanced_plan(f, "pk_shard_pack_balanced_dev")) return rc;
@@ -576,6 +593,7 @@ int pk_shard_pack_balanced_dev(pk_filter* f, const int64_t* table, int32_t world
  * ITSELF -- the children from position `keep` on, destined for its own slots [keep, P): what k_bal_pack writes for another rank whose
  * free slots are [keep, P), with the 64-byte balanced header (and the new-landmark bookkeeping behind the map while that is on). */
 int pk_shard_pack_balanced_loop_dev(pk_filter* f, int64_t keep, int64_t a0, int64_t a1, void* dev_buf) {
+  if (int rc = refuse_retire(f, "pk_shard_pack_balanced_loop_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   if (!f || keep < 0 || keep > f->d.P || a0 < 0 || a1 < a0 || a1 > f->d.P || (a1 > a0 && !dev_buf))
     return fail(PK_ERR_INVALID, "pk_shard_pack_balanced_loop_dev: bad argument");
@@ -593,6 +611,7 @@ int pk_shard_pack_balanced_loop_dev(pk_filter* f, int64_t keep, int64_t a0, int6
 
 int pk_shard_adopt_balanced_dev(pk_filter* f, const int64_t* table, int32_t world, int32_t rank, const void* dev_recv,
                                 int64_t n_received, int32_t mode) {
+  if (int rc = refuse_retire(f, "pk_shard_adopt_balanced_dev")) return rc;
   if (int rc = refuse_path(f, "pk_shard_adopt_balanced_dev")) return rc;
   if (int rc = ct_shard_call(f)) return rc;
   poses_change(f);

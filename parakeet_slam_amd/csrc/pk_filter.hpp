@@ -360,6 +360,7 @@ struct pk_filter {
   int64_t ad_calls = 0;             // gated calls enqueued (pk_resample_stats: 0 -> nothing to report)
   GrowState grow{};                 // section 8(f4) on the device (pk_grow_enable): per-particle new-landmark bookkeeping
   bool grow_on = false;
+  RetireState retire{};             // pk_grow_retire (pk_api_retire.hip): the clocks of the retirement rule -- nothing until it is switched on
   int32_t* anc = nullptr;           // P
   unsigned char* slot_tmp = nullptr;  // one slot
   // timing
@@ -483,6 +484,9 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
 // pk_api_shard.hip
 int refuse_balanced(const pk_filter* f, const char* who);
 int refuse_path(const pk_filter* f, const char* who);
+int refuse_retire(const pk_filter* f, const char* who);
+// pk_api_retire.hip
+int retire_restart(pk_filter* f, int64_t p0, int64_t p1);  // pk_grow_upload wrote these particles: their clocks restart
 // pk_api_path.hip
 int path_record(pk_filter* f);  // behind pk_resample's kernels while the ring is on
 inline void path_clear(pk_filter* f) {  // the history ends: the population was replaced

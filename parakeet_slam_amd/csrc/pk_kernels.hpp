@@ -51,6 +51,17 @@ struct GrowState {
 // the bookkeeping of one particle behind its record in the sharded exchange: counters (16 B) | slot ids | readings
 __host__ __device__ inline size_t grow_tail_readings_off(int S) { return 16 + (((size_t)S * 4 + 15) & ~(size_t)15); }
 inline size_t grow_tail_bytes(const GrowState& g) { return g.R > 0 ? grow_tail_readings_off(g.S) + (size_t)g.R * 64 : 0; }
+// retirement of stale readings and unconfirmed features (pk_grow_retire; pk_k_grow_retire.hip): the per-particle clocks, beside
+// GrowState's arrays and double-buffered with them (GrowState::cur indexes both).  Nothing is allocated until it is switched on.
+struct RetireState {
+  uint32_t* scan[2] = {nullptr, nullptr};  // [P][R] the scan at which every stored reading was filed
+  int32_t* seen[2] = {nullptr, nullptr};   // [P][S] count word of every spare slot in use at the last pass
+  int32_t* idle[2] = {nullptr, nullptr};   // [P][S] consecutive passes it did not change
+  int32_t* cnt[2] = {nullptr, nullptr};    // [P][4]: covered readings, covered slots, readings retired, features retired
+  uint32_t t = 0;                          // scans that ran the bookkeeping since retirement was switched on (wraps)
+  int A = 0, M = 0;                        // reading_max_age, potential_max_idle (0: never)
+  bool on() const { return cnt[0] != nullptr; }
+};
 
 // Where the landmark slot of a particle lives: its own map buffer or the adoption buffer.
 struct SlotSource {
@@ -546,6 +557,10 @@ void launch_new_landmarks(hipStream_t s, DeviceState& d, GrowState& g, const int
 // anc >= 0: a particle of this filter; anc < 0: record -anc - 1 of buf (stride bytes apart, its bookkeeping tail_off bytes in)
 void launch_grow_gather(hipStream_t s, GrowState& g, const int32_t* anc_dev, int64_t P, const unsigned char* buf_dev = nullptr,
                         size_t stride = 0, size_t tail_off = 0);
+// behind launch_new_landmarks while retirement is on (r.t already counts this scan): every particle's slot is its own
+void launch_grow_retire(hipStream_t s, DeviceState& d, const GrowState& g, const RetireState& r);
+// the clocks by the same ancestors, into the buffers launch_grow_gather makes current: BEFORE it (it flips g.cur)
+void launch_retire_gather(hipStream_t s, const GrowState& g, const RetireState& r, const int32_t* anc_dev, int64_t P);
 // scan block: pinned (device-mapped) host memory -> HBM by a kernel, in stream order
 void launch_upload(hipStream_t s, void* dst_dev, const void* src_host_mapped, size_t bytes);
 
