@@ -348,7 +348,8 @@ int pk_map_discovered(pk_filter* f, int32_t weighting, int64_t reference_particl
  *   poses      x, y, heading of all P particles of the generation that was just resampled (the pose at which the scan was
  *              applied, after every motion update since the last resample), float64;
  *   ancestors  anc[k] = the index IN THAT GENERATION of the parent of particle k of the new generation, int32.
- * A full ring overwrites its oldest row; `recorded` counts the rows ever recorded.  capacity 0 switches recording off and
+ * A full ring overwrites its oldest row (unless a trunk takes the oldest rows first: pk_path_trunk_enable, below); `recorded`
+ * counts the rows ever recorded.  capacity 0 switches recording off and
  * releases the memory; any pk_path_enable starts from an empty ring.  Off is the default: a step then launches what it always did.
  * Row convention everywhere: rows 0 .. held - 1 are the recorded steps, oldest first; row `held` is the CURRENT generation.
  * The lineage of a current particle k: j_held = k, j_t = anc_t[j_{t + 1}]; its path is pose_t[j_t], then its current pose.
@@ -393,6 +394,59 @@ int pk_path_trace(pk_filter* f, const int64_t* particles, int64_t n, double* out
 int pk_path_summary(pk_filter* f, double* mean, double* spread, int64_t* survivors);
 int pk_path_summary_weighted(pk_filter* f, int32_t weight_domain, double* mean, double* spread, double* n_eff);
 int pk_best_particle(pk_filter* f, int64_t* index, double* log_weight);
+
+/* ---- the trunk: the whole run's path in bounded memory ("The trunk") ----------------------------------
+ * A full ring overwrites its oldest row, and with it the start of the run.  With a trunk, a row's estimate is SETTLED into one
+ * record of 13 doubles on the device before the row leaves the ring; the filter's whole path is then the trunk, the ring, the
+ * current generation.  Off by default: a filter that does not ask for it holds, launches and returns what it always did.
+ *   lo_t, hi_t   the lowest and highest lineage index j_t(k) of row t over ALL current particles, whatever their weight.  The
+ *                row is FINAL iff lo_t == hi_t: every current particle descends from that one ancestor, and no later step can
+ *                change the row's pose, pose_t[lo_t].  The final rows are a prefix of the ring.
+ *   a trunk row  doubles 0-7: mean x, mean y, sum w sin h, sum w cos h, var x, cov xy, var y, S1 -- the row's estimate by the
+ *                current particles' weights at the moment it was settled, bit for bit the numbers pk_path_summary_weighted
+ *                takes for that row (the same weights, reference pose and order of every sum); 8, 9: lo_t, hi_t (exact);
+ *                10-12: x, y, heading of pose_t[lo_t] as recorded.  It stands at global step index first_step + t, first_step =
+ *                recorded - held of the ring at that moment.
+ *   weighting    PK_WEIGHTS_LINEAR, PK_WEIGHTS_LOG, or PK_PATH_UNIFORM: every current particle counts once, w = 1.0 (the sums
+ *                of PK_WEIGHTS_LOG with every log-weight 0).  Weights that sum to nothing leave NaN in doubles 0-7 of the rows
+ *                that are not final; lo, hi and the pose are exact regardless.  Settling reads nothing back and refuses nothing
+ *                on that account.
+ * Settling E rows drops them from the ring (held -= E; `recorded` stays) and writes nothing else of the filter.  While the trunk
+ * is on, trunk first_step + length == ring recorded - held at all times.  Five launches whatever the ring holds (the maximum
+ * log-weight for PK_WEIGHTS_LOG, particle 0's lineage, the walk by index down to row E, the reduction of rows E - 1 .. 0, the
+ * fold), no floating-point atomics, no host round trip.  The trunk's rows start at max(4 batch, 1024) and grow by doubling
+ * (allocate, device-to-device copy, free): that is the ONLY synchronisation a settling step can ever meet.  All of it is counted
+ * in pk_device_bytes; the scratch is pk_path_summary_weighted's, reserved by pk_path_trunk_enable.
+ *   pk_path_trunk_enable    batch in [1, capacity] switches the trunk on: from then on the record that fills the ring (held ==
+ *                     capacity behind it) settles the oldest `batch` rows at once, in the PK_T_RESAMPLE span, so that between
+ *                     calls the ring holds capacity - batch .. capacity - 1 rows and overwrites nothing.  Behind pk_resample /
+ *                     pk_step the weighting is PK_PATH_UNIFORM (behind a resample the population is the estimate); behind
+ *                     pk_resample_adaptive / pk_step_adaptive it is that call's weight domain over the NEW generation's
+ *                     log-weights (0 after a resample, carried over after a kept step: the verdict stays on the device).  A
+ *                     ring that is full already stays full: pk_path_settle makes room, or else the next record first settles
+ *                     `batch` rows by the generation it is about to record, every particle once (its lineages include the new
+ *                     generation's: what is reported final is final).  batch 0 switches off and releases;
+ *                     PK_ERR_STATE without a ring, PK_ERR_INVALID outside [0, capacity].  pk_path_enable (any capacity)
+ *                     starts without a trunk; pk_upload_poses empties it and sets its first_step to `recorded`.
+ *   pk_path_settle    the explicit form: settles held rows 0 .. rows - 1 by `weighting`.  PK_ERR_INVALID for rows outside
+ *                     [0, held] or a bad weighting; rows == 0 is fine and launches nothing.
+ *   pk_path_trunk_shape     batch, first_step, length.  Any output may be NULL.
+ *   pk_path_trunk_download  the raw rows of global steps [s0, s1): rows[s1 - s0][13] -- what a snapshot carries.
+ *   pk_path_trunk_upload    replaces the trunk by n rows from first_step on and sets recorded = first_step + n.  Only while the
+ *                     ring holds no rows (PK_ERR_STATE otherwise); lo <= hi, both whole and in [0, P), else PK_ERR_INVALID.
+ *   pk_path_trunk_summary   steps [s0, s1), n = s1 - s0, host arithmetic: mean[n][3], spread[n][4] in pk_path_summary_weighted's
+ *                     convention, ancestors[n][2] = lo, hi.  A final row: the mean is doubles 10-12 as recorded, the spread
+ *                     (0, 0, 0, 1).  Any output may be NULL.
+ * With the trunk on, pk_path_upload must continue it: an empty trunk takes first_step = recorded - n, otherwise recorded - n must
+ * equal the trunk's end (PK_ERR_INVALID, nothing changed); n == capacity settles `batch` rows at once, uniformly.  Every call here
+ * but pk_path_trunk_enable is PK_ERR_STATE while the trunk is off. */
+#define PK_PATH_UNIFORM 2
+int pk_path_trunk_enable(pk_filter* f, int32_t batch);
+int pk_path_settle(pk_filter* f, int32_t rows, int32_t weighting);
+int pk_path_trunk_shape(const pk_filter* f, int32_t* batch, int64_t* first_step, int64_t* length);
+int pk_path_trunk_download(pk_filter* f, int64_t s0, int64_t s1, double* rows);
+int pk_path_trunk_upload(pk_filter* f, int64_t first_step, int64_t n, const double* rows);
+int pk_path_trunk_summary(pk_filter* f, int64_t s0, int64_t s1, double* mean, double* spread, int64_t* ancestors);
 
 /* One whole cam_cb without host synchronisation: reset weights, motion, observe,
  * resample.  Arguments as in the calls above. */

@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(HERE, "libparakeet_slam.so")
 PK_OK = 0
 PK_ERR_INVALID, PK_ERR_HIP, PK_ERR_STATE, PK_ERR_UNSUPPORTED, PK_ERR_NOMEM = -1, -2, -3, -4, -5
 PK_WEIGHTS_LINEAR, PK_WEIGHTS_LOG = 0, 1
+PK_PATH_UNIFORM = 2  # pk_path_settle's third weighting: every current particle counts once
 PK_MAP_UNIFORM, PK_MAP_WEIGHTED = mapsum.UNIFORM, mapsum.WEIGHTED
 PK_LANDMARK_POTENTIAL = 0x40000000  # flag in a landmark's count word: potential feature (prkt_core_v2.py:109-118)
 PK_T_NAMES = ("motion", "assoc", "observe", "weights", "resample", "summary", "materialise")
@@ -84,6 +85,12 @@ SIGNATURES = {
     "pk_path_trace": (C.c_int, [_h, _lp, C.c_int64, _dp]),
     "pk_path_summary": (C.c_int, [_h, _dp, _dp, _lp]),
     "pk_path_summary_weighted": (C.c_int, [_h, C.c_int32, _dp, _dp, _dp]),
+    "pk_path_trunk_enable": (C.c_int, [_h, C.c_int32]),
+    "pk_path_settle": (C.c_int, [_h, C.c_int32, C.c_int32]),
+    "pk_path_trunk_shape": (C.c_int, [_h, C.POINTER(C.c_int32), _lp, _lp]),
+    "pk_path_trunk_download": (C.c_int, [_h, C.c_int64, C.c_int64, _dp]),
+    "pk_path_trunk_upload": (C.c_int, [_h, C.c_int64, C.c_int64, _dp]),
+    "pk_path_trunk_summary": (C.c_int, [_h, C.c_int64, C.c_int64, _dp, _dp, _lp]),
     "pk_best_particle": (C.c_int, [_h, _lp, _dp]),
     "pk_step": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32,
                           _ip, C.c_double, C.c_int32]),
@@ -456,6 +463,45 @@ class DeviceFilter(object):
         mean, spread, n_eff = np.empty((held + 1, 3)), np.empty((held + 1, 4)), np.empty(1)
         check(self._lib.pk_path_summary_weighted(self._h, int(domain), dptr(mean), dptr(spread), dptr(n_eff)))
         return path.WeightedPathSummary(mean, spread, n_eff[0], recorded - held)
+
+    # -- the trunk (pk_path_trunk_*): the rows the ring has given up, 13 doubles each, at global steps first_step ..
+    def path_trunk_enable(self, batch):
+        """Settle the oldest ``batch`` rows into the trunk whenever a record fills the ring (0: off, memory released)."""
+        check(self._lib.pk_path_trunk_enable(self._h, int(batch)))
+
+    def path_settle(self, rows, weighting=PK_PATH_UNIFORM):
+        """Settle the oldest ``rows`` held rows now, by PK_WEIGHTS_LINEAR / PK_WEIGHTS_LOG / PK_PATH_UNIFORM."""
+        check(self._lib.pk_path_settle(self._h, int(rows), int(weighting)))
+
+    def path_trunk_shape(self):
+        """(batch, first_step, length)."""
+        a, b, c = C.c_int32(), C.c_int64(), C.c_int64()
+        check(self._lib.pk_path_trunk_shape(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def _trunk_range(self, s0, s1):
+        _, first, n = self.path_trunk_shape()
+        return (first if s0 is None else int(s0)), (first + n if s1 is None else int(s1))
+
+    def path_trunk_download(self, s0=None, s1=None):
+        """The raw trunk rows of global steps [s0, s1) (default: all), (n, 13): what a snapshot carries."""
+        s0, s1 = self._trunk_range(s0, s1)
+        rows = np.empty((max(s1 - s0, 0), path.TRUNK_RES), dtype=np.float64)
+        check(self._lib.pk_path_trunk_download(self._h, s0, s1, dptr(rows)))
+        return rows
+
+    def path_trunk_upload(self, rows, first_step=0):
+        """Replaces the trunk by ``rows`` (n, 13) from ``first_step`` on; only while the ring holds no rows."""
+        r = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, path.TRUNK_RES)
+        check(self._lib.pk_path_trunk_upload(self._h, int(first_step), r.shape[0], dptr(r)))
+
+    def path_trunk_summary(self, s0=None, s1=None):
+        """(mean (n, 3), spread (n, 4), ancestors (n, 2) int64 = lo, hi) of the trunk's steps [s0, s1) (default: all)."""
+        s0, s1 = self._trunk_range(s0, s1)
+        n = max(s1 - s0, 0)
+        mean, spread, anc = np.empty((n, 3)), np.empty((n, 4)), np.empty((n, 2), dtype=np.int64)
+        check(self._lib.pk_path_trunk_summary(self._h, s0, s1, dptr(mean), dptr(spread), lptr(anc)))
+        return mean, spread, anc
 
     def best_particle(self):
         """(index, log-weight) of the particle with the largest log-weight: the lowest index among equals, NaN never."""

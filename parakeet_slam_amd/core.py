@@ -26,6 +26,7 @@ import threading
 import numpy as np
 
 from . import _lib, adaptive, mapsum, msgs
+from . import path as _path
 from .msgs import Blob, Odometry, Twist, heading_to_quaternion, quaternion_to_heading
 
 NO_MATCH_WEIGHT = 0.1  # prkt_core_v2.py:851-857
@@ -554,6 +555,9 @@ class FastSLAM(object):
     surviving lineages with the number of distinct ancestors left per step, ``particle_paths(indices)`` the paths of single
     particles, ``path_summary(weighting="weights")`` the path by the particles' weights (between the resamples of an adaptively
     resampled filter) and ``best_path()`` that of the most likely particle.  One GPU only: with devices=[several] it is refused.
+    settle_path=E (default None: off; True: max(1, T // 4)): the ring never overwrites -- the record that fills it settles its
+    oldest E rows into a trunk of 104 bytes per step on the device (pk_path_trunk_enable), and ``full_path()`` is the path of the
+    whole run, trunk, ring and current generation, in bounded memory.  Needs record_path, E <= T.
 
     resample_threshold=theta (default None: resample behind every scan, as the reference does): adaptive resampling -- the
     filter resamples only when the effective sample size of its weights falls below theta * num_particles, decided on the device
@@ -586,6 +590,9 @@ class FastSLAM(object):
                                  "(bookkeeping='device'): host lists cannot follow a particle from one GPU to another")
             if a["device"] not in (0, list(devices)[0]):
                 raise ValueError("FastSLAM: give either device= or devices=, not both")
+            if a["settle_path"]:
+                raise ValueError("FastSLAM(devices=[...], settle_path=...): the path is recorded and settled on one GPU only -- "
+                                 "lineages across ranks are out of scope")
             if a["record_path"]:
                 raise ValueError("FastSLAM(devices=[...], record_path=...): the path is recorded on one GPU only -- lineages "
                                  "across ranks are out of scope (the sharded resample is refused on a recording filter)")
@@ -607,7 +614,7 @@ class FastSLAM(object):
     def __init__(self, preset_features=[], num_particles=50, device=0, weight_domain="linear", rng="global",
                  seed=0, publish_debug=None, new_landmarks=False, spare_landmarks=0, pair_threshold=30.0, devices=None,
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
-                 reading_max_age=0, potential_max_idle=0):
+                 reading_max_age=0, potential_max_idle=0, settle_path=None):
         if devices is not None and len(list(devices)) == 1:
             device = list(devices)[0]
         self._retire = (int(reading_max_age), int(potential_max_idle))
@@ -669,8 +676,15 @@ class FastSLAM(object):
         if self._record_path < 0:
             self._filter.close()
             raise ValueError("record_path must be a number of steps >= 0")
+        self._settle_path = max(1, self._record_path // 4) if settle_path is True else int(settle_path or 0)
+        if self._settle_path < 0 or (self._settle_path and not self._record_path) or self._settle_path > self._record_path:
+            self._filter.close()
+            raise ValueError("settle_path=%r: a number of rows in [1, record_path] of a filter that records its path "
+                             "(record_path=%d), True, or None" % (settle_path, self._record_path))
         if self._record_path:
             self._filter.path_enable(self._record_path)
+        if self._settle_path:
+            self._filter.path_trunk_enable(self._settle_path)
         self.Qt = _default_Qt()
         self._domain = {"linear": _lib.PK_WEIGHTS_LINEAR, "log": _lib.PK_WEIGHTS_LOG}[weight_domain]
         if rng not in ("global", "device"):
@@ -1037,6 +1051,22 @@ class FastSLAM(object):
                 return self._filter.path_summary_weighted(self._domain)
             return self._filter.path_summary()
 
+    def full_path(self, weighting="uniform"):
+        """The path of the whole run (``path.FullPath``): the trunk's settled rows (FastSLAM(..., settle_path=E)), then
+        ``path_summary(weighting)``'s rows of the ring and of the current generation -- steps first_step .. recorded without a
+        gap.  A trunk row is ``final`` where every particle that was current when it was settled descended from one ancestor; a
+        ring row where the uniform summary reports one survivor.  Under "weights" the ring's rows are all reported not final:
+        the weighted summary counts no ancestors, and a row with one WEIGHTED lineage but several lineages overall is not final
+        -- this errs on the safe side.  Without settle_path it is path_summary in FullPath's form."""
+        self._need_path("full_path")
+        with self._lock:
+            summary = self.path_summary(weighting)
+            ring_final = summary.survivors == 1 if weighting == "uniform" else np.zeros(summary.mean.shape[0], dtype=bool)
+            trunk = None
+            if self._settle_path:
+                trunk = self._filter.path_trunk_summary() + (self._filter.path_trunk_shape()[1],)
+            return _path.FullPath.assemble(trunk, summary, ring_final)
+
     def best_particle(self):
         """The index of the particle with the largest weight (the lowest one among equals)."""
         with self._lock:
@@ -1078,6 +1108,9 @@ class FastSLAM(object):
             if self._record_path:
                 extra["path_poses"], extra["path_ancestors"] = self._filter.path_download()
                 extra["path_recorded"] = np.int64(self._filter.path_shape()[2])
+            if self._settle_path:
+                extra["path_trunk_rows"] = self._filter.path_trunk_download()
+                extra["path_trunk_first"] = np.int64(self._filter.path_trunk_shape()[1])
             np.savez_compressed(
                 path, poses=poses, means=m, covs=c, counts=k, Qt=np.asarray(self.Qt, dtype=np.float64),
                 immutable=np.array([bool(f.__immutable__) for f in self._features], dtype=np.uint8),
@@ -1103,6 +1136,19 @@ class FastSLAM(object):
                 if d["path_ancestors"].shape != (n, P) or d["path_poses"].shape != (n, P, 3) or n > self._record_path:
                     raise ValueError("snapshot: a path of %s x %s does not fit this filter's ring of %d steps x %d particles"
                                      % (d["path_ancestors"].shape[0], d["path_ancestors"].shape[1:], self._record_path, P))
+            have_trunk = self._settle_path and "path_trunk_rows" in d.files
+            if have_trunk:
+                rows = d["path_trunk_rows"]
+                if rows.ndim != 2 or rows.shape[1] != _path.TRUNK_RES or int(d["path_trunk_first"]) < 0:
+                    raise ValueError("snapshot: path_trunk_rows must be (n, %d) from a step >= 0" % _path.TRUNK_RES)
+                if rows.shape[0] and not (np.all(rows[:, 8] >= 0) and np.all(rows[:, 8] <= rows[:, 9]) and np.all(rows[:, 9] < P)
+                                          and np.all(rows[:, 8:10] == np.floor(rows[:, 8:10]))):
+                    raise ValueError("snapshot: the trunk's ancestors are not lineage indices of %d particles" % P)
+                n_ring = d["path_ancestors"].shape[0] if have_path else 0
+                end = int(d["path_recorded"]) - n_ring if have_path else int(d["path_trunk_first"]) + rows.shape[0]
+                if int(d["path_trunk_first"]) + rows.shape[0] != end:
+                    raise ValueError("snapshot: a trunk of steps [%d, %d) does not meet a ring that begins at step %d"
+                                     % (int(d["path_trunk_first"]), int(d["path_trunk_first"]) + rows.shape[0], end))
             have_logw = self._threshold is not None and "log_weights" in d.files
             if have_logw and (d["log_weights"].shape != (P,) or not np.all(d["log_weights"] < np.inf)):
                 raise ValueError("snapshot: log_weights must be %d numbers below +inf" % P)
@@ -1136,6 +1182,8 @@ class FastSLAM(object):
                                                     d["nl_clock_idle"], int(d["nl_clock_now"]))
             elif have_nl:
                 self._nl_assign(*_nl_restore(d, P))
+            if have_trunk:  # (behind upload_poses, ahead of the ring; a snapshot without it: the trunk restarts where the ring begins)
+                self._filter.path_trunk_upload(d["path_trunk_rows"], int(d["path_trunk_first"]))
             if have_path:  # (behind upload_poses, which empties the ring; a snapshot without a path leaves it empty)
                 self._filter.path_upload(d["path_poses"], d["path_ancestors"], int(d["path_recorded"]))
             self._touch()

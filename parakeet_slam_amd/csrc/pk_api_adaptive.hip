@@ -81,7 +81,8 @@ int pk_resample_adaptive(pk_filter* f, double u, int32_t weight_domain, double t
   ++f->ad_calls;
   if (f->retire.on()) launch_retire_gather(f->stream, f->grow, f->retire, f->anc, d.P);  // (pk_grow_retire: the clocks too)
   if (f->grow_on) launch_grow_gather(f->stream, f->grow, f->anc, d.P);  // by the ancestors: the identity when the call kept
-  if (f->path.cap && (rc = path_record(f))) return rc;                   // one ring row per call, kept or not
+  if (f->path.cap && (rc = path_record(f, weight_domain))) return rc;    // one ring row per call, kept or not; a trunk settles by
+                                                                         // the new generation's weights
   PK_LAUNCH_CHECK("pk_resample_adaptive");
   f->src_identity = false;  // (the host does not know the verdict: as behind a resample)
   f->gmax_fused = false;

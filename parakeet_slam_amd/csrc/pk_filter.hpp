@@ -3,7 +3,8 @@
 //   pk_api.hip          lifecycle, transfers, motion, resample, the step, new-landmark bookkeeping, options, timing, the probe
 //   pk_api_observe.hip  the observe pipeline: staging, routing, association, the one-pass stages, the colour table's host side
 //   pk_api_shard.hip    the multi-GPU protocol: host-side, device-resident and balanced
-//   pk_api_path.hip     the path estimate: the ring of resampled generations, its transfers, trace and summaries, the best particle
+//   pk_api_path.hip     the path estimate: the ring of resampled generations, its transfers, trace and summaries, the trunk of
+//                       settled rows, the best particle
 //   pk_api_adaptive.hip adaptive resampling: the gated resample and step, the weight sums, the weighted pose summary
 //   pk_api_mapmatch.hip the discovered landmarks: the matched moments and the finished estimate
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
@@ -352,6 +353,10 @@ struct pk_filter {
   double* pw_part = nullptr;     // [pw_rows][path_blocks(P)][kPathSums]
   double* pw_res = nullptr;      // [pw_rows][kPathWRes], then the call's own maximum log-weight (1 word)
   int64_t pw_rows = 0;
+  // the trunk (pk_path_trunk_enable): the settled rows; settling works in pk_path_summary_weighted's scratch, which
+  // pk_path_trunk_enable reserves for the whole ring, so that no step allocates.  The rows start at max(4 batch, 1024) and grow by
+  // doubling -- allocate, device-to-device copy, free -- which is the ONLY synchronisation a settling step can ever meet.
+  PathTrunk trunk{};
   // adaptive resampling and the weighted pose summary (pk_api_adaptive.hip): nothing until one of its entry points is first called
   double* ad_s2 = nullptr;          // [nblocks] sum w^2 of every scan block
   double* ad_words = nullptr;       // [kAdWords] the scan's shift | the plan beyond kAncestorsScanMaxBlocks blocks | a maximum log-weight | the pose summary
@@ -488,7 +493,12 @@ int refuse_retire(const pk_filter* f, const char* who);
 // pk_api_retire.hip
 int retire_restart(pk_filter* f, int64_t p0, int64_t p1);  // pk_grow_upload wrote these particles: their clocks restart
 // pk_api_path.hip
-int path_record(pk_filter* f);  // behind pk_resample's kernels while the ring is on
+// behind pk_resample's kernels while the ring is on; weighting: what a trunk settles by when this record fills the ring
+// (PK_PATH_UNIFORM, or the gated call's weight domain over the new generation's log-weights)
+int path_record(pk_filter* f, int weighting = PK_PATH_UNIFORM);
 inline void path_clear(pk_filter* f) {  // the history ends: the population was replaced
-  if (f) f->path.held = f->path.first = 0;
+  if (!f) return;
+  f->path.held = f->path.first = 0;
+  f->trunk.length = 0;  // (the trunk's memory stays)
+  f->trunk.first_step = f->path.recorded;
 }

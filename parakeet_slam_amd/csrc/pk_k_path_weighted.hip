@@ -7,128 +7,9 @@
 // covers the whole ring -- no atomics, no grid barrier, no quantised weights.  Every sum runs over k in a fixed order -- lane, wave,
 // the waves in order, then the workgroups one by one -- so the same ring and weights give the same bits twice.  DESIGN.md section
 // 4, "The weighted path estimate".
-#include "pk_device.hpp"
+#include "pk_path_rows.hpp"  // walk_rows, rows_reduce, the fold of a row: shared with pk_k_path_settle.hip
 
 namespace pk {
-
-namespace {
-
-constexpr int kPwWaves = kPathLanes / kWave;
-constexpr int kPwRows = 8;  // rows a thread takes at a time (1, 4 and 8 measured: profiles/r12)
-
-// What one workgroup keeps in LDS per turn (a turn: up to kPwRows rows reduced behind ONE barrier).  Two of them, taken in turn:
-// turn n + 1 writes the other one, and the one turn n wrote is written again only behind turn n + 1's barrier, which thread 0
-// reaches after it has read.
-struct PwLds {
-  PathMoments wm[kPwRows][kPwWaves];
-  double ss[kPwRows][kPwWaves], sc[kPwRows][kPwWaves], s2[kPwWaves];
-};
-
-// k_pose_moments' reduction of a workgroup, for R rows side by side (R independent chains: their latencies overlap): the wave by
-// path_shfl_down (sums: the xor butterfly), the waves in order.  o: the workgroup's partial of row q = 0; row q's lies q *
-// row_doubles before it (the rows are taken newest first).
-template <int R>
-__device__ __forceinline__ void rows_reduce(PathMoments (&m)[R], double (&ss)[R], double (&sc)[R], double s2, PwLds& l,
-                                            double* __restrict__ o, size_t row_doubles) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int q = 0; q < R; ++q) m[q] = path_merge(m[q], path_shfl_down(m[q], off));  // lane 0 holds the wave's
-  }
-#pragma unroll
-  for (int q = 0; q < R; ++q) {
-    ss[q] = wave_sum(ss[q]);
-    sc[q] = wave_sum(sc[q]);
-  }
-  s2 = wave_sum(s2);
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-      l.wm[q][wave] = m[q];
-      l.ss[q][wave] = ss[q];
-      l.sc[q][wave] = sc[q];
-    }
-    l.s2[wave] = s2;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  s2 = l.s2[0];
-#pragma unroll
-  for (int w = 1; w < kPwWaves; ++w) s2 += l.s2[w];
-#pragma unroll
-  for (int q = 0; q < R; ++q) {
-    PathMoments t = l.wm[q][0];
-    double s = l.ss[q][0], c = l.sc[q][0];
-#pragma unroll
-    for (int w = 1; w < kPwWaves; ++w) {
-      t = path_merge(t, l.wm[q][w]);
-      s += l.ss[q][w];
-      c += l.sc[q][w];
-    }
-    double* __restrict__ const oq = o - (size_t)q * row_doubles;
-    oq[0] = t.n;
-    oq[1] = t.mx;
-    oq[2] = t.my;
-    oq[3] = t.xx;
-    oq[4] = t.xy;
-    oq[5] = t.yy;
-    oq[6] = s;
-    oq[7] = c;
-    oq[8] = q == 0 ? s2 : 0.0;
-    oq[9] = 0.0;
-  }
-}
-
-// Held rows t, t - 1 .. t - R + 1 (r: the ring row of t; returns that of t - R).  Per particle: R steps down the index chain
-// j = anc_row[j], the only loads that depend on one another; then the R rows' gathers, which do not, all in flight together.
-template <int R>
-__device__ __forceinline__ int walk_rows(const PathWeightedArgs& a, int t, int r, PwLds& l) {
-  const int64_t P = a.P, step = (int64_t)gridDim.x * kPathLanes, i0 = (int64_t)blockIdx.x * kPathLanes + threadIdx.x;
-  const double* __restrict__ const wgt = a.wgt;
-  int32_t* __restrict__ const idx = a.idx;
-  const int32_t* __restrict__ anc[R];
-  const double* __restrict__ px[R];
-  double rx[R], ry[R], ss[R], sc[R];
-  PathMoments m[R];
-#pragma unroll
-  for (int q = 0; q < R; ++q) {
-    anc[q] = a.anc + (size_t)r * P;
-    px[q] = a.pose + (size_t)r * 3 * P;
-    rx[q] = a.ref[3 * (t - q)];
-    ry[q] = a.ref[3 * (t - q) + 1];
-    ss[q] = sc[q] = 0.0;
-    m[q] = PathMoments{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    r = r == 0 ? a.cap - 1 : r - 1;
-  }
-  for (int64_t i = i0; i < P; i += step) {
-    const double w = wgt[i];
-    int32_t j = idx[i], jj[R];
-#pragma unroll
-    for (int q = 0; q < R; ++q) jj[q] = j = anc[q][j];
-    idx[i] = j;
-    double gx[R], gy[R], gh[R];
-#pragma unroll
-    for (int q = 0; q < R; ++q) {  // (a loop of their own: sincos branches, and no load is moved across a branch)
-      const int32_t k = jj[q];
-      gx[q] = px[q][k];
-      gy[q] = px[q][P + k];
-      gh[q] = px[q][2 * P + k];
-    }
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-      m[q] = path_merge(m[q], PathMoments{w, gx[q] - rx[q], gy[q] - ry[q], 0.0, 0.0, 0.0});
-      double s, co;
-      sincos(gh[q], &s, &co);
-      ss[q] = __fma_rn(w, s, ss[q]);
-      sc[q] = __fma_rn(w, co, sc[q]);
-    }
-  }
-  rows_reduce<R>(m, ss, sc, 0.0, l, a.part + ((size_t)t * gridDim.x + blockIdx.x) * kPathSums, (size_t)gridDim.x * kPathSums);
-  return r;
-}
-
-}  // namespace
 
 // part[row][block][kPathSums]: S1, mean dx, mean dy, xx, xy, yy (centred, weighted; d = pose - the row's reference pose), sum w
 // sin h, sum w cos h, sum w^2 (row `held`; 0 elsewhere), 0.  wgt[P] and idx[P] are the launch's own scratch: a thread reads and
@@ -179,26 +60,7 @@ __global__ void __launch_bounds__(kWave) k_path_weighted_fold(const double* __re
                                                               double* __restrict__ res) {
   if (threadIdx.x != 0) return;
   const int t = blockIdx.x;
-  const double* p = part + (size_t)t * nb * kPathSums;
-  PathMoments m{p[0], p[1], p[2], p[3], p[4], p[5]};
-  double ss = p[6], sc = p[7], s2 = p[8];
-  for (int b = 1; b < nb; ++b) {
-    const double* q = p + (size_t)b * kPathSums;
-    m = path_merge(m, PathMoments{q[0], q[1], q[2], q[3], q[4], q[5]});
-    ss += q[6];
-    sc += q[7];
-    s2 += q[8];
-  }
-  double* o = res + (size_t)t * kPathWRes;
-  o[0] = ref[3 * t + 0] + m.mx;
-  o[1] = ref[3 * t + 1] + m.my;
-  o[2] = ss;
-  o[3] = sc;
-  o[4] = m.xx / m.n;
-  o[5] = m.xy / m.n;
-  o[6] = m.yy / m.n;
-  o[7] = m.n;
-  o[8] = s2;
+  path_weighted_fold_row(part + (size_t)t * nb * kPathSums, ref[3 * t + 0], ref[3 * t + 1], nb, res + (size_t)t * kPathWRes);
 }
 
 void launch_path_weighted(hipStream_t s, const DeviceState& d, const PathRing& ring, const double* gmax_dev, int domain,

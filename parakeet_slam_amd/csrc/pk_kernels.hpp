@@ -456,6 +456,27 @@ struct PathWeightedArgs {
 constexpr int kPathWRes = 9;
 void launch_path_weighted(hipStream_t s, const DeviceState& d, const PathRing& ring, const double* gmax_dev, int domain,
                           int32_t* idx_dev, double* wgt_dev, double* ref_dev, double* part_dev, double* res_dev);
+// The trunk (pk_k_path_settle.hip; DESIGN.md section 4, "The trunk"): what is left of the rows the ring has given up, one record
+// of kPathTrunkRes doubles per step, oldest first -- mean x, mean y, sum w sin h, sum w cos h, var x, cov xy, var y, S1 by the
+// weights of the particles that were current when the row was settled (k_path_weighted_fold's first eight words for that row), the
+// lowest and the highest lineage index of the row over ALL of those particles (equal: the row is final), and the pose of the
+// lowest one as recorded.
+struct PathTrunk {
+  double* rows = nullptr;  // [cap][kPathTrunkRes]
+  int64_t cap = 0;         // rows allocated
+  int64_t length = 0;      // rows settled
+  int64_t first_step = 0;  // global step index of row 0
+  int batch = 0;           // rows path_record settles when it has filled the ring (0: the trunk is off)
+  bool scratch_mine = false;  // pk_path_trunk_enable made the settle scratch (host bookkeeping: switching off gives it back)
+};
+constexpr int kPathTrunkRes = 13;
+// Settles held rows 0 .. settle - 1 (1 <= settle <= ring.held; nothing for settle <= 0) into out_dev[settle][kPathTrunkRes].
+// Four launches whatever the ring holds: particle 0's lineage into ref_dev[held + 1][3]; a lane per particle -- its weight
+// (weighting: 0 / 1 as launch_path_weighted's domain, 2: every weight 1.0) into wgt_dev[P] and its lineage index in row `settle`,
+// walked by index alone, into idx_dev[P]; k_path_weighted's reduction of rows settle - 1 .. 0 with each workgroup's lowest and
+// highest lineage index into part_dev[row][path_blocks(P)][kPathSums]; one fold, a workgroup per row.  The ring is read only.
+void launch_path_settle(hipStream_t s, const DeviceState& d, const PathRing& ring, int settle, const double* gmax_dev, int weighting,
+                        int32_t* idx_dev, double* wgt_dev, double* ref_dev, double* part_dev, double* out_dev);
 // The particle with the largest log-weight, the lowest index among equals, NaN never: part_dev[path_blocks(P)][2], then one fold
 // in workgroup order into out_dev[2] = the log-weight, the index as a double (-1: every log-weight is NaN)
 void launch_best_particle(hipStream_t s, const DeviceState& d, double* part_dev, double* out_dev);

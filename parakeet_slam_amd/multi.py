@@ -195,16 +195,19 @@ class ShardedFastSLAM(object):
     every rank's device (pk_grow_enable); a particle that migrates in the resample takes its orphaned readings, id counter and
     spare-slot ids along behind its map, so the filter grows the same maps whatever the number of GPUs.
 
-    record_path (the path estimate of ``FastSLAM``) is refused: lineages across ranks are not recorded.  So is
+    record_path (the path estimate of ``FastSLAM``) and settle_path (its trunk) are refused: lineages across ranks are not recorded.  So is
     resample_threshold (adaptive resampling): the ranks would have to all-reduce their weight sums for one verdict.
 
     (``FastSLAM(..., devices=[...])`` arrives here with FastSLAM's OWN defaults -- weight_domain "linear", rng "global".)"""
 
     def __init__(self, preset_features=[], num_particles=50, devices=(0, 1), weight_domain="log", rng="device", seed=0,
                  backend="nccl", publish_debug=None, _shard_factory=None, new_landmarks=False, spare_landmarks=0,
-                 pair_threshold=30.0, reading_capacity=64, record_path=0, resample_threshold=None):
+                 pair_threshold=30.0, reading_capacity=64, record_path=0, resample_threshold=None, settle_path=None):
         from . import _lib  # constants only; loads nothing
 
+        if settle_path:  # (before any process starts)
+            raise ValueError("ShardedFastSLAM: settle_path is for one GPU, as record_path is -- the path is recorded and settled on "
+                             "one device only")
         if record_path:  # (before any process starts)
             raise ValueError("ShardedFastSLAM: record_path is for one GPU -- the lineages of particles that migrate between ranks "
                              "are not recorded (the sharded resample is refused on a recording filter)")
