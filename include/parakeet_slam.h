@@ -495,6 +495,42 @@ int pk_resample_stats(pk_filter* f, double out[4], int32_t* resampled, int64_t c
 int pk_weight_sums(pk_filter* f, int32_t weight_domain, double gmax, double out[2]);
 int pk_summary_weighted(pk_filter* f, int32_t weight_domain, double mean[3], double spread[4], double* n_eff);
 
+/* ---- the odometry motion model ("The odometry motion model") -------------------------------------------
+ * The reference declares FastSLAM.odom_motion_update (prkt_core_v2.py:140-146) and leaves it empty; pk_motion moves the particles
+ * by a commanded twist only.  These calls move them by the CHANGE between two odometry poses instead: the model of Thrun, Burgard,
+ * Fox, Probabilistic Robotics, Table 5.6 -- rotate by rot1, translate by trans, rotate by rot2 -- with four noise parameters.
+ *   wrap(a) = remainder(a, 2 pi) (IEEE): into [-pi, pi]; the one wrap every angle below goes through.
+ *   delta of prev = (x, y, th), now = (x', y', th'):
+ *     trans = hypot(x' - x, y' - y);  dth = wrap(th' - th)
+ *     rot1  = trans < min_trans ? 0 : wrap(atan2(y' - y, x' - x) - th);  rot2 = wrap(dth - rot1)
+ *   min_trans guards the turn in place, where atan2 of a vanishing translation is noise: below it the translation is applied along
+ *   the current heading.  The heading stays exact; the position is off by 2 trans sin(phi / 2), phi the angle between the heading
+ *   and the direction that was dropped: at most min_trans for a creep within 60 degrees of the heading, never more than
+ *   2 trans < 2 min_trans (a creep backwards, applied forwards).  min_trans = 0: no guard.
+ *   sigmas of a delta, alpha = (a1, a2, a3, a4); rotations are folded so that driving backwards (rot1 near +-pi) is not taken
+ *   for a large turn, r1n = min(|rot1|, pi - |rot1|), r2n likewise:
+ *     sigma_rot1 = sqrt(a1 r1n^2 + a2 trans^2);  sigma_trans = sqrt(a3 trans^2 + a4 (r1n^2 + r2n^2));
+ *     sigma_rot2 = sqrt(a1 r2n^2 + a2 trans^2)     -- the same for every particle: formed once, on the host.
+ *   the sample, per particle with standard normals z0, z1, z2:
+ *     r1 = rot1 - sigma_rot1 z0;  t = trans - sigma_trans z1;  r2 = rot2 - sigma_rot2 z2
+ *     x += t cos(h + r1);  y += t sin(h + r1);  h = wrapped((h + r1) + r2), to (-pi, pi] as pk_motion leaves it.
+ * pk_odom_delta, pk_odom_sigmas   host only, no filter: delta[3] = (rot1, trans, rot2); sigma[3] = (rot1, trans, rot2).
+ * pk_motion_odom         pk_motion for a delta: z and (seed, draw) as there -- the Philox counters and keys are pk_motion's, so the
+ *                        normals of (particle, seed, draw) are the same in both -- in the PK_T_MOTION span; a staged scan rides
+ *                        the launch.
+ * pk_motion_odom_range   pk_motion_range for a delta: the particles [p0, p1), device noise.
+ * pk_step_odom           pk_step with pk_motion_odom for its motion; threshold NaN: pk_step's reset and resample, else
+ *                        pk_step_adaptive's carried weights and gate.
+ * PK_ERR_INVALID, nothing changed: NULL arguments, a delta that is not finite or has trans < 0, an alpha or min_trans that is not
+ * finite or negative, a bad particle range, a bad threshold. */
+int pk_odom_delta(const double prev[3], const double now[3], double min_trans, double delta[3]);
+int pk_odom_sigmas(const double delta[3], const double alpha[4], double sigma[3]);
+int pk_motion_odom(pk_filter* f, const double delta[3], const double alpha[4], const double* z, uint64_t seed, uint64_t draw);
+int pk_motion_odom_range(pk_filter* f, const double delta[3], const double alpha[4], uint64_t seed, uint64_t draw, int64_t p0,
+                         int64_t p1);
+int pk_step_odom(pk_filter* f, const double delta[3], const double alpha[4], const double* z, uint64_t seed, uint64_t draw,
+                 const double* blobs, int32_t num_blobs, const int32_t* ids, double u, int32_t weight_domain, double threshold);
+
 /* ---- sharded (multi-GPU) resampling: see DESIGN.md section 6 -------------------
  * Particles are sharded contiguously over one process per GPU; global particle index =
  * global_offset + local index.  The collectives themselves are the caller's

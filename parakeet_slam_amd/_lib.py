@@ -100,6 +100,11 @@ SIGNATURES = {
     "pk_resample_stats": (C.c_int, [_h, _dp, C.POINTER(C.c_int32), _lp]),
     "pk_weight_sums": (C.c_int, [_h, C.c_int32, C.c_double, _dp]),
     "pk_summary_weighted": (C.c_int, [_h, C.c_int32, _dp, _dp, _dp]),
+    "pk_odom_delta": (C.c_int, [_dp, _dp, C.c_double, _dp]),
+    "pk_odom_sigmas": (C.c_int, [_dp, _dp, _dp]),
+    "pk_motion_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64]),
+    "pk_motion_odom_range": (C.c_int, [_h, _dp, _dp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64]),
+    "pk_step_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_double, C.c_int32, C.c_double]),
     "pk_shard_max_logw": (C.c_int, [_h, _dp]),
     "pk_shard_num_blocks": (C.c_int64, [_h]),
     "pk_shard_block_totals": (C.c_int, [_h, C.c_double, C.c_int32, _dp]),
@@ -224,6 +229,20 @@ def f64(a, shape=None):
     return a
 
 
+def odom_delta(prev, now, min_trans=0.01):
+    """(rot1, trans, rot2) between two odometry poses (x, y, heading): pk_odom_delta.  Host only, needs no GPU."""
+    a, b, out = f64(prev, (3,)), f64(now, (3,)), np.empty(3, dtype=np.float64)
+    check(load().pk_odom_delta(dptr(a), dptr(b), float(min_trans), dptr(out)))
+    return out
+
+
+def odom_sigmas(delta, alphas):
+    """(sigma_rot1, sigma_trans, sigma_rot2) of a delta under the four noise parameters: pk_odom_sigmas.  Host only."""
+    d, a, out = f64(delta, (3,)), f64(alphas, (4,)), np.empty(3, dtype=np.float64)
+    check(load().pk_odom_sigmas(dptr(d), dptr(a), dptr(out)))
+    return out
+
+
 class DeviceFilter(object):
     """Thin, numpy-in / numpy-out wrapper of one ``pk_filter`` handle.
 
@@ -311,6 +330,12 @@ class DeviceFilter(object):
     def motion(self, v, w, dt, z=None, seed=0, draw=0):
         zz = f64(z, (self.P, 3)) if z is not None else None
         check(self._lib.pk_motion(self._h, float(v), float(w), float(dt), dptr(zz), int(seed), int(draw)))
+
+    def motion_odom(self, delta, alphas, z=None, seed=0, draw=0):
+        """motion for an odometry delta (rot1, trans, rot2) with the noise parameters (a1, a2, a3, a4): pk_motion_odom."""
+        d, a = f64(delta, (3,)), f64(alphas, (4,))
+        zz = f64(z, (self.P, 3)) if z is not None else None
+        check(self._lib.pk_motion_odom(self._h, dptr(d), dptr(a), dptr(zz), int(seed), int(draw)))
 
     def download_log_weights(self):
         out = np.empty(self.P, dtype=np.float64)
@@ -517,6 +542,16 @@ class DeviceFilter(object):
         check(self._lib.pk_step(self._h, float(v), float(w), float(dt), dptr(zz), int(seed), int(draw), dptr(b), B,
                                 iptr(i), float(u), int(domain)))
 
+    def step_odom(self, delta, alphas, blobs, u, threshold=None, z=None, seed=0, draw=0, ids=None, domain=PK_WEIGHTS_LINEAR):
+        """step with motion_odom for its motion; threshold None: step's reset and resample, else step_adaptive's gate."""
+        d, a = f64(delta, (3,)), f64(alphas, (4,))
+        b = f64(blobs).reshape(-1, 4)
+        B = b.shape[0]
+        zz = f64(z, (self.P, 3)) if z is not None else None
+        i = np.ascontiguousarray(ids, dtype=np.int32).reshape(B) if ids is not None else None
+        check(self._lib.pk_step_odom(self._h, dptr(d), dptr(a), dptr(zz), int(seed), int(draw), dptr(b), B, iptr(i), float(u),
+                                     int(domain), float("nan") if threshold is None else float(threshold)))
+
     # -- adaptive resampling (pk_resample_adaptive ...): the device decides, the host asks when it wants to know
     def resample_adaptive(self, u, threshold, domain=PK_WEIGHTS_LINEAR, return_ancestors=False):
         """Resamples iff n_eff < threshold * P (decided on the device); else the particles stay and the ancestors are arange(P)."""
@@ -675,6 +710,10 @@ class DeviceFilter(object):
 
     def motion_range(self, v, w, dt, seed, draw, p0, p1):
         check(self._lib.pk_motion_range(self._h, float(v), float(w), float(dt), int(seed), int(draw), int(p0), int(p1)))
+
+    def motion_odom_range(self, delta, alphas, seed, draw, p0, p1):
+        d, a = f64(delta, (3,)), f64(alphas, (4,))
+        check(self._lib.pk_motion_odom_range(self._h, dptr(d), dptr(a), int(seed), int(draw), int(p0), int(p1)))
 
     def staged_takes_regs(self):
         return bool(self._lib.pk_staged_takes_regs(self._h))

@@ -26,6 +26,7 @@ import threading
 import numpy as np
 
 from . import _lib, adaptive, mapsum, msgs
+from . import odom as _odom
 from . import path as _path
 from .msgs import Blob, Odometry, Twist, heading_to_quaternion, quaternion_to_heading
 
@@ -565,6 +566,17 @@ class FastSLAM(object):
     then the WEIGHTED pose, ``pose_summary()`` its full form, ``map_summary()`` weights by default, ``resample_stats()`` says
     what the last step decided, and ``last_ancestors`` is the identity on a kept step.  The resample draw is taken at every
     step, kept or not, so the random stream does not depend on the decisions.  One GPU only, as record_path.
+
+    motion="odometry" (default "twist": the reference's commanded twist with its hard-wired noise): the particles move by
+    ``odom_motion_update(odom)`` alone -- the reference's empty stub (:140-146), finished.  Every message after the first moves
+    ALL particles by the change between the previous message's pose and its own: the odometry motion model of Probabilistic
+    Robotics, Table 5.6 (rotate, translate, rotate; pk_odom_delta, pk_motion_odom), whose noise grows with the motion through
+    ``odom_alphas=(a1, a2, a3, a4)``: sigma_rot^2 = a1 rot^2 + a2 trans^2, sigma_trans^2 = a3 trans^2 + a4 (rot1^2 + rot2^2).
+    A translation below ``odom_min_trans`` (0.01 m) is a turn in place: it is applied along the current heading, which puts the
+    position off by 2 trans sin(phi / 2), phi the angle between the heading and the dropped direction -- at most odom_min_trans
+    within 60 degrees of the heading, below 2 odom_min_trans always; the heading stays exact.  ``motion_update(twist)`` then only records the control, and ``cam_cb`` applies the scan to
+    the poses as the last odometry message left them.  A robot that stood still launches nothing and consumes no draw.
+    ``motion_model(particle, twist, dt)`` stays the twist model.  Works with devices=[several] too.
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -606,7 +618,8 @@ class FastSLAM(object):
                                    weight_domain=a["weight_domain"], rng=a["rng"], seed=a["seed"],
                                    publish_debug=a["publish_debug"], new_landmarks=a["new_landmarks"],
                                    spare_landmarks=a["spare_landmarks"], pair_threshold=a["pair_threshold"],
-                                   reading_capacity=a["reading_capacity"], **extra)
+                                   reading_capacity=a["reading_capacity"], motion=a["motion"], odom_alphas=a["odom_alphas"],
+                                   odom_min_trans=a["odom_min_trans"], **extra)
         if extra:
             raise TypeError("FastSLAM: %s only apply with devices=[...] naming several GPUs" % ", ".join(sorted(extra)))
         return super(FastSLAM, cls).__new__(cls)
@@ -614,7 +627,10 @@ class FastSLAM(object):
     def __init__(self, preset_features=[], num_particles=50, device=0, weight_domain="linear", rng="global",
                  seed=0, publish_debug=None, new_landmarks=False, spare_landmarks=0, pair_threshold=30.0, devices=None,
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
-                 reading_max_age=0, potential_max_idle=0, settle_path=None):
+                 reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
+                 odom_min_trans=_odom.DEFAULT_MIN_TRANS):
+        self._motion, self._odom_alphas, self._odom_min_trans = _odom.check_keywords(motion, odom_alphas, odom_min_trans)
+        self._odom_prev = None  # the last odometry pose (x, y, heading); None: the next message is the first
         if devices is not None and len(list(devices)) == 1:
             device = list(devices)[0]
         self._retire = (int(reading_max_age), int(potential_max_idle))
@@ -837,7 +853,7 @@ class FastSLAM(object):
     def cam_cb(self, ros_view):
         """One filter step (:59-137)."""
         with self._lock:
-            self._motion_update(self.last_control)  # :75-77
+            self._motion_update(self.last_control)  # :75-77 (odometry mode: the poses are current up to the last /odom message)
             scan = ros_view.last_sensor_reading  # :82
             blobs = _blob_matrix(scan.observes)
             self._filter.set_measurement_noise(self.Qt)
@@ -910,7 +926,21 @@ class FastSLAM(object):
                 self._used[i] += len(fresh)
 
     def odom_motion_update(self, odom):
-        pass  # :140-146 alpha feature, empty in the reference
+        """:140-146, empty in the reference.  motion="odometry": move every particle by the change between the last odometry
+        message's pose and this one's (pk_odom_delta, pk_motion_odom); the first message only stores its pose.  A robot that
+        stood still (a delta of exactly zero) launches nothing and consumes no draw.  motion="twist": nothing, as the reference."""
+        if self._motion != "odometry":
+            return
+        now = _odom.check_pose(_state_pose(odom))  # (a message that is not finite: ValueError, nothing stored, nothing moved)
+        with self._lock:
+            prev = self._odom_prev
+            delta = None if prev is None else _lib.odom_delta(prev, now, self._odom_min_trans)
+            self._odom_prev = now  # (only once the delta was formed: a refused message leaves the stored pose as it was)
+            if delta is None or _odom.is_zero(delta):
+                return
+            self._filter.motion_odom(delta, self._odom_alphas, z=self._noise(self.num_particles), seed=self._seed, draw=self._draw)
+            self._draw += 1
+            self._touch()
 
     # ------------------------------------------------------------------ a2
     def _noise(self, n):
@@ -922,11 +952,13 @@ class FastSLAM(object):
 
     def _motion_update(self, new_twist):
         dt = msgs.now() - self.last_update  # :158
-        v = float(self.last_control.linear.x)  # moves with the PREVIOUS control (:163)
-        w = float(self.last_control.angular.z)
-        self._filter.motion(v, w, dt.to_sec(), z=self._noise(self.num_particles), seed=self._seed, draw=self._draw)
-        self._draw += 1
-        self._touch()
+        if self._motion == "twist":
+            v = float(self.last_control.linear.x)  # moves with the PREVIOUS control (:163)
+            w = float(self.last_control.angular.z)
+            self._filter.motion(v, w, dt.to_sec(), z=self._noise(self.num_particles), seed=self._seed, draw=self._draw)
+            self._draw += 1
+            self._touch()
+        # (motion="odometry": the control and its time are recorded, the particles move by odom_motion_update alone)
         self.last_update = self.last_update + dt  # :165
         self.last_control = new_twist  # :166
 
@@ -1108,6 +1140,8 @@ class FastSLAM(object):
             if self._record_path:
                 extra["path_poses"], extra["path_ancestors"] = self._filter.path_download()
                 extra["path_recorded"] = np.int64(self._filter.path_shape()[2])
+            if self._motion == "odometry" and self._odom_prev is not None:
+                extra["odom_prev"] = np.array(self._odom_prev, dtype=np.float64)
             if self._settle_path:
                 extra["path_trunk_rows"] = self._filter.path_trunk_download()
                 extra["path_trunk_first"] = np.int64(self._filter.path_trunk_shape()[1])
@@ -1152,6 +1186,9 @@ class FastSLAM(object):
             have_logw = self._threshold is not None and "log_weights" in d.files
             if have_logw and (d["log_weights"].shape != (P,) or not np.all(d["log_weights"] < np.inf)):
                 raise ValueError("snapshot: log_weights must be %d numbers below +inf" % P)
+            have_odom = self._motion == "odometry" and "odom_prev" in d.files
+            if have_odom and (d["odom_prev"].shape != (3,) or not np.all(np.isfinite(d["odom_prev"]))):
+                raise ValueError("snapshot: odom_prev must be a finite pose (x, y, heading)")
             if have_nl:  # everything is checked before anything is assigned
                 _nl_check_snapshot(d, P, self._L0, L, self._spare, self._filter.grow_shape()[2] if self._nl_device else None)
             # (a snapshot without the clocks, or a filter that retires nothing: pk_grow_upload restarts them / they are not read)
@@ -1174,6 +1211,8 @@ class FastSLAM(object):
             self.last_control.linear.x = float(d["last_control"][0])
             self.last_control.angular.z = float(d["last_control"][1])
             self._draw = int(d["draw"])
+            if self._motion == "odometry":  # (a snapshot without the pose: the next message is the first)
+                self._odom_prev = tuple(float(v) for v in d["odom_prev"]) if have_odom else None
             if have_nl and self._nl_device:
                 _, S, R = self._filter.grow_shape()
                 self._filter.grow_upload(0, P, *_nl_arrays_from_snapshot(d, P, self._L0, S, R))

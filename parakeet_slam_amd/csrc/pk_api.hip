@@ -6,7 +6,7 @@
 // direction cos/sin (prkt_core_v2.py:510), which are O(B), not O(P*L).
 // This file: the filter's lifecycle and transfers, motion, resample, the step, the new-landmark bookkeeping, options, timing and
 // the probe.  The observe pipeline is pk_api_observe.hip, the multi-GPU protocol pk_api_shard.hip, the path estimate pk_api_path.hip,
-// adaptive resampling pk_api_adaptive.hip; pk_filter.hpp is what they share.
+// adaptive resampling pk_api_adaptive.hip, the odometry motion model pk_api_odom.hip; pk_filter.hpp is what they share.
 #include "pk_filter.hpp"
 
 extern "C" {
@@ -588,46 +588,12 @@ int pk_reset_weights(pk_filter* f) {
   return PK_OK;
 }
 
-// bytes of a staged ML scan block that the device needs: ctl | blobs + directions | exact records | [tables]
-static size_t staged_upload_bytes(const pk_filter::Staged& sg) {
-  const size_t o_exact = kCtlBytes + (size_t)sg.B * 6 * sizeof(double);
-  const size_t o_tab = o_exact + (size_t)sg.B * 6 * sizeof(double);
-  return sg.use_grid ? o_tab + sg.tab_bytes : o_exact;
-}
-
 int pk_motion(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw) {
   if (!f) return fail(PK_ERR_INVALID, "pk_motion: NULL handle");
   if (!std::isfinite(v) || !std::isfinite(w) || !std::isfinite(dt)) return fail(PK_ERR_INVALID, "pk_motion: non-finite control");
-  int rc;
-  if ((rc = use_device(f))) return rc;
-  const double* zd = nullptr;
-  if (z) {
-    // Parity mode: the caller's (pageable) buffer must be consumed before we return.
-    PK_HIP(hipMemcpyAsync(f->z_dev, z, (size_t)f->d.P * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    PK_HIP(hipStreamSynchronize(f->stream));
-    zd = f->z_dev;
-  }
-  Span t(f, PK_T_MOTION);
-  // a scan staged by pk_stage_scan and not uploaded yet rides in extra workgroups of this launch
-  // (what pk_step does; the sharded step stages the next scan before it calls pk_motion)
-  pk_filter::Staged& sg = f->staged;
-  if (!z && sg.valid && !sg.uploaded && f->opt.upload_kernel) {
-    void* dev_view = nullptr;
-    if (hipHostGetDevicePointer(&dev_view, sg.st, 0) == hipSuccess && dev_view) {
-      launch_motion(f->stream, f->d, v, w, dt, nullptr, seed, draw, 0, f->scan_dev, dev_view, staged_upload_bytes(sg), f->pose_part);
-      f->pose_part_ok = true;
-      sg.uploaded = true;
-      f->gmax_fused = false;  // the block's control words (running weight maximum) were just overwritten
-      if ((rc = note_upload(f, sg.slot))) return rc;
-      PK_LAUNCH_CHECK("pk_motion");
-      return PK_OK;
-    }
-    (void)hipGetLastError();
-  }
-  launch_motion(f->stream, f->d, v, w, dt, zd, seed, draw, 0, nullptr, nullptr, 0, f->pose_part);
-  f->pose_part_ok = true;
-  PK_LAUNCH_CHECK("pk_motion");
-  return PK_OK;
+  return motion_impl(f, "pk_motion", z, [&](const double* zd, void* up_dst, const void* up_src, size_t up_bytes) {
+    launch_motion(f->stream, f->d, v, w, dt, zd, seed, draw, 0, up_dst, up_src, up_bytes, f->pose_part);
+  });
 }
 
 int pk_motion_range(pk_filter* f, double v, double w, double dt, uint64_t seed, uint64_t draw, int64_t p0, int64_t p1) {
@@ -850,12 +816,46 @@ int pk_map_summary(pk_filter* f, int32_t weighting, double* mean, double* cov_wi
 
 int pk_step(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw,
             const double* blobs, int32_t B, const int32_t* ids, double u, int32_t weight_domain) {
-  return step_impl(f, v, w, dt, z, seed, draw, blobs, B, ids, u, weight_domain, nullptr);
+  return step_impl(f, StepMotion::twist(v, w, dt), z, seed, draw, blobs, B, ids, u, weight_domain, nullptr);
 }
 
 }  // extern "C"
 
-int step_impl(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
+// The body of pk_motion and pk_motion_odom behind their argument checks: `launch` is the one thing that differs.
+int motion_impl(pk_filter* f, const char* who, const double* z, const MotionLaunch& launch) {
+  int rc;
+  if ((rc = use_device(f))) return rc;
+  const double* zd = nullptr;
+  if (z) {
+    // Parity mode: the caller's (pageable) buffer must be consumed before we return.
+    PK_HIP(hipMemcpyAsync(f->z_dev, z, (size_t)f->d.P * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    PK_HIP(hipStreamSynchronize(f->stream));
+    zd = f->z_dev;
+  }
+  Span t(f, PK_T_MOTION);
+  // a scan staged by pk_stage_scan and not uploaded yet rides in extra workgroups of this launch
+  // (what pk_step does; the sharded step stages the next scan before it calls pk_motion)
+  pk_filter::Staged& sg = f->staged;
+  if (!z && sg.valid && !sg.uploaded && f->opt.upload_kernel) {
+    void* dev_view = nullptr;
+    if (hipHostGetDevicePointer(&dev_view, sg.st, 0) == hipSuccess && dev_view) {
+      launch(nullptr, f->scan_dev, dev_view, staged_upload_bytes(sg));
+      f->pose_part_ok = true;
+      sg.uploaded = true;
+      f->gmax_fused = false;  // the block's control words (running weight maximum) were just overwritten
+      if ((rc = note_upload(f, sg.slot))) return rc;
+      PK_LAUNCH_CHECK(who);
+      return PK_OK;
+    }
+    (void)hipGetLastError();
+  }
+  launch(zd, nullptr, nullptr, 0);
+  f->pose_part_ok = true;
+  PK_LAUNCH_CHECK(who);
+  return PK_OK;
+}
+
+int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
               int32_t B, const int32_t* ids, double u, int32_t weight_domain, const double* gate) {
   const bool reset = gate == nullptr;
   auto resample = [&]() {
@@ -864,8 +864,7 @@ int step_impl(pk_filter* f, double v, double w, double dt, const double* z, uint
   int rc;
   // Throughput mode with ML association: the host half of the scan upload first, then ONE launch
   // for the motion update and the upload of the scan block, then the observe kernels.
-  if (f && !f->dense && !f->grow_on && !z && !ids && B > 0 && blobs && f->map_loaded && f->opt.upload_kernel && std::isfinite(v) && std::isfinite(w) &&
-      std::isfinite(dt)) {
+  if (f && !f->dense && !f->grow_on && !z && !ids && B > 0 && blobs && f->map_loaded && f->opt.upload_kernel && m.finite()) {
     bool finite = true;
     for (int i = 0; i < 4 * B && finite; ++i) finite = std::isfinite(blobs[i]);
     if (finite && B <= 65535) {
@@ -876,8 +875,11 @@ int step_impl(pk_filter* f, double v, double w, double dt, const double* z, uint
       if (hipHostGetDevicePointer(&dev_view, sg.st, 0) == hipSuccess && dev_view) {
         {
           Span t(f, PK_T_MOTION);
-          launch_motion(f->stream, f->d, v, w, dt, nullptr, seed, draw, 0, f->scan_dev, dev_view, staged_upload_bytes(sg), f->pose_part);
-      f->pose_part_ok = true;
+          if (m.odom)
+            launch_motion_odom(f->stream, f->d, m.delta, m.sigma, nullptr, seed, draw, f->scan_dev, dev_view, staged_upload_bytes(sg), f->pose_part);
+          else
+            launch_motion(f->stream, f->d, m.v, m.w, m.dt, nullptr, seed, draw, 0, f->scan_dev, dev_view, staged_upload_bytes(sg), f->pose_part);
+          f->pose_part_ok = true;
         }
         sg.uploaded = true;
         f->gmax_fused = false;
@@ -889,7 +891,7 @@ int step_impl(pk_filter* f, double v, double w, double dt, const double* z, uint
       (void)hipGetLastError();
     }
   }
-  if ((rc = pk_motion(f, v, w, dt, z, seed, draw))) return rc;              // :75-77
+  if ((rc = m.odom ? motion_odom_checked(f, m.delta, m.sigma, z, seed, draw) : pk_motion(f, m.v, m.w, m.dt, z, seed, draw))) return rc;  // :75-77
   if ((rc = observe_impl(f, blobs, B, ids, nullptr, reset))) return rc;   // :73 (reset fused) + :82-124
   return resample();
 }

@@ -27,10 +27,6 @@ int bad_domain(const char* who, int32_t weight_domain) {
   if (weight_domain == PK_WEIGHTS_LINEAR || weight_domain == PK_WEIGHTS_LOG) return PK_OK;
   return fail(PK_ERR_INVALID, "%s: weight_domain %d", who, weight_domain);
 }
-int bad_threshold(const char* who, double threshold) {
-  if (std::isfinite(threshold) && threshold >= 0.0) return PK_OK;
-  return fail(PK_ERR_INVALID, "%s: threshold = %g is not a finite share of P >= 0", who, threshold);
-}
 
 // the maximum log-weight a call takes by itself or is given, into ad_words[kAdGmax] (the linear domain reads none)
 int own_gmax(pk_filter* f, int32_t weight_domain, double gmax) {
@@ -45,6 +41,11 @@ int own_gmax(pk_filter* f, int32_t weight_domain, double gmax) {
 }
 
 }  // namespace
+
+int bad_threshold(const char* who, double threshold) {
+  if (std::isfinite(threshold) && threshold >= 0.0) return PK_OK;
+  return fail(PK_ERR_INVALID, "%s: threshold = %g is not a finite share of P >= 0", who, threshold);
+}
 
 extern "C" {
 
@@ -98,7 +99,7 @@ int pk_resample_adaptive(pk_filter* f, double u, int32_t weight_domain, double t
 int pk_step_adaptive(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
                      int32_t B, const int32_t* ids, double u, int32_t weight_domain, double threshold) {
   if (int rc = bad_threshold("pk_step_adaptive", threshold)) return rc;  // before anything moves
-  return step_impl(f, v, w, dt, z, seed, draw, blobs, B, ids, u, weight_domain, &threshold);
+  return step_impl(f, StepMotion::twist(v, w, dt), z, seed, draw, blobs, B, ids, u, weight_domain, &threshold);
 }
 
 int pk_resample_stats(pk_filter* f, double out[4], int32_t* resampled, int64_t counts[2]) {

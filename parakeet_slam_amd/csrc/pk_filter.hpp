@@ -15,6 +15,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -474,10 +475,40 @@ inline unsigned* ctl_pub_stats(pk_filter* f) { return reinterpret_cast<unsigned*
 // ---- helpers that more than one file calls
 // pk_api.hip
 int materialise(pk_filter* f);
-// the body of pk_step and pk_step_adaptive.  gate == NULL: the weights restart from 1 and pk_resample ends the step; else they
-// carry over and pk_resample_adaptive ends it with the threshold *gate
-int step_impl(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
+// What moves the particles in a step: the commanded twist (pk_step, pk_step_adaptive) or an odometry delta with its sigmas
+// (pk_step_odom, which has checked both).
+struct StepMotion {
+  bool odom = false;
+  double v = 0.0, w = 0.0, dt = 0.0;                             // the twist
+  double delta[3] = {0.0, 0.0, 0.0}, sigma[3] = {0.0, 0.0, 0.0};  // the delta (rot1, trans, rot2) and its sigmas
+  static StepMotion twist(double v, double w, double dt) {
+    StepMotion m;
+    m.v = v;
+    m.w = w;
+    m.dt = dt;
+    return m;
+  }
+  bool finite() const { return odom || (std::isfinite(v) && std::isfinite(w) && std::isfinite(dt)); }
+};
+// the body of pk_step, pk_step_adaptive and pk_step_odom.  gate == NULL: the weights restart from 1 and pk_resample ends the step;
+// else they carry over and pk_resample_adaptive ends it with the threshold *gate
+int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
               int32_t B, const int32_t* ids, double u, int32_t weight_domain, const double* gate);
+// bytes of a staged ML scan block that the device needs: ctl | blobs + directions | exact records | [tables]
+inline size_t staged_upload_bytes(const pk_filter::Staged& sg) {
+  const size_t o_exact = kCtlBytes + (size_t)sg.B * 6 * sizeof(double);
+  const size_t o_tab = o_exact + (size_t)sg.B * 6 * sizeof(double);
+  return sg.use_grid ? o_tab + sg.tab_bytes : o_exact;
+}
+// the body pk_motion and pk_motion_odom share behind their argument checks: the copy of a supplied z, the PK_T_MOTION span, the
+// staged scan that rides the launch, pose_part_ok.  launch(z_dev, up_dst_dev, up_src_host_mapped, up_bytes) is the kernel's.
+using MotionLaunch = std::function<void(const double*, void*, const void*, size_t)>;
+int motion_impl(pk_filter* f, const char* who, const double* z, const MotionLaunch& launch);
+// pk_api_adaptive.hip
+int bad_threshold(const char* who, double threshold);  // a gate's threshold: finite and >= 0, else PK_ERR_INVALID
+// pk_api_odom.hip
+// pk_motion_odom behind its argument checks (what step_impl runs for an odometry step that cannot ride the fused launch)
+int motion_odom_checked(pk_filter* f, const double delta[3], const double sigma[3], const double* z, uint64_t seed, uint64_t draw);
 // pk_api_observe.hip
 int note_upload(pk_filter* f, int slot);
 int colour_rows_for_download(pk_filter* f, int64_t p0, int64_t p1);

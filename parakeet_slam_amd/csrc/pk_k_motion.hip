@@ -2,8 +2,7 @@
 //
 // Hand-written gfx950 (CDNA4, wave64) kernels of the FastSLAM particle update; see DESIGN.md
 // section 4.  No MFMA: the algebra is 2x2 / 3x3 and register resident (pk_math.hpp).
-#include "pk_device.hpp"
-#include "pk_philox.hpp"
+#include "pk_motion_common.hpp"
 
 namespace pk {
 
@@ -18,10 +17,7 @@ __global__ void __launch_bounds__(256) k_motion(double* __restrict__ x, double* 
                                                 double* __restrict__ pose_part) {
   __shared__ double red[4];
   if ((int)blockIdx.x >= motion_blocks) {
-    // the extra workgroups of a combined launch: the per-scan upload (see k_upload)
-    const int64_t nb = (int64_t)gridDim.x - motion_blocks;
-    for (int64_t i = (int64_t)(blockIdx.x - motion_blocks) * blockDim.x + threadIdx.x; i < up_n16; i += nb * blockDim.x)
-      up_dst[i] = up_src[i];
+    motion_upload_tail(motion_blocks, up_dst, up_src, up_n16);
     return;
   }
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -29,30 +25,7 @@ __global__ void __launch_bounds__(256) k_motion(double* __restrict__ x, double* 
   double px = 0.0, py = 0.0, ps = 0.0, pc = 0.0;  // this particle's share of the block's pose sums
   if (i < P) {
   double z0, z1, z2;
-  if (z) {
-    z0 = z[3 * i];
-    z1 = z[3 * i + 1];
-    z2 = z[3 * i + 2];
-  } else {
-    // the counter is the particle's index in the WHOLE filter: its slot plus the shard's offset, or -- balanced placement of
-    // the sharded filter -- the logical index its slot carries
-    uint64_t g = logical ? (uint64_t)logical[i] : (uint64_t)(i + goff);
-    Philox4 a = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)draw,
-                              (uint32_t)(draw >> 32) & 0x7fffffffu, (uint32_t)seed, (uint32_t)(seed >> 32));
-    Philox4 b = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)draw,
-                              ((uint32_t)(draw >> 32) & 0x7fffffffu) | 0x80000000u, (uint32_t)seed,
-                              (uint32_t)(seed >> 32));
-    double u1 = u53(a.v[0], a.v[1]), u2 = u53(a.v[2], a.v[3]);
-    double u3 = u53(b.v[0], b.v[1]), u4 = u53(b.v[2], b.v[3]);
-    double r1 = sqrt(-2.0 * log(u1)), r2 = sqrt(-2.0 * log(u3));
-    double s1, c1, s2, c2;
-    sincos(Consts<double>::two_pi * u2, &s1, &c1);
-    sincos(Consts<double>::two_pi * u4, &s2, &c2);
-    z0 = r1 * c1;
-    z1 = r1 * s1;
-    z2 = r2 * c2;
-    (void)s2;
-  }
+  motion_normals(z, i, logical, goff, seed, draw, z0, z1, z2);
   double xi = x[i], yi = y[i], hi = h[i];
   // normal(0, s, 1) == 0 + s * gauss  (numpy legacy), prkt_core_v2.py:185,190,193
   motion_model(xi, yi, hi, v, w, dt, 0.0 + sd * z0, 0.0 + sh * z1, 0.0 + sh * z2);
@@ -65,20 +38,7 @@ __global__ void __launch_bounds__(256) k_motion(double* __restrict__ x, double* 
     sincos(hi, &ps, &pc);
   }
   }
-  // The block's sums of x, y, sin h, cos h of the MOVED particles (fixed order): k_candidates takes the particles' mean pose from
-  // them (the reference the candidate lists are made around), which used to cost two launches of its own per scan
-  if (pose_part) {  // (kernel-uniform)
-    px = block_sum<4>(px, red);
-    py = block_sum<4>(py, red);
-    ps = block_sum<4>(ps, red);
-    pc = block_sum<4>(pc, red);
-    if (threadIdx.x == 0) {
-      pose_part[4 * blockIdx.x + 0] = px;
-      pose_part[4 * blockIdx.x + 1] = py;
-      pose_part[4 * blockIdx.x + 2] = ps;
-      pose_part[4 * blockIdx.x + 3] = pc;
-    }
-  }
+  if (pose_part) motion_pose_sums(px, py, ps, pc, red, pose_part);  // (kernel-uniform)
 }
 
 void launch_motion(hipStream_t s, DeviceState& d, double v, double w, double dt, const double* z_dev,

@@ -90,6 +90,13 @@ void launch_motion(hipStream_t s, DeviceState& d, double v, double w, double dt,
 inline int64_t motion_pose_blocks(int64_t P) { return (P + 255) / 256; }
 void launch_motion_range(hipStream_t s, DeviceState& d, double v, double w, double dt, uint64_t seed, uint64_t draw,
                          int64_t p0, int64_t p1);
+// K1 for an odometry delta (rot1, trans, rot2) with its sigmas (pk_k_motion_odom.hip): launch_motion's draws, upload workgroups
+// and pose sums
+void launch_motion_odom(hipStream_t s, DeviceState& d, const double delta[3], const double sigma[3], const double* z_dev,
+                        uint64_t seed, uint64_t draw, void* up_dst_dev = nullptr, const void* up_src_host_mapped = nullptr,
+                        size_t up_bytes = 0, double* pose_part_dev = nullptr);
+void launch_motion_odom_range(hipStream_t s, DeviceState& d, const double delta[3], const double sigma[3], uint64_t seed,
+                              uint64_t draw, int64_t p0, int64_t p1);
 void launch_reset_weights(hipStream_t s, DeviceState& d);
 // K2: maximum-likelihood association -> ids[P*B]
 // (a) reference kernel: every (landmark, blob) pair is gate-tested

@@ -464,4 +464,21 @@ __device__ __forceinline__ void motion_model(T& x, T& y, T& h, T v, T w, T dt, T
   h = wrap_heading(h2);  // :206 quaternion round trip
 }
 
+// The odometry motion model (Thrun, Burgard, Fox, Probabilistic Robotics, Table 5.6) on one pose: rotate by rot1, translate by
+// trans along the new heading, rotate by rot2.  n0..n2 are the three draws already scaled by the sigmas of the delta
+// (sigma_rot1 z0, sigma_trans z1, sigma_rot2 z2; the sigmas are the same for every particle and formed on the host), and are
+// SUBTRACTED, as the table samples them.  Ends, as motion_model does, with the heading wrapped to (-pi, pi].
+template <typename T>
+__device__ __forceinline__ void odom_motion_model(T& x, T& y, T& h, T rot1, T trans, T rot2, T n0, T n1, T n2) {
+  T r1 = rot1 - n0;
+  T t = trans - n1;
+  T r2 = rot2 - n2;
+  T h1 = h + r1;
+  T s, c;
+  sincos(h1, &s, &c);
+  x += t * c;
+  y += t * s;
+  h = wrap_heading(h1 + r2);
+}
+
 }  // namespace pk

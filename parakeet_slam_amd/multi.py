@@ -15,6 +15,10 @@ serves commands from a pipe:
     observe       the same without the resample (the debug publishers of :126-127, :237 want the poses in between)
     resample      low_variance_resample (:210-252) on the weights as they stand
     motion        motion_update (:148-166)
+    odom_delta / motion_odom   odom_motion_update in odometry mode: rank 0 forms the delta between two odometry poses (the
+                  library's one definition, host only), every rank moves its particles by it
+    step_still    a step without motion (odometry mode: the poses are current up to the last odometry message);
+                  observe_still likewise
     summary       (:254-276): every rank all-reduces four pose sums; rank 0 answers
     poses / landmarks / set_particle / set_state   views for ``particles[i]`` (lazy, like the single-GPU facade),
                   ``particles[i] = p`` (:162) on the owning rank, snapshots
@@ -42,6 +46,7 @@ import traceback
 import numpy as np
 
 from . import msgs
+from . import odom as _odom
 from .msgs import Odometry, Twist
 
 
@@ -81,6 +86,24 @@ def _worker_main(rank, world, device, store_path, backend, P_local, L, means, co
                     sf.set_measurement_noise(qt)
                     sf.motion(v, w, dt, z=z, seed=seed, draw=draw)
                     sf.observe(blobs, fresh=True)
+                    conn.send(("ok", None))
+                elif op == "step_still":
+                    _, seed, draw, blobs, qt, u = cmd
+                    sf.set_measurement_noise(qt)
+                    sf.step(0.0, 0.0, 0.0, blobs, u, seed=seed, draw=draw, domain=domain, motion="none")
+                    conn.send(("ok", None))
+                elif op == "observe_still":
+                    _, blobs, qt = cmd
+                    sf.set_measurement_noise(qt)
+                    sf.observe(blobs, fresh=True)
+                    conn.send(("ok", None))
+                elif op == "odom_delta":
+                    from . import _lib
+
+                    conn.send(("ok", _lib.odom_delta(cmd[1], cmd[2], cmd[3])))
+                elif op == "motion_odom":
+                    _, delta, alphas, z, seed, draw = cmd
+                    sf.motion_odom(delta, alphas, z=z, seed=seed, draw=draw)
                     conn.send(("ok", None))
                 elif op == "resample":
                     sf.resample(cmd[1], domain=domain)
@@ -198,12 +221,19 @@ class ShardedFastSLAM(object):
     record_path (the path estimate of ``FastSLAM``) and settle_path (its trunk) are refused: lineages across ranks are not recorded.  So is
     resample_threshold (adaptive resampling): the ranks would have to all-reduce their weight sums for one verdict.
 
+    motion="odometry", odom_alphas, odom_min_trans: as in ``FastSLAM`` -- the particles move by ``odom_motion_update`` alone, with the
+    Philox counters of one filter, so the result does not depend on the number of GPUs.
+
     (``FastSLAM(..., devices=[...])`` arrives here with FastSLAM's OWN defaults -- weight_domain "linear", rng "global".)"""
 
     def __init__(self, preset_features=[], num_particles=50, devices=(0, 1), weight_domain="log", rng="device", seed=0,
                  backend="nccl", publish_debug=None, _shard_factory=None, new_landmarks=False, spare_landmarks=0,
-                 pair_threshold=30.0, reading_capacity=64, record_path=0, resample_threshold=None, settle_path=None):
+                 pair_threshold=30.0, reading_capacity=64, record_path=0, resample_threshold=None, settle_path=None,
+                 motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS, odom_min_trans=_odom.DEFAULT_MIN_TRANS):
         from . import _lib  # constants only; loads nothing
+
+        self._motion, self._odom_alphas, self._odom_min_trans = _odom.check_keywords(motion, odom_alphas, odom_min_trans)
+        self._odom_prev = None  # the last odometry pose (x, y, heading); None: the next message is the first
 
         if settle_path:  # (before any process starts)
             raise ValueError("ShardedFastSLAM: settle_path is for one GPU, as record_path is -- the path is recorded and settled on "
@@ -379,8 +409,22 @@ class ShardedFastSLAM(object):
             from .core import _blob_matrix
 
             blobs = _blob_matrix(ros_view.last_sensor_reading.observes)  # :82
-            zs = self._noise()
             qt = np.asarray(self.Qt, dtype=np.float64).reshape(4, 4)
+            if self._motion == "odometry":
+                # no twist motion: the poses are current up to the last odometry message.  Everything else as below.
+                if self._publish:
+                    self._all("observe_still", blobs, qt)
+                    self._pose_cache = None
+                    self._publish_all(self.particle_track_pub, self.download_poses())
+                    self.last_update = self.last_update + dt
+                    self.low_variance_resample()
+                    return
+                u = _pyrandom.random()
+                self._all("step_still", self._seed, self._draw, blobs, qt, float(u))
+                self.last_update = self.last_update + dt
+                self._pose_cache = None
+                return
+            zs = self._noise()
             if self._publish:
                 # the debug publishers want the poses between the weighting and the resample: two commands, and ONE gathered
                 # pose download that feeds /particle_track (:126-127) and /aged_particles (:237)
@@ -406,12 +450,14 @@ class ShardedFastSLAM(object):
         with self._lock:
             self._check_open()
             dt = msgs.now() - self.last_update
-            v, w = float(self.last_control.linear.x), float(self.last_control.angular.z)
-            zs = self._noise()
-            for r in range(len(self._conns)):
-                self._post(r, ("motion", v, w, float(dt.to_sec()), zs[r], self._seed, self._draw))
-            self._collect("motion")
-            self._draw += 1
+            if self._motion == "twist":
+                v, w = float(self.last_control.linear.x), float(self.last_control.angular.z)
+                zs = self._noise()
+                for r in range(len(self._conns)):
+                    self._post(r, ("motion", v, w, float(dt.to_sec()), zs[r], self._seed, self._draw))
+                self._collect("motion")
+                self._draw += 1
+            # (motion="odometry": the control and its time are recorded, the particles move by odom_motion_update alone)
             self.last_update = self.last_update + dt
             self.last_control = new_twist
             self._pose_cache = None
@@ -462,7 +508,26 @@ class ShardedFastSLAM(object):
             return self._all("map_summary", code)[0]
 
     def odom_motion_update(self, odom):
-        pass  # :140-146 alpha feature, empty in the reference
+        """:140-146, empty in the reference.  motion="odometry": as ``FastSLAM.odom_motion_update`` -- every message after the
+        first moves ALL particles, on every rank, by the change of the odometry pose; motion="twist": nothing."""
+        if self._motion != "odometry":
+            return
+        from .core import _state_pose
+
+        now = _odom.check_pose(_state_pose(odom))  # (not finite: ValueError here, nothing stored, no rank ever sees it)
+        with self._lock:
+            self._check_open()
+            prev = self._odom_prev
+            delta = None if prev is None else self._one(0, "odom_delta", prev, now, self._odom_min_trans)
+            self._odom_prev = now  # (only once the delta was formed)
+            if delta is None or _odom.is_zero(delta):  # the first message; the robot stood still: nothing to launch, no draw
+                return
+            zs = self._noise()
+            for r in range(len(self._conns)):
+                self._post(r, ("motion_odom", delta, self._odom_alphas, zs[r], self._seed, self._draw))
+            self._collect("motion_odom")
+            self._draw += 1
+            self._pose_cache = None
 
     # ------------------------------------------------------------------ views
     def download_poses(self):
@@ -582,6 +647,8 @@ class ShardedFastSLAM(object):
 
                 g = self._all("grow", 0, self._P_local)
                 extra = _nl_snapshot_arrays(*[np.concatenate([q[a] for q in g])[self._where] for a in range(3)], L0=self._L0)
+            if self._motion == "odometry" and self._odom_prev is not None:
+                extra["odom_prev"] = np.array(self._odom_prev, dtype=np.float64)
             np.savez_compressed(
                 path, poses=poses, means=m, covs=c, counts=k, Qt=np.asarray(self.Qt, dtype=np.float64),
                 immutable=np.array([bool(f.__immutable__) for f in self._features], dtype=np.uint8),
@@ -596,6 +663,9 @@ class ShardedFastSLAM(object):
             if d["poses"].shape != (P, 4) or d["means"].shape != (P, L, 5):
                 raise ValueError("snapshot is for %s particles x %s landmarks, this filter has %d x %d"
                                  % (d["poses"].shape[0], d["means"].shape[1], P, L))
+            have_odom = self._motion == "odometry" and "odom_prev" in d.files
+            if have_odom and (d["odom_prev"].shape != (3,) or not np.all(np.isfinite(d["odom_prev"]))):  # as FastSLAM.load_state
+                raise ValueError("snapshot: odom_prev must be a finite pose (x, y, heading)")
             nl = None
             if self._grow:
                 from .core import _nl_arrays_from_snapshot, _nl_check_snapshot
@@ -618,6 +688,8 @@ class ShardedFastSLAM(object):
             self.last_control.linear.x = float(d["last_control"][0])
             self.last_control.angular.z = float(d["last_control"][1])
             self._draw = int(d["draw"])
+            if self._motion == "odometry":  # (a snapshot without the pose: the next message is the first)
+                self._odom_prev = tuple(float(v) for v in d["odom_prev"]) if have_odom else None
             self._pose_cache = None
 
     # ------------------------------------------------------------------ shutdown

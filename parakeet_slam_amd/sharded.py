@@ -470,6 +470,11 @@ class ShardedFilter(object):
         self._complete()
         return self.f.motion(v, w, dt, z=self._my_rows(z), seed=seed, draw=draw)
 
+    def motion_odom(self, delta, alphas, z=None, seed=0, draw=0):
+        """motion for an odometry delta (rot1, trans, rot2) and the noise parameters (a1 .. a4): z and the Philox keys as there."""
+        self._complete()
+        return self.f.motion_odom(delta, alphas, z=self._my_rows(z), seed=seed, draw=draw)
+
     def _my_rows(self, z):
         if z is None:
             return None
@@ -682,12 +687,19 @@ class ShardedFilter(object):
                 f.adopt_from(R, recv, n_recv)
             self._recv_keepalive = recv if n_recv else None
 
-    def _complete_and_step_split(self, v, w, dt, seed, draw):
+    def _complete_and_step_split(self, v, w, dt, seed, draw, motion=None):
         """The pending exchange AND the motion + observe of the next step, overlapped: the particles that stay on this rank
         (output slots [a, b) of the new generation) are moved and observed while the migrating ones travel; the slots at
-        either end follow.  The staged scan must take the register route."""
+        either end follow.  The staged scan must take the register route.  motion: as step's."""
         with self._ctx():
             f, comm, W, R = self.f, self.comm, self.world, self.rank
+
+            def move(p0, p1):  # the particles [p0, p1) by the step's motion: the twist, an odometry delta, or none
+                if motion is None:
+                    f.motion_range(v, w, dt, seed, draw, p0, p1)
+                elif motion != "none":
+                    f.motion_odom_range(motion[1], motion[2], seed, draw, p0, p1)
+
             allr, send_counts, recv_counts, moving, a, b = self._read_plan()
             n_send, n_recv = sum(send_counts), sum(recv_counts)
             self.last_migrated = n_send
@@ -737,10 +749,10 @@ class ShardedFilter(object):
                     f.adopt_balanced(allr.reshape(-1), W, R, None, 0, 2)
                 else:
                     f.adopt_remote(R, None, 0)
-                f.motion_range(v, w, dt, seed, draw, 0, self.P)
+                move(0, self.P)
                 f.observe_staged_range(True, 0, self.P, True, True)
             else:
-                f.motion_range(v, w, dt, seed, draw, a, b)
+                move(a, b)
                 f.observe_staged_range(True, a, b, True, False)  # weight reset (:73) fused in; consumes the staged scan
                 if work is not None:
                     work.wait()  # the stream waits for the records, the host does not
@@ -748,8 +760,8 @@ class ShardedFilter(object):
                     f.adopt_balanced(allr.reshape(-1), W, R, recv, n_recv, 2)
                 else:
                     f.adopt_remote(R, recv, n_recv)
-                f.motion_range(v, w, dt, seed, draw, 0, a)
-                f.motion_range(v, w, dt, seed, draw, b, self.P)
+                move(0, a)
+                move(b, self.P)
                 f.observe_staged_range(True, 0, a, False, False)
                 f.observe_staged_range(True, b, self.P, False, True)
             self._recv_keepalive = recv if n_recv else None  # read by the launches above: freed in stream order later
@@ -802,19 +814,26 @@ class ShardedFilter(object):
 
         return torch.from_numpy(np.ascontiguousarray(a)).to(like.device)
 
-    def step(self, v, w, dt, blobs, u, z=None, seed=0, draw=0, ids=None, domain=_lib.PK_WEIGHTS_LINEAR):
+    def step(self, v, w, dt, blobs, u, z=None, seed=0, draw=0, ids=None, domain=_lib.PK_WEIGHTS_LINEAR, motion=None):
         """One cam_cb.  The host half of the scan upload (association tables) is done BEFORE the
-        previous step's exchange is completed, i.e. while the GPU is still busy with that step."""
+        previous step's exchange is completed, i.e. while the GPU is still busy with that step.
+        motion: None -- the twist (v, w, dt), as ever; ("odom", delta, alphas) -- an odometry delta in its place (v, w, dt are not
+        read); "none" -- observe and resample only (the particles were moved already: FastSLAM(motion="odometry"))."""
+        if not (motion is None or motion == "none" or (isinstance(motion, tuple) and len(motion) == 3 and motion[0] == "odom")):
+            raise ValueError("ShardedFilter.step: motion must be None, ('odom', delta, alphas) or 'none', not %r" % (motion,))
         staged = False
         if ids is None and hasattr(self.f, "stage_scan") and len(blobs) > 0:
             self.f.stage_scan(blobs)
             staged = True
         if (staged and self.split_step and z is None and self._pending is not None and hasattr(self.f, "staged_takes_regs")
                 and self.f.staged_takes_regs()):
-            self._complete_and_step_split(v, w, dt, seed, draw)
+            self._complete_and_step_split(v, w, dt, seed, draw, motion)
         else:
             self._complete()
-            self.f.motion(v, w, dt, z=self._my_rows(z), seed=seed, draw=draw)
+            if motion is None:
+                self.f.motion(v, w, dt, z=self._my_rows(z), seed=seed, draw=draw)
+            elif motion != "none":
+                self.f.motion_odom(motion[1], motion[2], z=self._my_rows(z), seed=seed, draw=draw)
             if staged:
                 self.f.observe_staged(fresh=True)  # weight reset (:73) fused into the observe kernels
                 self._recv_keepalive = None
