@@ -159,6 +159,27 @@ int pk_set_option(pk_filter* f, const char* name, int64_t value);
  * the general dense kernel (PK_ROUTE_DENSE), converting maps that are already loaded. */
 int pk_set_measurement_noise(pk_filter* f, const double Qt[16]);
 
+/* The measurement model of the filter's observes ("The bearing model").  It keeps no state of its own and may be
+ * changed at any time between scans.
+ *   PK_MODEL_REFERENCE (default)  the reference's, quirks included: what a filter that never asks computes, bit for bit.
+ *   PK_MODEL_BEARING              the textbook robot-frame bearing.  With wrap(a) = a - 2 pi rint(a / 2 pi), pse = atan2(dy, dx):
+ *       gate        |wrap(bearing - (pse - heading))| > 0.5 -> probability 0 (the colour gate is unchanged);
+ *       position    the blob's unit ray turned by the heading is the ray's world direction; closest point and 2x2 density as ever,
+ *                   without the reference's half-plane test and behind-the-ray branch (neither can fire behind the gate);
+ *       update      zhat0 = pse - heading, innovation wrap(bearing - zhat0), H's first row (-dy / q, dx / q); the colour block as ever;
+ *       weight      log w = -2 log 2 pi - 1/2 log det Q - 1/2 d' Q^-1 d, det Q = Q00 det(C + Qc); potential features and unmatched
+ *                   blobs weigh 0.1 as ever.
+ *     Its scans take the general kernels alone: PK_ROUTE_KNOWN_IDS with ids, else PK_ROUTE_ML_GENERAL (the association kernel, or the
+ *     brute-force one with "assoc_kernel" = 1, then k_observe); pk_associate runs the same model.  Motion, resampling, summaries, the
+ *     path, the map estimates and the new-landmark bookkeeping with its retirement are the same under both models.
+ *     PK_ERR_UNSUPPORTED while it is on: the dense layout (covariances or a Qt that couple position, bearing and colour) in
+ *     pk_observe* / pk_associate / pk_step*, and pk_observe_staged_range (the ranged and split observes of the sharded step).
+ * pk_set_measurement_model: PK_ERR_INVALID for any other value, PK_ERR_STATE inside a split observe; nothing changed either way. */
+#define PK_MODEL_REFERENCE 0
+#define PK_MODEL_BEARING 1
+int pk_set_measurement_model(pk_filter* f, int32_t model);
+int pk_measurement_model(const pk_filter* f, int32_t* model);
+
 /* FilterParticle.load_feature_list (prkt_core_v2.py:294-299) for every particle:
  * means[L*5] (x,y,r,g,b), covs[L*25] row-major 5x5, immutable[L] = Feature.__immutable__
  * (:883; NULL = all mutable).  update_count starts at 0.  Symmetric, block-diagonal covariances
@@ -719,6 +740,17 @@ enum {
   PK_MATH_COUNT = 11 /* one past the last op */
 };
 int pk_probe_math(int32_t device, int32_t op, int64_t n, const double* in, double* out);
+
+/* The same for the bearing model's primitives (PK_MODEL_BEARING), an entry point of their own: in[n][arity] -> out[n][outputs].
+ *   what  calls                    arity -> outputs
+ *   0     the match probabilities  23 -> 5   PK_MATH_MATCH's row; ux uy is the blob's ROBOT-frame unit ray, which the kernel turns by
+ *                                            the heading before it calls closest_point
+ *   1     the update               32 -> 17  PK_MATH_EKF_UPDATE's row with the heading behind sx sy:
+ *         in:  sx sy heading | the 14 landmark fields | count | blob bearing r g b | Qt as q00 rr rg rb gg gb bb | zhat0 | flags | prod_in
+ *              flags: bit 0 immutable, bit 1 zhat0 is passed as the known pk_atan2(dy, dx) (the heading is subtracted inside);
+ *              any other bit is PK_ERR_INVALID.  prod_in comes back unchanged.
+ * PK_ERR_INVALID for any other `what`. */
+int pk_probe_bearing(int32_t device, int32_t what, int64_t n, const double* in, double* out);
 
 /* ---- instrumentation ----------------------------------------------------------
  * Kernel launches of the enabled PK_T_* slots are bracketed by hipEvents on the handle's

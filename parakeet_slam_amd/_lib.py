@@ -32,6 +32,19 @@ PK_MATH_SHAPES = {PK_MATH_LOG_FEW_ULP: (1, 1), PK_MATH_PUB_LOG: (1, 1), PK_MATH_
                   PK_MATH_ROUND_DOWN_F32: (1, 1), PK_MATH_KEY: (1, 2), PK_MATH_FAR_BOUND: (14, 2), PK_MATH_PR_FROM_PARTS: (4, 1),
                   PK_MATH_EKF_UPDATE: (31, 17), PK_MATH_MATCH: (23, 5)}  # op -> (arity, outputs)
 PK_ABI_VERSION = 1
+PK_MODEL_REFERENCE, PK_MODEL_BEARING = 0, 1  # pk_set_measurement_model
+MEASUREMENT_MODELS = {"reference": PK_MODEL_REFERENCE, "bearing": PK_MODEL_BEARING}
+PK_BEARING_SHAPES = {0: (23, 5), 1: (32, 17)}  # pk_probe_bearing: what -> (arity, outputs)
+
+
+def measurement_model_code(model):
+    """The PK_MODEL_* value of a model's name ("reference", "bearing") or of the value itself; ValueError for anything else."""
+    if isinstance(model, str):
+        if model not in MEASUREMENT_MODELS:
+            raise ValueError("measurement_model: %r is neither %s" % (model, " nor ".join(repr(k) for k in MEASUREMENT_MODELS)))
+        return MEASUREMENT_MODELS[model]
+    return int(model)
+
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -55,6 +68,8 @@ SIGNATURES = {
     "pk_device_bytes": (C.c_int64, [_h]),
     "pk_set_option": (C.c_int, [_h, C.c_char_p, C.c_int64]),
     "pk_set_measurement_noise": (C.c_int, [_h, _dp]),
+    "pk_set_measurement_model": (C.c_int, [_h, C.c_int32]),
+    "pk_measurement_model": (C.c_int, [_h, C.POINTER(C.c_int32)]),
     "pk_upload_map": (C.c_int, [_h, _dp, _dp, _bp]),
     "pk_upload_poses": (C.c_int, [_h, _dp]),
     "pk_download_poses": (C.c_int, [_h, _dp]),
@@ -144,6 +159,7 @@ SIGNATURES = {
     "pk_adopt_particles": (C.c_int, [_h, _lp, C.c_void_p, C.c_int64]),
     "pk_probe": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pk_probe_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp]),
+    "pk_probe_bearing": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp]),
     "pk_enable_timing": (C.c_int, [_h, C.c_int32]),
     "pk_reset_timings": (C.c_int, [_h]),
     "pk_timings": (C.c_int, [_h, _dp, _lp]),
@@ -284,6 +300,15 @@ class DeviceFilter(object):
     def set_measurement_noise(self, Qt):
         q = f64(Qt, (16,))
         check(self._lib.pk_set_measurement_noise(self._h, dptr(q)))
+
+    def set_measurement_model(self, model):
+        """"reference" (default) or "bearing" -- or PK_MODEL_* -- for the observes that follow (pk_set_measurement_model)."""
+        check(self._lib.pk_set_measurement_model(self._h, measurement_model_code(model)))
+
+    def measurement_model(self):
+        m = C.c_int32()
+        check(self._lib.pk_measurement_model(self._h, C.byref(m)))
+        return {v: k for k, v in MEASUREMENT_MODELS.items()}[int(m.value)]
 
     def upload_map(self, means, covs, immutable=None):
         m = f64(means, (self.L, 5))
@@ -897,6 +922,17 @@ def probe_math(op, array, device=0):
     if op == PK_MATH_KEY:
         return out[:, 0].copy().view(np.uint64), out[:, 1].copy()
     return out[:, 0].copy() if outputs == 1 else out
+
+
+def probe_bearing(what, array, device=0):
+    """The bearing model's primitives on the rows of ``array`` on the GPU (pk_probe_bearing): what 0 the match probabilities
+    (n x 23 -> n x 5), 1 the update (n x 32 -> n x 17)."""
+    lib = load()
+    arity, outputs = PK_BEARING_SHAPES.get(int(what), (1, 1))
+    a = f64(array, (-1, arity))
+    out = np.empty((a.shape[0], outputs), dtype=np.float64)
+    check(lib.pk_probe_bearing(int(device), int(what), a.shape[0], dptr(a), dptr(out)))
+    return out
 
 
 class HostRng(object):

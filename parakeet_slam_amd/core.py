@@ -577,6 +577,12 @@ class FastSLAM(object):
     within 60 degrees of the heading, below 2 odom_min_trans always; the heading stays exact.  ``motion_update(twist)`` then only records the control, and ``cam_cb`` applies the scan to
     the poses as the last odometry message left them.  A robot that stood still launches nothing and consumes no draw.
     ``motion_model(particle, twist, dt)`` stays the twist model.  Works with devices=[several] too.
+
+    measurement_model="bearing" (default "reference": the reference's model, quirks included): the textbook robot-frame bearing
+    model -- wrapped bearing differences in the gate and the innovation, the blob's ray turned by the heading, H = (-dy / q, dx / q),
+    the Gaussian density with det Q as the weight (pk_set_measurement_model; DESIGN.md section 4, "The bearing model").  It is the
+    model that localises a robot that turns.  Its scans take the general kernels; one GPU only, the compact layout only.
+    ``save_state`` writes the model's name and ``load_state`` refuses a snapshot taken with the other one.
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -602,6 +608,10 @@ class FastSLAM(object):
                                  "(bookkeeping='device'): host lists cannot follow a particle from one GPU to another")
             if a["device"] not in (0, list(devices)[0]):
                 raise ValueError("FastSLAM: give either device= or devices=, not both")
+            if a["measurement_model"] != "reference":
+                raise ValueError("FastSLAM(devices=[...], measurement_model=%r): the bearing model runs on one GPU -- the ranged "
+                                 "and split observes of the sharded step have no kernel for it; an unknown name is refused the "
+                                 "same way" % (a["measurement_model"],))
             if a["settle_path"]:
                 raise ValueError("FastSLAM(devices=[...], settle_path=...): the path is recorded and settled on one GPU only -- "
                                  "lineages across ranks are out of scope")
@@ -628,7 +638,10 @@ class FastSLAM(object):
                  seed=0, publish_debug=None, new_landmarks=False, spare_landmarks=0, pair_threshold=30.0, devices=None,
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
-                 odom_min_trans=_odom.DEFAULT_MIN_TRANS):
+                 odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference"):
+        if measurement_model not in _lib.MEASUREMENT_MODELS:
+            raise ValueError("FastSLAM(measurement_model=%r): 'reference' (default) or 'bearing'" % (measurement_model,))
+        self._model = measurement_model
         self._motion, self._odom_alphas, self._odom_min_trans = _odom.check_keywords(motion, odom_alphas, odom_min_trans)
         self._odom_prev = None  # the last odometry pose (x, y, heading); None: the next message is the first
         if devices is not None and len(list(devices)) == 1:
@@ -654,6 +667,8 @@ class FastSLAM(object):
         self._pair_threshold = float(pair_threshold)
         self._L0 = L
         self._filter = _lib.DeviceFilter(self.num_particles, L + self._spare, device=self._device)
+        if self._model != "reference":
+            self._filter.set_measurement_model(self._model)
         if L + self._spare:
             means = np.zeros((L + self._spare, 5))
             covs = np.tile(np.identity(5).reshape(25), (L + self._spare, 1))
@@ -1149,7 +1164,8 @@ class FastSLAM(object):
                 path, poses=poses, means=m, covs=c, counts=k, Qt=np.asarray(self.Qt, dtype=np.float64),
                 immutable=np.array([bool(f.__immutable__) for f in self._features], dtype=np.uint8),
                 last_control=np.array([float(self.last_control.linear.x), float(self.last_control.angular.z)]),
-                last_update=float(self.last_update.to_sec()), draw=self._draw, **extra)
+                last_update=float(self.last_update.to_sec()), draw=self._draw,
+                measurement_model=np.array(self._model), **extra)
 
     def load_state(self, path):
         with self._lock:
@@ -1158,6 +1174,11 @@ class FastSLAM(object):
             if d["poses"].shape != (P, 4) or d["means"].shape != (P, L, 5):
                 raise ValueError("snapshot is for %s particles x %s landmarks, this filter has %d x %d"
                                  % (d["poses"].shape[0], d["means"].shape[1], P, L))
+            # (a snapshot from before the field: the reference model)
+            model = str(d["measurement_model"]) if "measurement_model" in d.files else "reference"
+            if model != self._model:
+                raise ValueError("snapshot: taken with measurement_model=%r, this filter runs %r -- the states of the two models "
+                                 "do not continue each other" % (model, self._model))
             if self._grow and "nl_offsets" not in d.files:
                 # (snapshots of before round 3 kept the bookkeeping as a pickled object array "new_landmarks": not read any
                 # more -- and a growing filter whose maps are replaced while its bookkeeping stays is inconsistent)

@@ -12,6 +12,14 @@ static int host_word(pk_filter* f, unsigned** p) {
   return PK_OK;
 }
 
+// The bearing model runs on the compact layout's general kernels of one whole filter: everything else says so here, once.
+int refuse_bearing(const pk_filter* f, const char* who, const char* what) {
+  if (f && f->model == PK_MODEL_BEARING)
+    return fail(PK_ERR_UNSUPPORTED, "%s: the bearing measurement model (pk_set_measurement_model) has no kernel for %s; "
+                                    "pk_set_measurement_model(f, PK_MODEL_REFERENCE) takes it", who, what);
+  return PK_OK;
+}
+
 static int ensure_scan_capacity(pk_filter* f, size_t bytes) {
   if (bytes <= f->scan_cap) return PK_OK;
   int rc;
@@ -228,6 +236,12 @@ static void build_blob_grid(const double* blobs, const double* dir, int B, bool 
   g.thr32 = thr < 3.0e38 ? (float)thr : INFINITY;
   const double thrb = (0.5 + 2.0 * std::ldexp(2.0 * Mb + 1.5, -24) + 1e-6) * (1.0 + 1e-6);
   g.thrb32 = thrb < 3.0e38 ? (float)thrb : INFINITY;
+  // The bearing model's screen: d' = fl(fl(bearing) - fl(e)) with e the expected bearing wrapped into [-pi, pi] in float64, then
+  // w' = fma(-k, fl(2 pi), d'), k = rint(d' fl(1 / 2 pi)).  |d' - d| <= 2^-24 2 (Mb + pi + 1); for a pair inside the gate k is the
+  // exact wrap's integer, |k| <= (Mb + pi) / 2 pi + 1, |fl(2 pi) - 2 pi| < 2^-22, and the fma rounds a value below 1 once:
+  // |w' - w| <= 2^-24 (2 (Mb + pi + 1) + 4 |k| + 1) <= 2^-24 (2.64 (Mb + pi) + 7).  Doubled, like the others.
+  const double thrbw = (0.5 + 2.0 * std::ldexp(2.64 * (Mb + 3.1415926535897932) + 7.0, -24) + 1e-6) * (1.0 + 1e-6);
+  g.thrb32w = thrbw < 3.0e38 ? (float)thrbw : INFINITY;
   auto cell_of = [&](int b) {
     int c[3];
     for (int k = 0; k < 3; ++k) {
@@ -390,6 +404,8 @@ static ScanPlan plan_scan(const pk_filter* f, int B, bool use_grid, int ncell, i
   ScanPlan p;
   if (!use_grid) return p;
   p.kind = ScanKind::General;
+  // the bearing model (pk_set_measurement_model) has the general kernels alone: no hand-off, no one-pass kernel, no stand-by launch
+  if (f->model == PK_MODEL_BEARING) return p;
   const int L = f->d.lay.L, Lp = f->d.lay.Lp;
   const bool sweep = L > kFastMaxL || f->opt.fast_observe >= 2;
   auto sweep_fits = [&] { return observe_sweep_plan(f->d, B).grid > 0; };
@@ -504,7 +520,11 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
   if ((rc = ct_end(f))) return rc;  // (the general association reads the slots' colour rows)
   Span t(f, PK_T_ASSOC);
   if (plan.kind == ScanKind::Brute) {
-    launch_assoc_brute(f->stream, f->d, al.blobs, al.dir, B, f->ids_dev);
+    launch_assoc_brute(f->stream, f->d, al.blobs, al.dir, B, f->ids_dev, f->model);
+    return PK_OK;
+  }
+  if (f->model == PK_MODEL_BEARING) {
+    launch_assoc_grid_bearing(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, f->ids_dev, finalize);
     return PK_OK;
   }
   FastHandoff fh{};
@@ -533,6 +553,7 @@ static int dense_observe(pk_filter* f, const double* blobs, int32_t B, const int
   int rc;
   const MapLayout& lay = f->d.lay;
   f->staged.valid = false;
+  if (int rb = refuse_bearing(f, "pk_observe", "the dense layout (covariances or a Qt that couple position, bearing and colour)")) return rb;
   if (dense_lds_bytes(lay.Lp, B) > kMaxDynLds)
     return fail(PK_ERR_UNSUPPORTED, "dense observe: %d landmarks and %d blobs need %zu bytes of LDS per particle, the workgroup has %zu",
                 lay.Lp, B, dense_lds_bytes(lay.Lp, B), (size_t)kMaxDynLds);
@@ -768,6 +789,7 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   if (f->dense) return dense_observe(f, blobs, B, ids, ids_out, reset, true);
   ObserveExtras ex;
   ex.reset = reset;
+  ex.model = f->model;
   if (ids) {
     if ((rc = ct_end(f))) return rc;  // (another route: k_observe streams whole slots)
     f->staged.valid = false;  // a staged ML scan does not survive another observe
@@ -937,6 +959,7 @@ int pk_staged_takes_regs(pk_filter* f) {
 int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1, int32_t first, int32_t last) {
   if (!f) return fail(PK_ERR_INVALID, "pk_observe_staged_range: NULL handle");
   if (int rc = refuse_path(f, "pk_observe_staged_range")) return rc;
+  if (int rc = refuse_bearing(f, "pk_observe_staged_range", "the ranged and split observes of the sharded step")) return rc;
   if (p0 < 0 || p1 < p0 || p1 > f->d.P) return fail(PK_ERR_INVALID, "pk_observe_staged_range: bad particle range [%lld, %lld)", (long long)p0, (long long)p1);
   if (f->grow_on) return fail(PK_ERR_STATE, "pk_observe_staged_range: the new-landmark bookkeeping (pk_grow_enable) runs behind whole observes (pk_observe / pk_observe_staged)");
   int rc;
@@ -998,6 +1021,20 @@ int pk_associate(pk_filter* f, const double* blobs, int32_t B, int32_t* ids_out)
   PK_LAUNCH_CHECK("pk_associate");
   PK_HIP(hipMemcpyAsync(ids_out, f->ids_dev, (size_t)f->d.P * B * 4, hipMemcpyDeviceToHost, f->stream));
   PK_HIP(hipStreamSynchronize(f->stream));
+  return PK_OK;
+}
+
+int pk_set_measurement_model(pk_filter* f, int32_t model) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_set_measurement_model: NULL handle");
+  if (model != PK_MODEL_REFERENCE && model != PK_MODEL_BEARING)
+    return fail(PK_ERR_INVALID, "pk_set_measurement_model: %d is neither PK_MODEL_REFERENCE (0) nor PK_MODEL_BEARING (1)", (int)model);
+  if (f->split.active) return fail(PK_ERR_STATE, "pk_set_measurement_model: a split observe is in progress");
+  f->model = model;  // (a staged scan stays: its tables serve both models)
+  return PK_OK;
+}
+int pk_measurement_model(const pk_filter* f, int32_t* model) {
+  if (!f || !model) return fail(PK_ERR_INVALID, "pk_measurement_model: NULL argument");
+  *model = f->model;
   return PK_OK;
 }
 

@@ -203,6 +203,7 @@ struct pk_filter {
   DeviceState d{};
   NoiseD qt{0.1, 0.1, 0.0, 0.0, 0.1, 0.0, 0.1};
   double qt16[16] = {0.1, 0, 0, 0, 0, 0.1, 0, 0, 0, 0, 0.1, 0, 0, 0, 0, 0.1};  // the same, dense (prkt_core_v2.py:50-53)
+  int model = PK_MODEL_REFERENCE;  // pk_set_measurement_model: what the observes compute (pk_math.hpp: kModelReference / kModelBearing)
   bool qt_dense = false;   // Qt couples bearing and colour or is not symmetric: only the dense kernels take it
   bool dense = false;      // maps in the dense 30-row layout (pk_layout.hpp): the general dense kernels run the observes
   std::vector<double> dense_staged;  // pk_stage_scan in dense mode: the blobs, kept on the host
@@ -517,6 +518,8 @@ int ct_maps_untouched(pk_filter* f, bool* untouched);
 void blob_directions(const double* blobs, int B, double* dir);
 int stage_ml_scan(pk_filter* f, const double* blobs, int B);
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out, bool reset);
+// what the bearing model (pk_set_measurement_model) has no kernels for, refused while it is on (a NULL handle passes)
+int refuse_bearing(const pk_filter* f, const char* who, const char* what);
 // pk_api_shard.hip
 int refuse_balanced(const pk_filter* f, const char* who);
 int refuse_path(const pk_filter* f, const char* who);

@@ -24,6 +24,7 @@ struct AssocArgs {
   int L, Lp, B;
 };
 
+template <int MODEL = kModelReference>
 __device__ __forceinline__ double match_probability_lazy(const double* f, const int* cnt, int Lp, int l,
                                                          Landmark<double>& lm, bool& have_cov, double sx,
                                                          double sy, double pse, const BlobT<double>& z,
@@ -40,14 +41,16 @@ __device__ __forceinline__ double match_probability_lazy(const double* f, const 
     lm.cbb = f[F_CBB * Lp + l];
     have_cov = true;
   }
-  double bp = 500.0 * prob_position_match(lm, sx, sy, pse, z.bearing, ux, uy);
+  double bp = 500.0 * prob_position_match<double, MODEL>(lm, sx, sy, pse, z.bearing, ux, uy);
   double cp = 500.0 * prob_color_match(lm, z.r, z.g, z.b);
   return bp * cp / 250000.0;
 }
 
-template <int PASS>
+// MODEL = kModelBearing: the wrapped gate, the blob's ray turned by the heading (ch, sn) = (cos sh, sin sh)
+template <int PASS, int MODEL = kModelReference>
 __device__ __forceinline__ void assoc_pass(const AssocArgs& a, const double* f, const int* cnt, double sx,
-                                           double sy, double sh, unsigned long long* best, int* bid) {
+                                           double sy, double sh, unsigned long long* best, int* bid, double ch = 1.0,
+                                           double sn = 0.0) {
   for (int l = threadIdx.x; l < a.L; l += blockDim.x) {
     Landmark<double> lm;
     lm.mx = f[F_MX * a.Lp + l];
@@ -60,10 +63,15 @@ __device__ __forceinline__ void assoc_pass(const AssocArgs& a, const double* f, 
     double eb = pse - sh;  // :408
     for (int b = 0; b < a.B; ++b) {
       BlobT<double> z{a.blobs[4 * b], a.blobs[4 * b + 1], a.blobs[4 * b + 2], a.blobs[4 * b + 3]};
-      if (fabs(z.bearing - eb) > 0.5) continue;                                    // :433
+      if constexpr (MODEL == kModelBearing) {
+        if (fabs(wrap_angle(z.bearing - eb)) > 0.5) continue;
+      } else {
+        if (fabs(z.bearing - eb) > 0.5) continue;                                  // :433
+      }
       if (fabs(color_distance2(lm.mr, lm.mg, lm.mb, z.r, z.g, z.b)) > 300.0) continue;  // :441
-      double pr = match_probability_lazy(f, cnt, a.Lp, l, lm, have_cov, sx, sy, pse, z, a.blobdir[2 * b],
-                                         a.blobdir[2 * b + 1]);
+      double ux = a.blobdir[2 * b], uy = a.blobdir[2 * b + 1];
+      if constexpr (MODEL == kModelBearing) rotate_ray(ux, uy, ch, sn, ux, uy);
+      double pr = match_probability_lazy<MODEL>(f, cnt, a.Lp, l, lm, have_cov, sx, sy, pse, z, ux, uy);
       if (!(pr > 0.0)) continue;
       unsigned long long bits = (unsigned long long)__double_as_longlong(pr);
       if (PASS == 0) {
@@ -75,7 +83,8 @@ __device__ __forceinline__ void assoc_pass(const AssocArgs& a, const double* f, 
   }
 }
 
-__global__ void __launch_bounds__(256) k_assoc_brute(AssocArgs a) {
+template <int MODEL>
+__device__ __forceinline__ void assoc_brute_body(const AssocArgs& a) {
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* best = reinterpret_cast<unsigned long long*>(smem);
   int* bid = reinterpret_cast<int*>(best + a.B);
@@ -88,17 +97,21 @@ __global__ void __launch_bounds__(256) k_assoc_brute(AssocArgs a) {
     best[b] = 0ull;
     bid[b] = INT_MAX;
   }
+  double ch = 1.0, sn = 0.0;
+  if constexpr (MODEL == kModelBearing) sincos(sh, &sn, &ch);
   __syncthreads();
-  assoc_pass<0>(a, f, cnt, sx, sy, sh, best, bid);
+  assoc_pass<0, MODEL>(a, f, cnt, sx, sy, sh, best, bid, ch, sn);
   __syncthreads();
-  assoc_pass<1>(a, f, cnt, sx, sy, sh, best, bid);
+  assoc_pass<1, MODEL>(a, f, cnt, sx, sy, sh, best, bid, ch, sn);
   __syncthreads();
   for (int b = threadIdx.x; b < a.B; b += blockDim.x)
     a.ids[(size_t)p * a.B + b] = best[b] != 0ull ? bid[b] + 1 : 0;
 }
+__global__ void __launch_bounds__(256) k_assoc_brute(AssocArgs a) { assoc_brute_body<kModelReference>(a); }
+__global__ void __launch_bounds__(256) k_assoc_brute_bearing(AssocArgs a) { assoc_brute_body<kModelBearing>(a); }
 
 void launch_assoc_brute(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev, int B,
-                        int32_t* ids_dev) {
+                        int32_t* ids_dev, int model) {
   if (d.P == 0 || B == 0) return;
   AssocArgs a;
   a.ss = slot_source(d);
@@ -116,11 +129,14 @@ void launch_assoc_brute(hipStream_t s, DeviceState& d, const double* blobs_dev, 
   const size_t lds = assoc_brute_lds_bytes(B);  // <= kMaxDynLds: checked by the caller
   static bool attr_set[kMaxDevices] = {false};
   if (first_time_on_this_device(attr_set)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_assoc_brute), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kMaxDynLds) != hipSuccess)
-      (void)hipGetLastError();
+    for (const void* fn : {reinterpret_cast<const void*>(k_assoc_brute), reinterpret_cast<const void*>(k_assoc_brute_bearing)})
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess)
+        (void)hipGetLastError();
   }
-  hipLaunchKernelGGL(k_assoc_brute, dim3((unsigned)d.P), dim3(256), lds, s, a);
+  if (model == kModelBearing)
+    hipLaunchKernelGGL(k_assoc_brute_bearing, dim3((unsigned)d.P), dim3(256), lds, s, a);
+  else
+    hipLaunchKernelGGL(k_assoc_brute, dim3((unsigned)d.P), dim3(256), lds, s, a);
 }
 
 
@@ -184,11 +200,15 @@ size_t blob_grid_table_bytes(int ncell, int B, int n9) {
 
 
 // probability_of_match (:383-455) of landmark l for the blob record rec = (bearing, r, g, b, ux, uy)
+// (MODEL = kModelBearing: the ray turned by the heading, (ch, sn) = (cos sh, sin sh))
+template <int MODEL = kModelReference>
 __device__ __forceinline__ double full_match_probability(const double* f, int Lp, int l, double sx, double sy,
-                                                         double sh, const double* rec) {
+                                                         double sh, const double* rec, double ch = 1.0, double sn = 0.0) {
   const Landmark<double> lm = load_landmark_nocount(f, Lp, l);
   BlobT<double> z{rec[0], rec[1], rec[2], rec[3]};
-  return probability_of_match(lm, sx, sy, sh, z, rec[4], rec[5]);
+  double ux = rec[4], uy = rec[5];
+  if constexpr (MODEL == kModelBearing) rotate_ray(ux, uy, ch, sn, ux, uy);
+  return probability_of_match<double, MODEL>(lm, sx, sy, sh, z, ux, uy);
 }
 
 constexpr int kCand = 4;
@@ -204,8 +224,11 @@ __device__ unsigned long long pk_stamp_acc[16];
 
 // GENERAL = false: S1 + hand-off only (light on registers); particles it flags are redone by
 // the GENERAL = true instance launched with only_flagged.
-template <int THREADS, bool DUP, bool GENERAL, int SLOTS>
-__global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
+// The body of k_assoc_grid and of k_assoc_grid_bearing, the GENERAL instance for the bearing model (MODEL = kModelBearing: both
+// bearing gates take the wrapped difference -- S1's fp32 screen against g.thrb32w --, the probabilities of S3 / S4 the turned ray).
+template <int THREADS, bool DUP, bool GENERAL, int SLOTS, int MODEL>
+__device__ __forceinline__ void assoc_grid_body(const AssocGridArgs& ga) {
+  static_assert(MODEL == kModelReference || GENERAL, "the bearing model has no hand-off instance");
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ int n_few, n_many, wg_flag;
   __shared__ long long s_row;
@@ -249,6 +272,8 @@ __global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
     const unsigned char* slot = a.ss.at(a.src[p]);
     const double* f = reinterpret_cast<const double*>(slot);
     const double sx = a.x[p], sy = a.y[p], sh = a.h[p];
+    double ch = 1.0, sn = 0.0;
+    if constexpr (MODEL == kModelBearing) sincos(sh, &sn, &ch);  // one per particle
     PK_STAMP(ts0)
     for (int t = threadIdx.x; t < B; t += THREADS) ccount[t] = 0;
     if (threadIdx.x == 0) {
@@ -283,7 +308,8 @@ __global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
       PK_STAMP(ta0)
       const double pse = pk_atan2(my - sy, mx - sx);
       const double eb = pse - sh;  // :408
-      const float mr32 = (float)mr, mg32 = (float)mg, mb32 = (float)mb, eb32 = (float)eb;
+      // (the bearing model's screen starts from the expected bearing wrapped in float64, so that its float is within pi whatever the heading)
+      const float mr32 = (float)mr, mg32 = (float)mg, mb32 = (float)mb, eb32 = (float)(MODEL == kModelBearing ? wrap_angle(eb) : eb);
       // same cell function as the host (floor((v - lo) * inv_h)): inside the colour gate
       // |dv| <= 17.3205 < 17.5, so the cell indices of blob and landmark differ by at most
       // one.  -1 / G mean "outside the grid": only the edge cell can hold a neighbour.
@@ -316,7 +342,15 @@ __global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
         const Float2 s01 = d01 * d01;
         const float cd32 = fmaf(d23.x, d23.x, s01.x + s01.y);
         // conservative fp32 gates; NaN/inf fall through to the exact float64 tests
-        return !(cd32 > g.thr32) && !(fabsf(d23.y) > g.thrb32);
+        if constexpr (MODEL == kModelBearing) {
+          // the difference wrapped in float32: off by the wrap's own error, which g.thrb32w allows for; a difference near an odd
+          // multiple of pi may wrap either way -- to about +-pi, outside the gate both ways
+          const float kf = rintf(d23.y * 0.15915494309189535f);
+          const float w32 = fmaf(-kf, 6.2831853071795862f, d23.y);
+          return !(cd32 > g.thr32) && !(fabsf(w32) > g.thrb32w);
+        } else {
+          return !(cd32 > g.thr32) && !(fabsf(d23.y) > g.thrb32);
+        }
       };
       auto prefilter = [&](int t) { return prefilter_q(rec32[t]); };
       unsigned pass[SLOTS / 2];  // the blobs that pass this landmark's gates (first SLOTS), two per word
@@ -324,7 +358,8 @@ __global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
       for (int j = 0; j < SLOTS / 2; ++j) pass[j] = 0xFFFFFFFFu;
       int npass = 0;
       auto exact_gates = [&](int tt, const double2& z01, const double2& z23) {
-        if (!(fabs(z01.x - eb) > 0.5) && !(fabs(color_distance2(mr, mg, mb, z01.y, z23.x, z23.y)) > 300.0)) {
+        const double delb = MODEL == kModelBearing ? wrap_angle(z01.x - eb) : z01.x - eb;
+        if (!(fabs(delb) > 0.5) && !(fabs(color_distance2(mr, mg, mb, z01.y, z23.x, z23.y)) > 300.0)) {
           const int n = atomicAdd(&ccount[tt], 1);
           if (GENERAL && n < 4) cand[4 * tt + n] = (unsigned short)l;  // the hand-off instance keeps no candidate lists
 #pragma unroll
@@ -541,7 +576,7 @@ __global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
       }
       if (valid) {
         lcand = cand[4 * t + k];
-        const double pr = full_match_probability(f, a.Lp, lcand, sx, sy, sh, ga.exact + 6 * (size_t)t);
+        const double pr = full_match_probability<MODEL>(f, a.Lp, lcand, sx, sy, sh, ga.exact + 6 * (size_t)t, ch, sn);
         if (pr > 0.0) {
           bits = (unsigned long long)__double_as_longlong(pr);
           atomicMax(&s3_best[slot], bits);
@@ -566,8 +601,8 @@ __global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
           continue;
         const double mx = f[F_MX * a.Lp + l2], my = f[F_MY * a.Lp + l2];
         const double eb = pk_atan2(my - sy, mx - sx) - sh;
-        if (fabs(zb - eb) > 0.5) continue;
-        const double pr = full_match_probability(f, a.Lp, l2, sx, sy, sh, rec);
+        if (fabs(MODEL == kModelBearing ? wrap_angle(zb - eb) : zb - eb) > 0.5) continue;
+        const double pr = full_match_probability<MODEL>(f, a.Lp, l2, sx, sy, sh, rec, ch, sn);
         if (pr > pm) {
           pm = pr;
           best = l2;
@@ -583,6 +618,15 @@ __global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
     PK_STAMP(ts7)
     PK_STAMP_ADD(9, ts6, ts7)
   }
+}
+
+template <int THREADS, bool DUP, bool GENERAL, int SLOTS>
+__global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
+  assoc_grid_body<THREADS, DUP, GENERAL, SLOTS, kModelReference>(ga);
+}
+template <int THREADS, bool DUP>
+__global__ void __launch_bounds__(THREADS) k_assoc_grid_bearing(AssocGridArgs ga) {
+  assoc_grid_body<THREADS, DUP, true, kFastSlots, kModelBearing>(ga);
 }
 
 #ifdef PK_STAMPS
@@ -601,11 +645,12 @@ size_t assoc_grid_lds_bytes(int ncell, int B, int n9) {
   return grid_cs_bytes(ncell) + (size_t)B * 30 + (size_t)n9 * 2 + 16;
 }
 
-template <int THREADS, bool DUP, bool GENERAL, int SLOTS>
-static void launch_assoc_grid_t(hipStream_t s, const AssocGridArgs& ga, size_t lds, int64_t P) {
+// KERNEL: an instance of k_assoc_grid or of k_assoc_grid_bearing, of THREADS lanes
+template <auto KERNEL, int THREADS>
+static void launch_assoc_grid_k(hipStream_t s, const AssocGridArgs& ga, size_t lds, int64_t P) {
   static bool attr_set[kMaxDevices] = {false};
   if (first_time_on_this_device(attr_set)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_assoc_grid<THREADS, DUP, GENERAL, SLOTS>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess)
       (void)hipGetLastError();  // leave no sticky error behind for other users of the runtime
   }
@@ -615,8 +660,7 @@ static void launch_assoc_grid_t(hipStream_t s, const AssocGridArgs& ga, size_t l
   static int asked_per_cu = 0;
   if (asked_lds != lds) {
     asked_lds = lds;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&asked_per_cu,
-                                                     reinterpret_cast<const void*>(k_assoc_grid<THREADS, DUP, GENERAL, SLOTS>),
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&asked_per_cu, reinterpret_cast<const void*>(KERNEL),
                                                      THREADS, lds) != hipSuccess) {
       (void)hipGetLastError();
       asked_per_cu = 0;
@@ -631,7 +675,11 @@ static void launch_assoc_grid_t(hipStream_t s, const AssocGridArgs& ga, size_t l
   }
   int64_t blocks = 256 * (int64_t)per_cu;
   if (blocks > P) blocks = P;
-  hipLaunchKernelGGL((k_assoc_grid<THREADS, DUP, GENERAL, SLOTS>), dim3((unsigned)blocks), dim3(THREADS), lds, s, ga);
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(THREADS), lds, s, ga);
+}
+template <int THREADS, bool DUP, bool GENERAL, int SLOTS>
+static void launch_assoc_grid_t(hipStream_t s, const AssocGridArgs& ga, size_t lds, int64_t P) {
+  launch_assoc_grid_k<k_assoc_grid<THREADS, DUP, GENERAL, SLOTS>, THREADS>(s, ga, lds, P);
 }
 
 void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
@@ -716,6 +764,44 @@ void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& gri
                        const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev, bool finalize,
                        const FastHandoff& fh) {
   launch_assoc_grid(s, d, B, grid, n9, tables_dev, exact_dev, ids_dev, finalize, fh, CandTable{});
+}
+
+// The bearing model: the general instance over every particle -- no hand-off, no candidate lists, no flags.
+void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9, const unsigned char* tables_dev,
+                               const double* exact_dev, int32_t* ids_dev, bool finalize) {
+  if (d.P == 0 || B == 0) return;
+  AssocGridArgs ga{};
+  AssocArgs& a = ga.a;
+  a.ss = slot_source(d);
+  a.count_off = d.lay.count_off;
+  a.src = d.src[d.cur];
+  a.x = d.x[d.cur];
+  a.y = d.y[d.cur];
+  a.h = d.h[d.cur];
+  a.ids = ids_dev;
+  a.L = d.lay.L;
+  a.Lp = d.lay.Lp;
+  a.B = B;
+  ga.g = grid;
+  ga.tables = tables_dev;
+  ga.exact = exact_dev;
+  ga.P = d.P;
+  ga.finalize = finalize ? 1 : 0;
+  ga.n9 = n9;
+  ga.cand_slots = kCandSlots;
+  const size_t lds = assoc_grid_lds_bytes(grid.ncell, B, n9);
+  const bool big = lds > 40 * 1024;  // as launch_assoc_grid sizes its general instance
+  if (n9 > 0) {
+    if (big)
+      launch_assoc_grid_k<k_assoc_grid_bearing<512, true>, 512>(s, ga, lds, d.P);
+    else
+      launch_assoc_grid_k<k_assoc_grid_bearing<256, true>, 256>(s, ga, lds, d.P);
+  } else {
+    if (big)
+      launch_assoc_grid_k<k_assoc_grid_bearing<512, false>, 512>(s, ga, lds, d.P);
+    else
+      launch_assoc_grid_k<k_assoc_grid_bearing<256, false>, 256>(s, ga, lds, d.P);
+  }
 }
 
 // ------------------------------------------------------------------ K2' candidate lists from a reference particle

@@ -135,6 +135,51 @@ __global__ void __launch_bounds__(256) k_probe_math(const double* __restrict__ i
   }
 }
 
+// The bearing model's primitives (pk_probe_bearing): what 0 the match probabilities, 1 the update -- the rows of PK_MATH_MATCH and
+// of PK_MATH_EKF_UPDATE with the heading behind the pose.
+constexpr int kBearingEkfIn = 32;
+template <int WHAT>
+__global__ void __launch_bounds__(256) k_probe_bearing(const double* __restrict__ in, double* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if constexpr (WHAT == 0) {
+    const double* r = in + (int64_t)kMatchIn * i;
+    const double sx = r[0], sy = r[1], heading = r[2];
+    const Landmark<double> lm = landmark_of_row(r + 3, 0);
+    const BlobT<double> z{r[17], r[18], r[19], r[20]};
+    double sn, ch, wx, wy;
+    sincos(heading, &sn, &ch);
+    rotate_ray(r[21], r[22], ch, sn, wx, wy);
+    const double pse = pk_atan2(lm.my - sy, lm.mx - sx);
+    double nx, ny;
+    closest_point<double, kModelBearing>(lm.mx, lm.my, sx, sy, wx, wy, nx, ny);
+    double* o = out + (int64_t)kMatchOut * i;
+    o[0] = probability_of_match<double, kModelBearing>(lm, sx, sy, heading, z, wx, wy);
+    o[1] = prob_position_match<double, kModelBearing>(lm, sx, sy, pse, z.bearing, wx, wy);
+    o[2] = prob_color_match(lm, z.r, z.g, z.b);
+    o[3] = nx;
+    o[4] = ny;
+  } else {
+    const double* r = in + (int64_t)kBearingEkfIn * i;
+    Landmark<double> lm = landmark_of_row(r + 3, (int)r[17]);
+    const BlobT<double> z{r[18], r[19], r[20], r[21]};
+    const Noise<double> qt = make_noise(r[22], r[23], r[24], r[25], r[26], r[27], r[28]);
+    const double pse = r[29];
+    const int flags = (int)r[30];
+    const bool immutable = (flags & 1) != 0;
+    double logw;
+    if (flags & 2)
+      logw = ekf_update<double, true, kModelBearing>(lm, r[0], r[1], z, qt, immutable, nullptr, &pse, nullptr, r[2]);
+    else
+      logw = ekf_update<double, true, kModelBearing>(lm, r[0], r[1], z, qt, immutable, nullptr, nullptr, nullptr, r[2]);
+    double* o = out + (int64_t)kEkfOut * i;
+    o[0] = logw;
+    row_of_landmark(lm, o + 1);
+    o[15] = (double)lm.count;
+    o[16] = r[31];
+  }
+}
+
 namespace {
 
 template <int OP>
@@ -209,5 +254,39 @@ extern "C" int pk_probe_math(int32_t device, int32_t op, int64_t n, const double
   if (e == hipSuccess) e = hipMemcpy(out, dev + n_in, n_out * sizeof(double), hipMemcpyDeviceToHost);
   (void)hipFree(dev);
   if (e != hipSuccess) return fail(PK_ERR_HIP, "pk_probe_math: %s", hipGetErrorString(e));
+  return PK_OK;
+}
+
+extern "C" int pk_probe_bearing(int32_t device, int32_t what, int64_t n, const double* in, double* out) {
+  if (!in || !out) return fail(PK_ERR_INVALID, "pk_probe_bearing: NULL argument");
+  if (what != 0 && what != 1) return fail(PK_ERR_INVALID, "pk_probe_bearing: what = %d is neither 0 (the match probabilities) nor 1 (the update)", what);
+  if (n < 0 || n > 2147483647LL) return fail(PK_ERR_INVALID, "pk_probe_bearing: n = %lld out of range", (long long)n);
+  const int arity = what == 0 ? pk::kMatchIn : pk::kBearingEkfIn, outputs = what == 0 ? pk::kMatchOut : pk::kEkfOut;
+  if (what == 1)
+    for (int64_t i = 0; i < n; ++i) {
+      const double fl = in[(size_t)i * arity + 30];
+      if (!(fl == 0.0 || fl == 1.0 || fl == 2.0 || fl == 3.0))
+        return fail(PK_ERR_INVALID, "pk_probe_bearing: row %lld: flags take bit 0 (immutable) and bit 1 (zhat0 known) only", (long long)i);
+    }
+  int ndev = pk_device_count();
+  if (ndev <= 0) return fail(PK_ERR_HIP, "pk_probe_bearing: no HIP device visible (the HIP path has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(PK_ERR_INVALID, "pk_probe_bearing: device %d of %d", device, ndev);
+  if (n == 0) return PK_OK;
+  PK_HIP(hipSetDevice(device));
+  const size_t n_in = (size_t)n * arity, n_out = (size_t)n * outputs;
+  double* dev = nullptr;
+  PK_HIP(hipMalloc((void**)&dev, (n_in + n_out) * sizeof(double)));
+  hipError_t e = hipMemcpy(dev, in, n_in * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (what == 0)
+      hipLaunchKernelGGL(pk::k_probe_bearing<0>, grid, dim3(256), 0, nullptr, dev, dev + n_in, n);
+    else
+      hipLaunchKernelGGL(pk::k_probe_bearing<1>, grid, dim3(256), 0, nullptr, dev, dev + n_in, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dev + n_in, n_out * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(dev);
+  if (e != hipSuccess) return fail(PK_ERR_HIP, "pk_probe_bearing: %s", hipGetErrorString(e));
   return PK_OK;
 }

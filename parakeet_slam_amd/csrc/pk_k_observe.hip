@@ -22,6 +22,7 @@ struct ObserveArgs {
   size_t slot_bytes, count_off;
   int32_t* src;  // in: slot of particle p in map_src; out: identity
   const double *x, *y;
+  const double* h;       // the bearing model's kernels alone read the headings
   double* logw;
   const double* blobs;   // B x 4
   const double* blobdir; // ML: B x 2 unit ray directions (closest_point :510)
@@ -44,12 +45,15 @@ struct ObserveArgs {
 // because the landmark's covariance is in registers here.  pr = (500 exp(a1)) (500 exp(a2))
 // / 250000 with a1, a2 the two log-pdfs; whenever a1 + a2 is far from the float64 underflow
 // edge the answer is known without evaluating a single exp/log; otherwise evaluate it
-// exactly as the reference does.  pse = atan2(f.my - sy, f.mx - sx).
+// exactly as the reference does.  pse = atan2(f.my - sy, f.mx - sx).  MODEL = kModelBearing: (ux, uy) is the world-frame ray and
+// there is no half-plane test.
+template <int MODEL = kModelReference>
 __device__ __forceinline__ bool match_is_positive(const Landmark<double>& f, double sx, double sy, double pse,
                                                   const BlobT<double>& z, double ux, double uy) {
-  if (fabs(pse - z.bearing) > Consts<double>::half_pi) return false;  // :473-475 -> bp = 0
+  if constexpr (MODEL == kModelReference)
+    if (fabs(pse - z.bearing) > Consts<double>::half_pi) return false;  // :473-475 -> bp = 0
   double nx, ny;
-  closest_point(f.mx, f.my, sx, sy, ux, uy, nx, ny);
+  closest_point<double, MODEL>(f.mx, f.my, sx, sy, ux, uy, nx, ny);
   const double ex = nx - f.mx, ey = ny - f.my;
   const double det2 = f.pxx * f.pyy - f.pxy * f.pxy;
   const double maha2 = (f.pyy * ex * ex - 2.0 * f.pxy * ex * ey + f.pxx * ey * ey) / det2;
@@ -75,10 +79,12 @@ __device__ __forceinline__ BlobT<double> load_blob(const double* blobs, int b) {
 // ML: the ids are tentative.  Association saw the state BEFORE any update (:84), so first
 // settle every blob of the chain against the untouched state (s_ids[b] = 0 drops it), then
 // apply the surviving ones sequentially.
-template <bool KNOWN>
+// MODEL = kModelBearing: (sh, ch, sn) = the particle's heading with its cosine and sine (one sincos per particle).
+template <bool KNOWN, int MODEL = kModelReference>
 __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, double sx, double sy,
                                               const ObserveArgs& a, const int32_t* first,
-                                              const int32_t* next, int32_t* s_ids, int32_t* gid) {
+                                              const int32_t* next, int32_t* s_ids, int32_t* gid, double sh = 0.0,
+                                              double ch = 1.0, double sn = 0.0) {
   double acc = 0.0;
   const int b0 = first[l];
   if (b0 < 0) return acc;
@@ -87,8 +93,9 @@ __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, doubl
   if (!KNOWN) {
     for (int b = b0; b >= 0; b = next[b]) {
       const BlobT<double> z = load_blob(a.blobs, b);
-      const double2 dir = *reinterpret_cast<const double2*>(a.blobdir + 2 * (size_t)b);
-      if (!match_is_positive(lm, sx, sy, pse, z, dir.x, dir.y)) {
+      double2 dir = *reinterpret_cast<const double2*>(a.blobdir + 2 * (size_t)b);
+      if constexpr (MODEL == kModelBearing) rotate_ray(dir.x, dir.y, ch, sn, dir.x, dir.y);
+      if (!match_is_positive<MODEL>(lm, sx, sy, pse, z, dir.x, dir.y)) {
         s_ids[b] = 0;
         gid[b] = 0;
       }
@@ -101,14 +108,20 @@ __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, doubl
       continue;
     }
     const BlobT<double> z = load_blob(a.blobs, b);
-    acc += ekf_update(lm, sx, sy, z, a.qt, imm, (EkfAux<double>*)nullptr, fresh ? &pse : (const double*)nullptr);
+    if constexpr (MODEL == kModelBearing)
+      acc += ekf_update<double, true, MODEL>(lm, sx, sy, z, a.qt, imm, (EkfAux<double>*)nullptr, fresh ? &pse : (const double*)nullptr,
+                                             (double*)nullptr, sh);
+    else
+      acc += ekf_update(lm, sx, sy, z, a.qt, imm, (EkfAux<double>*)nullptr, fresh ? &pse : (const double*)nullptr);
     fresh = imm;
   }
   return acc;
 }
 
-template <bool KNOWN, int NV>
-__global__ void __launch_bounds__(kObsThreads) k_observe(ObserveArgs a) {
+// The body of k_observe and of k_observe_bearing, its instance for the bearing model (a kernel of its own: the reference model's
+// kernels keep their names and what they compute).
+template <bool KNOWN, int NV, int MODEL>
+__device__ __forceinline__ void observe_body(const ObserveArgs& a) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ double red[kObsThreads / kWave];
   if (a.only_flagged && *a.n_flagged == 0u) return;  // workgroup-uniform: nobody was handed on
@@ -125,6 +138,11 @@ __global__ void __launch_bounds__(kObsThreads) k_observe(ObserveArgs a) {
   const int* sc = reinterpret_cast<const int*>(sslot + a.count_off);
   int* dc = reinterpret_cast<int*>(dslot + a.count_off);
   const double sx = a.x[p], sy = a.y[p];
+  double sh = 0.0, ch = 1.0, sn = 0.0;
+  if constexpr (MODEL == kModelBearing) {
+    sh = a.h[p];
+    sincos(sh, &sn, &ch);
+  }
   const int Lp = a.Lp;
 
   const int32_t* first = a.first;
@@ -186,8 +204,8 @@ __global__ void __launch_bounds__(kObsThreads) k_observe(ObserveArgs a) {
                          v[8].x, v[9].x, v[10].x, v[11].x, v[12].x, v[13].x, c.x};
       Landmark<double> Bq{v[0].y, v[1].y, v[2].y, v[3].y, v[4].y, v[5].y, v[6].y, v[7].y,
                           v[8].y, v[9].y, v[10].y, v[11].y, v[12].y, v[13].y, c.y};
-      if (l0 < a.L) acc += apply_blobs<KNOWN>(A, l0, sx, sy, a, first, next, s_ids_mut, gid_mut);
-      if (l0 + 1 < a.L) acc += apply_blobs<KNOWN>(Bq, l0 + 1, sx, sy, a, first, next, s_ids_mut, gid_mut);
+      if (l0 < a.L) acc += apply_blobs<KNOWN, MODEL>(A, l0, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
+      if (l0 + 1 < a.L) acc += apply_blobs<KNOWN, MODEL>(Bq, l0 + 1, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
       __builtin_nontemporal_store(d2v{A.mx, Bq.mx}, reinterpret_cast<d2v*>(df + (size_t)F_MX * Lp + l0));
       __builtin_nontemporal_store(d2v{A.my, Bq.my}, reinterpret_cast<d2v*>(df + (size_t)F_MY * Lp + l0));
       __builtin_nontemporal_store(d2v{A.mr, Bq.mr}, reinterpret_cast<d2v*>(df + (size_t)F_MR * Lp + l0));
@@ -208,7 +226,7 @@ __global__ void __launch_bounds__(kObsThreads) k_observe(ObserveArgs a) {
     // one landmark per lane: half the registers, twice the waves in flight
     for (int l = tid; l < Lp; l += kObsThreads) {
       Landmark<double> A = load_landmark(sf, sc, Lp, l);
-      if (l < a.L) acc += apply_blobs<KNOWN>(A, l, sx, sy, a, first, next, s_ids_mut, gid_mut);
+      if (l < a.L) acc += apply_blobs<KNOWN, MODEL>(A, l, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
       __builtin_nontemporal_store(A.mx, &df[(size_t)F_MX * Lp + l]);
       __builtin_nontemporal_store(A.my, &df[(size_t)F_MY * Lp + l]);
       __builtin_nontemporal_store(A.mr, &df[(size_t)F_MR * Lp + l]);
@@ -235,6 +253,15 @@ __global__ void __launch_bounds__(kObsThreads) k_observe(ObserveArgs a) {
   }
   __syncthreads();  // (the LDS tables and the reduction's scratch are the next particle's)
   }
+}
+
+template <bool KNOWN, int NV>
+__global__ void __launch_bounds__(kObsThreads) k_observe(ObserveArgs a) {
+  observe_body<KNOWN, NV, kModelReference>(a);
+}
+template <bool KNOWN, int NV>
+__global__ void __launch_bounds__(kObsThreads) k_observe_bearing(ObserveArgs a) {
+  observe_body<KNOWN, NV, kModelBearing>(a);
 }
 
 
@@ -305,6 +332,7 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
   a.src = d.src[d.cur];
   a.x = d.x[d.cur];
   a.y = d.y[d.cur];
+  a.h = d.h[d.cur];
   a.logw = d.logw[d.cur];
   a.blobs = blobs_dev;
   a.blobdir = blobdir_dev;
@@ -324,7 +352,20 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
   a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
   // (behind a one-pass kernel few particles, if any, are flagged: 4 096 workgroups walk the flags)
   const unsigned grid = (unsigned)(ex.only_flagged && d.P > 4096 ? 4096 : d.P);
-  if (ids_dev == nullptr && ex.single_sightings && !ex.only_flagged && d.lay.Lp <= 1024 && g_observe_nv == 0) {
+  if (ex.model == kModelBearing) {  // the bearing model: k_observe's two shapes, no loop-free single-sighting kernel
+    if (ids_dev == nullptr) {
+      hipLaunchKernelGGL((k_observe_bearing<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a);
+    } else {
+      const size_t lds = observe_general_lds_bytes(d.lay.Lp, B);  // <= kMaxDynLds: checked by the caller
+      static bool attr_set[kMaxDevices] = {false};
+      if (first_time_on_this_device(attr_set)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_observe_bearing<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kMaxDynLds) != hipSuccess)
+          (void)hipGetLastError();
+      }
+      hipLaunchKernelGGL((k_observe_bearing<false, 1>), dim3(grid), dim3(kObsThreads), lds, s, a);
+    }
+  } else if (ids_dev == nullptr && ex.single_sightings && !ex.only_flagged && d.lay.Lp <= 1024 && g_observe_nv == 0) {
     if (d.lay.Lp <= 256)
       hipLaunchKernelGGL((k_observe_single<256>), dim3((unsigned)d.P), dim3(256), 0, s, a);
     else if (d.lay.Lp <= 512)

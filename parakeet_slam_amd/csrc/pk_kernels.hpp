@@ -101,7 +101,7 @@ void launch_reset_weights(hipStream_t s, DeviceState& d);
 // K2: maximum-likelihood association -> ids[P*B]
 // (a) reference kernel: every (landmark, blob) pair is gate-tested
 void launch_assoc_brute(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev,
-                        int B, int32_t* ids_dev);
+                        int B, int32_t* ids_dev, int model = 0);
 // (b) production kernel: blobs bucketed on the host into a 3-D colour grid whose cell edge
 // exceeds the colour gate radius sqrt(300), so a landmark only meets the blobs of its 27
 // neighbouring cells.  Tables (device): start u16[ncell+1] (16-byte padded) | rec32
@@ -116,6 +116,7 @@ struct BlobGrid {
   int ncell;
   float thr32;   // conservative fp32 pre-filter threshold for the colour gate (300)
   float thrb32;  // conservative fp32 pre-filter threshold for the bearing gate (0.5)
+  float thrb32w; // ... for the bearing model's gate, whose fp32 screen wraps the difference (the wrap's own error on top)
 };
 constexpr double kGridCell = 17.5;  // > sqrt(300) = 17.3205 (prkt_core_v2.py:441)
 constexpr int kGridMax = 16;
@@ -183,6 +184,7 @@ struct ObserveExtras {
   const double* ctab = nullptr;                 // k_step_pub's 512-lane instances in table mode: the colour table (ColourTable below), its
   int ctab_depth = 0;                           //   depth, and where the kernel leaves the highest level it read
   unsigned* ctab_max = nullptr;
+  int model = 0;                                // launch_observe: the measurement model (pk_math.hpp: kModelReference / kModelBearing)
   int lean = 0;                                 // k_step_pub<2, 512>: lean groups take the lean body (option "pub_lean"); the scan's
   unsigned* lean_stats = nullptr;               //   figures (k_cand_entries), where the kernel counts the pairs that fell back: [6]
 };
@@ -207,6 +209,9 @@ constexpr int kFastMaxL = 512;  // k_observe_fast / k_step_fused keep a particle
 void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
                        const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev,
                        bool finalize, const FastHandoff& fh);
+// the bearing model's association (pk_math.hpp: kModelBearing): the general instance alone, every particle
+void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
+                               const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev, bool finalize);
 // ML observe for L <= kFastMaxL straight from the hand-off: contested blobs are settled here,
 // with the landmark state in registers.  Particles flagged in fh.pflag are skipped (the general
 // k_observe, launched with only_flagged, takes them).

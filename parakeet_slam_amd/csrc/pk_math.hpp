@@ -164,13 +164,39 @@ __device__ __forceinline__ double pk_atan2(double y, double x) {
 #endif
 }
 
+// The measurement model a filter runs (pk_set_measurement_model; DESIGN.md section 4, "The bearing model").  kModelReference is the
+// reference's, quirks and all, and what every function below computes unless told otherwise; kModelBearing is the textbook
+// robot-frame bearing: the gate and the innovation take the WRAPPED difference to atan2(dy, dx) - heading, the blob's ray is turned
+// into the world frame before the closest point is taken, the Jacobian is (-dy / q, dx / q) and the weight is the Gaussian density
+// with det Q.  The model is a template parameter resolved with `if constexpr`: the reference model's code is what it was.
+constexpr int kModelReference = 0;
+constexpr int kModelBearing = 1;
+
+// a - 2 pi rint(a / 2 pi), each operation rounded by itself (no contraction: the host reference forms it the same way).  Returns a
+// unchanged, exactly, whenever |a| < pi (rint gives 0).
+__device__ __forceinline__ double wrap_angle(double a) {
+  const double k = rint(a / Consts<double>::two_pi);
+  return __dsub_rn(a, __dmul_rn(Consts<double>::two_pi, k));
+}
+
+// The blob's robot-frame unit ray (ux, uy) turned by the heading (ch, sh) = (cos h, sin h): the ray's direction in the world frame.
+__device__ __forceinline__ void rotate_ray(double ux, double uy, double ch, double sh, double& wx, double& wy) {
+  wx = ux * ch - uy * sh;
+  wy = ux * sh + uy * ch;
+}
+
 // closest_point, prkt_core_v2.py:496-522.  (ux, uy) = unit((cos b, sin b, 0)),
 // utils.py:68-76, precomputed per blob.
-template <typename T>
+// MODEL = kModelBearing: (ux, uy) is the ray in the world frame and the behind-the-ray branch is gone (behind the bearing gate the
+// ray and the landmark are at most 0.5 rad apart).
+template <typename T, int MODEL = kModelReference>
 __device__ __forceinline__ void closest_point(T fx, T fy, T sx, T sy, T ux, T uy, T& nx, T& ny) {
   T ox = fx - sx, oy = fy - sy;
   T mag = ox * ux + oy * uy;  // dot_product, utils.py:37-43
-  if (mag < T(0)) {           // :515-516 behind the ray: the robot position itself
+  if constexpr (MODEL == kModelBearing) {
+    nx = sx + ux * mag;
+    ny = sy + uy * mag;
+  } else if (mag < T(0)) {    // :515-516 behind the ray: the robot position itself
     nx = sx;
     ny = sy;
   } else {
@@ -180,17 +206,18 @@ __device__ __forceinline__ void closest_point(T fx, T fy, T sx, T sy, T ux, T uy
 }
 
 // prob_position_match, prkt_core_v2.py:457-494 (scipy multivariate_normal.pdf, k = 2,
-// in closed form).  pse = atan2(fy - sy, fx - sx).
-template <typename T>
+// in closed form).  pse = atan2(fy - sy, fx - sx).  MODEL = kModelBearing: (ux, uy) in the world frame, no half-plane test.
+template <typename T, int MODEL = kModelReference>
 __device__ __forceinline__ T prob_position_match(const Landmark<T>& f, T sx, T sy, T pse, T bearing,
                                                  T ux, T uy, T* near_xy = nullptr) {
   T nx, ny;
-  closest_point(f.mx, f.my, sx, sy, ux, uy, nx, ny);
+  closest_point<T, MODEL>(f.mx, f.my, sx, sy, ux, uy, nx, ny);
   if (near_xy) {
     near_xy[0] = nx;
     near_xy[1] = ny;
   }
-  if (fabs(pse - bearing) > Consts<T>::half_pi) return T(0);  // :473-475, frames mixed as in the reference
+  if constexpr (MODEL == kModelReference)
+    if (fabs(pse - bearing) > Consts<T>::half_pi) return T(0);  // :473-475, frames mixed as in the reference
   T ex = nx - f.mx, ey = ny - f.my;
   T det = f.pxx * f.pyy - f.pxy * f.pxy;
   T maha = (f.pyy * ex * ex - T(2) * f.pxy * ex * ey + f.pxx * ey * ey) / det;
@@ -213,16 +240,17 @@ __device__ __forceinline__ T color_distance2(T mr, T mg, T mb, T r, T g, T b) {
   return dr * dr + dg * dg + db * db;  // :425-427
 }
 
-// probability_of_match, prkt_core_v2.py:383-455.
-template <typename T>
+// probability_of_match, prkt_core_v2.py:383-455.  MODEL = kModelBearing: the difference is wrapped, (ux, uy) is the world-frame ray.
+template <typename T, int MODEL = kModelReference>
 __device__ __forceinline__ T probability_of_match(const Landmark<T>& f, T sx, T sy, T heading,
                                                   const BlobT<T>& z, T ux, T uy) {
   T pse = pk_atan2(f.my - sy, f.mx - sx);
   T delb = z.bearing - (pse - heading);  // :408-415, never wrapped (:416-423 commented out)
+  if constexpr (MODEL == kModelBearing) delb = wrap_angle(delb);
   if (fabs(delb) > T(0.5)) return T(0);  // :433
   T cd = color_distance2(f.mr, f.mg, f.mb, z.r, z.g, z.b);
   if (fabs(cd) > T(300)) return T(0);  // :441
-  T bp = T(500) * prob_position_match(f, sx, sy, pse, z.bearing, ux, uy);  // :439
+  T bp = T(500) * prob_position_match<T, MODEL>(f, sx, sy, pse, z.bearing, ux, uy);  // :439
   T cp = T(500) * prob_color_match(f, z.r, z.g, z.b);                     // :446
   return bp * cp / T(250000);                                            // :455
 }
@@ -349,14 +377,18 @@ __device__ __forceinline__ Sym3<T> colour_block_step(const Sym3<T>& C, const Noi
 }
 // COLOUR = false (k_step_pub in table mode, a landmark's only update of the scan): the colour block is left as it was -- the caller
 // neither stores it nor reads it again; everything else as ever.
-template <typename T, bool COLOUR = true>
+// MODEL = kModelBearing (no fro_prod): zhat0 = atan2(dy, dx) - heading (zhat0_known still holds the atan2), the innovation is
+// wrapped, H's first row is (-dy / q, dx / q), and the weight is the density: -2 log 2 pi - 1/2 log(Q00 det(C + Qc)) - 1/2 d' Q^-1 d.
+template <typename T, bool COLOUR = true, int MODEL = kModelReference>
 __device__ __forceinline__ T ekf_update(Landmark<T>& f, T sx, T sy, const BlobT<T>& z,
                                         const Noise<T>& qt, bool immutable,
-                                        EkfAux<T>* aux = nullptr, const T* zhat0_known = nullptr, T* fro_prod = nullptr) {
+                                        EkfAux<T>* aux = nullptr, const T* zhat0_known = nullptr, T* fro_prod = nullptr,
+                                        T heading = T(0)) {
   T dx = f.mx - sx, dy = f.my - sy;
   // :871 world frame: the heading is NOT subtracted here.  A caller that already holds
   // atan2(dy, dx) for this very state passes it in (one float64 atan2 saved).
   T zhat0 = zhat0_known ? *zhat0_known : pk_atan2(dy, dx);
+  if constexpr (MODEL == kModelBearing) zhat0 = zhat0 - heading;
   T q = dx * dx + dy * dy;  // :785
   T h0, h1;                 // :789/:795 -- (dy/q, dx/q): the reference's signs, not the textbook's
   if (q == T(0)) {          // ZeroDivisionError branch :790,:796
@@ -366,6 +398,7 @@ __device__ __forceinline__ T ekf_update(Landmark<T>& f, T sx, T sy, const BlobT<
     T iq = T(1) / q;
     h0 = dy * iq;
     h1 = dx * iq;
+    if constexpr (MODEL == kModelBearing) h0 = -h0;
   }
   T a0 = f.pxx * h0 + f.pxy * h1;  // Pxy h
   T a1 = f.pxy * h0 + f.pyy * h1;
@@ -376,6 +409,7 @@ __device__ __forceinline__ T ekf_update(Landmark<T>& f, T sx, T sy, const BlobT<
   T iq00 = T(1) / q00;
 
   T d0 = z.bearing - zhat0;  // :846/:911 innovation, not wrapped
+  if constexpr (MODEL == kModelBearing) d0 = wrap_angle(d0);
   T d1 = z.r - f.mr, d2 = z.g - f.mg, d3 = z.b - f.mb;
 
   // importance_factor :844-849: (2 pi ||Q||_F)^-1/2 exp(-1/2 d' Q^-1 d) with the
@@ -390,7 +424,10 @@ __device__ __forceinline__ T ekf_update(Landmark<T>& f, T sx, T sy, const BlobT<
   // fro_prod (the one-pass kernels): the caller takes ONE logarithm, of the product of the norms of all the updates of its lane,
   // -1/4 log(prod) -- the logarithm is 45 of an update's 300 instructions; here the factor is multiplied in and the term left out
   T logw;
-  if (fro_prod) {
+  if constexpr (MODEL == kModelBearing) {
+    logw = T(-2) * Consts<T>::log_two_pi - T(0.5) * log_few_ulp(q00 * detc) - T(0.5) * maha;
+    if (f.count & kPotentialBit) logw = (T)Consts<double>::log_no_match;
+  } else if (fro_prod) {
     logw = T(-0.5) * Consts<T>::log_two_pi - T(0.5) * maha;
     if (f.count & kPotentialBit)
       logw = (T)Consts<double>::log_no_match;  // :111-112 "update as if the feature not seen"

@@ -653,12 +653,16 @@ class ShardedFastSLAM(object):
                 path, poses=poses, means=m, covs=c, counts=k, Qt=np.asarray(self.Qt, dtype=np.float64),
                 immutable=np.array([bool(f.__immutable__) for f in self._features], dtype=np.uint8),
                 last_control=np.array([float(self.last_control.linear.x), float(self.last_control.angular.z)]),
-                last_update=float(self.last_update.to_sec()), draw=self._draw, **extra)
+                last_update=float(self.last_update.to_sec()), draw=self._draw,
+                measurement_model=np.array("reference"), **extra)  # (the bearing model runs on one GPU: FastSLAM refuses it here)
 
     def load_state(self, path):
         with self._lock:
             self._check_open()
             d = np.load(path, allow_pickle=False)
+            if "measurement_model" in d.files and str(d["measurement_model"]) != "reference":  # as FastSLAM.load_state
+                raise ValueError("snapshot: taken with measurement_model=%r, this filter runs 'reference' -- the states of the two "
+                                 "models do not continue each other" % str(d["measurement_model"]))
             P, L, Pl = self.num_particles, self._L, self._P_local
             if d["poses"].shape != (P, 4) or d["means"].shape != (P, L, 5):
                 raise ValueError("snapshot is for %s particles x %s landmarks, this filter has %d x %d"
