@@ -65,7 +65,9 @@ enum {
   PK_T_RESAMPLE = 4,
   PK_T_SUMMARY = 5,
   PK_T_MATERIALISE = 6,
-  PK_T_COUNT = 7
+  PK_T_PROPOSE = 7, /* k_propose (pk_propose, pk_propose_odom) */
+  PK_T_COUNT = 8    /* was 7 before PK_T_PROPOSE was appended: pk_timings writes PK_T_COUNT entries into both of its arrays, so a
+                     * caller compiled against the shorter enum must be rebuilt (or pass arrays of at least 8) */
 };
 
 typedef struct pk_filter pk_filter; /* opaque */
@@ -552,6 +554,50 @@ int pk_motion_odom_range(pk_filter* f, const double delta[3], const double alpha
 int pk_step_odom(pk_filter* f, const double delta[3], const double alpha[4], const double* z, uint64_t seed, uint64_t draw,
                  const double* blobs, int32_t num_blobs, const int32_t* ids, double u, int32_t weight_domain, double threshold);
 
+/* ---- the measurement-informed proposal (FastSLAM 2.0 sampling) ----
+ * pk_motion + pk_observe draw every pose from the motion model alone and let the scan only weigh it (FastSLAM 1.0).  These calls
+ * draw it from the motion model CONDITIONED on the scan, in the space of the three standard normals xi the motion kernels consume
+ * (prior N(0, I)); s = the sigmas of the launch (pk_motion's sd, sh, sh; pk_odom_sigmas), g = the motion model as it stands:
+ *   1. predicted pose x^ = g(x-, u, 0): the same kernel with normals 0.
+ *   2. G = d pose / d (s . xi) at 0, closed form, h1 the heading the translation is made along:
+ *        twist     h1 = h^ - w dt / 2, ds = v dt: columns (cos h1, sin h1, 0), (-ds sin h1, ds cos h1, 1), (0, 0, 1)
+ *        odometry  h1 = h^ - rot2, t = trans:     columns (t sin h1, -t cos h1, -1), (-cos h1, -sin h1, 0), (0, 0, -1)
+ *   3. association at x^ (the bearing model's kernels, or ids); tentative ids are settled there against the untouched landmarks,
+ *      a dropped id becomes 0.
+ *   4. every settled match b -> j, j not potential, against j's state BEFORE the scan (a landmark matched by several blobs gives
+ *      each of them against that same state): dx = fx - x^, dy = fy - y^, q = dx^2 + dy^2, nu = wrap(beta - (atan2(dy, dx) - h^)),
+ *      h_x = (dy / q, -dx / q, -1), h_m = (-dy / q, dx / q) (both 0 at q = 0), sigma^2 = h_m' P h_m + Q00, a = s . (G' h_x);
+ *      Lambda += a a' / sigma^2, eta += a nu / sigma^2, c += nu^2 / sigma^2, l += log sigma^2,
+ *      kappa += log det(C + Qc) + d_c' (C + Qc)^-1 d_c, n += 1.
+ *   5. Lambda <- I + Lambda = R R' (Cholesky), m = Lambda^-1 eta; xi = m + R^-T z, z the normals the motion kernel would have drawn
+ *      (z[3 p ..], or the Philox draws of (particle, seed, draw)); the weight increment
+ *        dlogw = -2 n log 2 pi - (l + log det Lambda) / 2 - (c - eta' m) / 2 - kappa / 2 + (unmatched + potential matches) log 0.1
+ *      is the Gaussian marginal of the stacked innovations under the joint linearisation.  No settled match: xi = z bit for bit.
+ *   6. the sampled pose is the motion kernel's for x- with normals xi, bit for bit (pk_motion / pk_motion_odom with z = xi).
+ *   7. the landmarks are updated at the sampled pose by the bearing model's EKF with the settled ids, in scan order; the log-weight
+ *      becomes (fresh ? 0 : old) + dlogw (the updates' own importance factors are not added).
+ * pk_propose        one pk_motion(v, w, dt, z, seed, draw) plus one pk_observe(blobs, num_blobs, ids, ids_out) (fresh != 0:
+ *                   pk_observe_fresh) under that rule.  No resample: pk_resample, pk_resample_adaptive, the path and the summaries
+ *                   follow as ever.  pk_observe_route: PK_ROUTE_KNOWN_IDS with ids, else PK_ROUTE_ML_GENERAL.  k_propose is timed in
+ *                   PK_T_PROPOSE, the rest in the spans of the plain calls.
+ * pk_propose_odom   the same for an odometry delta: pk_motion_odom(delta, alpha, z, seed, draw).
+ * pk_proposal_download  the last call's per-particle results: xi[P][3], dlogw[P], used[P] (the matches of step 4); any may be NULL.
+ *                   PK_ERR_STATE before the first call.
+ * The first call allocates 84 P bytes of state (pk_device_bytes: ten rows of P doubles, one of P int32).  The scan itself uses the
+ * buffers a pk_observe of the same scan uses -- the id table of a maximum-likelihood scan, and the per-scan block, which with supplied
+ * ids also carries the id row (4 num_blobs bytes more than pk_observe's, where that makes the block grow).  A filter that never
+ * calls them allocates and launches what it did.  The limits of a maximum-likelihood pk_observe (65 535 blobs, the LDS chains of
+ * landmarks + 2 x blobs) hold for maximum-likelihood scans here; supplied ids have neither.
+ * Refused, nothing changed -- PK_ERR_UNSUPPORTED: a filter not on PK_MODEL_BEARING (the reference model's Jacobian is not one), the
+ * dense layout, growing maps or retirement (pk_grow_enable, pk_grow_retire), a shard of a sharded filter or a split step in progress;
+ * PK_ERR_STATE: a staged scan in flight (pk_stage_scan), no map; PK_ERR_INVALID: the arguments, as pk_motion / pk_motion_odom /
+ * pk_observe refuse them. */
+int pk_propose(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
+               int32_t num_blobs, const int32_t* ids, int32_t fresh, int32_t* ids_out);
+int pk_propose_odom(pk_filter* f, const double delta[3], const double alpha[4], const double* z, uint64_t seed, uint64_t draw,
+                    const double* blobs, int32_t num_blobs, const int32_t* ids, int32_t fresh, int32_t* ids_out);
+int pk_proposal_download(pk_filter* f, double* xi, double* dlogw, int32_t* used);
+
 /* ---- sharded (multi-GPU) resampling: see DESIGN.md section 6 -------------------
  * Particles are sharded contiguously over one process per GPU; global particle index =
  * global_offset + local index.  The collectives themselves are the caller's
@@ -758,6 +804,7 @@ int pk_probe_bearing(int32_t device, int32_t what, int64_t n, const double* in, 
  * counts per PK_T_* slot since the last pk_reset_timings. */
 int pk_enable_timing(pk_filter* f, int32_t mask);
 int pk_reset_timings(pk_filter* f);
+/* (Both arrays hold PK_T_COUNT entries -- 8 since PK_T_PROPOSE was appended, 7 before: see the enum.) */
 int pk_timings(pk_filter* f, double ms[PK_T_COUNT], int64_t launches[PK_T_COUNT]);
 /* Algorithmic HBM bytes of one observe launch (14 scalars read + 14 written per
  * particle.landmark) and the bytes the layout actually moves (adds update_count, ids). */

@@ -22,7 +22,7 @@ PK_WEIGHTS_LINEAR, PK_WEIGHTS_LOG = 0, 1
 PK_PATH_UNIFORM = 2  # pk_path_settle's third weighting: every current particle counts once
 PK_MAP_UNIFORM, PK_MAP_WEIGHTED = mapsum.UNIFORM, mapsum.WEIGHTED
 PK_LANDMARK_POTENTIAL = 0x40000000  # flag in a landmark's count word: potential feature (prkt_core_v2.py:109-118)
-PK_T_NAMES = ("motion", "assoc", "observe", "weights", "resample", "summary", "materialise")
+PK_T_NAMES = ("motion", "assoc", "observe", "weights", "resample", "summary", "materialise", "propose")
 PK_T_COUNT = len(PK_T_NAMES)
 PK_PROBE_LEN = 79
 (PK_MATH_LOG_FEW_ULP, PK_MATH_PUB_LOG, PK_MATH_PUB_RECIP, PK_MATH_ATAN2, PK_MATH_ROUND_DOWN_F32, PK_MATH_KEY, PK_MATH_FAR_BOUND,
@@ -118,6 +118,9 @@ SIGNATURES = {
     "pk_odom_delta": (C.c_int, [_dp, _dp, C.c_double, _dp]),
     "pk_odom_sigmas": (C.c_int, [_dp, _dp, _dp]),
     "pk_motion_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64]),
+    "pk_propose": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_int32, _ip]),
+    "pk_propose_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_int32, _ip]),
+    "pk_proposal_download": (C.c_int, [_h, _dp, _dp, _ip]),
     "pk_motion_odom_range": (C.c_int, [_h, _dp, _dp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64]),
     "pk_step_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_double, C.c_int32, C.c_double]),
     "pk_shard_max_logw": (C.c_int, [_h, _dp]),
@@ -361,6 +364,36 @@ class DeviceFilter(object):
         d, a = f64(delta, (3,)), f64(alphas, (4,))
         zz = f64(z, (self.P, 3)) if z is not None else None
         check(self._lib.pk_motion_odom(self._h, dptr(d), dptr(a), dptr(zz), int(seed), int(draw)))
+
+    def propose(self, v, w, dt, blobs, z=None, seed=0, draw=0, ids=None, return_ids=False, fresh=False):
+        """One motion(v, w, dt, z, seed, draw) plus one observe(blobs, ids) with every pose drawn from the motion model conditioned
+        on the scan (FastSLAM 2.0; bearing model only): pk_propose."""
+        b = f64(blobs).reshape(-1, 4)
+        B = b.shape[0]
+        zz = f64(z, (self.P, 3)) if z is not None else None
+        i = np.ascontiguousarray(ids, dtype=np.int32).reshape(B) if ids is not None else None
+        out = np.empty((self.P, B), dtype=np.int32) if return_ids else None
+        check(self._lib.pk_propose(self._h, float(v), float(w), float(dt), dptr(zz), int(seed), int(draw), dptr(b), B, iptr(i),
+                                   1 if fresh else 0, iptr(out)))
+        return out
+
+    def propose_odom(self, delta, alphas, blobs, z=None, seed=0, draw=0, ids=None, return_ids=False, fresh=False):
+        """propose for an odometry delta (rot1, trans, rot2) with the noise parameters (a1, a2, a3, a4): pk_propose_odom."""
+        d, a = f64(delta, (3,)), f64(alphas, (4,))
+        b = f64(blobs).reshape(-1, 4)
+        B = b.shape[0]
+        zz = f64(z, (self.P, 3)) if z is not None else None
+        i = np.ascontiguousarray(ids, dtype=np.int32).reshape(B) if ids is not None else None
+        out = np.empty((self.P, B), dtype=np.int32) if return_ids else None
+        check(self._lib.pk_propose_odom(self._h, dptr(d), dptr(a), dptr(zz), int(seed), int(draw), dptr(b), B, iptr(i),
+                                        1 if fresh else 0, iptr(out)))
+        return out
+
+    def proposal_download(self):
+        """(xi (P, 3), dlogw (P,), used (P,)) of the last propose / propose_odom: pk_proposal_download."""
+        xi, dl, used = np.empty((self.P, 3)), np.empty(self.P), np.empty(self.P, dtype=np.int32)
+        check(self._lib.pk_proposal_download(self._h, dptr(xi), dptr(dl), iptr(used)))
+        return xi, dl, used
 
     def download_log_weights(self):
         out = np.empty(self.P, dtype=np.float64)

@@ -578,6 +578,13 @@ class FastSLAM(object):
     the poses as the last odometry message left them.  A robot that stood still launches nothing and consumes no draw.
     ``motion_model(particle, twist, dt)`` stays the twist model.  Works with devices=[several] too.
 
+    proposal="measurement" (default "motion": every pose is drawn from the motion model alone and the scan only weighs it,
+    FastSLAM 1.0; that code path is untouched): with measurement_model="bearing", ``cam_cb`` draws every pose from the motion model
+    CONDITIONED on its scan (FastSLAM 2.0; pk_propose, pk_propose_odom; DESIGN.md section 4, "The measurement-informed proposal") --
+    one call in place of the move and the observe, with the same dt bookkeeping and draw counter.  In odometry mode
+    ``odom_motion_update`` only stores the message, and ``cam_cb`` moves by the change since the pose it last moved up to.  One GPU,
+    preset maps only (no new_landmarks).  ``record_ids=True`` keeps every step's settled ids in ``last_ids`` (one download per step).
+
     measurement_model="bearing" (default "reference": the reference's model, quirks included): the textbook robot-frame bearing
     model -- wrapped bearing differences in the gate and the innovation, the blob's ray turned by the heading, H = (-dy / q, dx / q),
     the Gaussian density with det Q as the weight (pk_set_measurement_model; DESIGN.md section 4, "The bearing model").  It is the
@@ -608,6 +615,9 @@ class FastSLAM(object):
                                  "(bookkeeping='device'): host lists cannot follow a particle from one GPU to another")
             if a["device"] not in (0, list(devices)[0]):
                 raise ValueError("FastSLAM: give either device= or devices=, not both")
+            if a["proposal"] != "motion":
+                raise ValueError("FastSLAM(devices=[...], proposal=%r): the measurement-informed proposal runs on one GPU; an "
+                                 "unknown name is refused the same way" % (a["proposal"],))
             if a["measurement_model"] != "reference":
                 raise ValueError("FastSLAM(devices=[...], measurement_model=%r): the bearing model runs on one GPU -- the ranged "
                                  "and split observes of the sharded step have no kernel for it; an unknown name is refused the "
@@ -638,10 +648,21 @@ class FastSLAM(object):
                  seed=0, publish_debug=None, new_landmarks=False, spare_landmarks=0, pair_threshold=30.0, devices=None,
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
-                 odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference"):
+                 odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion"):
         if measurement_model not in _lib.MEASUREMENT_MODELS:
             raise ValueError("FastSLAM(measurement_model=%r): 'reference' (default) or 'bearing'" % (measurement_model,))
+        if proposal not in ("motion", "measurement"):
+            raise ValueError("FastSLAM(proposal=%r): 'motion' (default) or 'measurement'" % (proposal,))
+        if proposal == "measurement" and measurement_model != "bearing":
+            raise ValueError("FastSLAM(proposal='measurement'): the measurement-informed proposal needs measurement_model='bearing' "
+                             "-- the reference model's Jacobian is not one")
+        if proposal == "measurement" and new_landmarks:
+            raise ValueError("FastSLAM(proposal='measurement', new_landmarks=True): growing maps are found by the plain step "
+                             "(proposal='motion')")
         self._model = measurement_model
+        self._proposal = proposal
+        self._proposal_ids = proposal == "measurement" and bool(record_ids)  # record_ids=True: cam_cb keeps every step's settled ids
+        self._odom_applied = None  # proposal='measurement', odometry mode: the odometry pose the particles were last moved up to
         self._motion, self._odom_alphas, self._odom_min_trans = _odom.check_keywords(motion, odom_alphas, odom_min_trans)
         self._odom_prev = None  # the last odometry pose (x, y, heading); None: the next message is the first
         if devices is not None and len(list(devices)) == 1:
@@ -867,6 +888,8 @@ class FastSLAM(object):
     # ------------------------------------------------------------------ a12
     def cam_cb(self, ros_view):
         """One filter step (:59-137)."""
+        if self._proposal == "measurement":
+            return self._cam_cb_proposed(ros_view)
         with self._lock:
             self._motion_update(self.last_control)  # :75-77 (odometry mode: the poses are current up to the last /odom message)
             scan = ros_view.last_sensor_reading  # :82
@@ -902,6 +925,44 @@ class FastSLAM(object):
                                   "triangulated -- raise reading_capacity, or use bookkeeping='host'" % (n, self._filter.grow_shape()[2]),
                                   RuntimeWarning, stacklevel=2)
                     self._warned_dropped = True
+
+    def _cam_cb_proposed(self, ros_view):
+        """cam_cb with proposal='measurement': the move and the observe are ONE call in which every pose is drawn from the motion
+        model conditioned on the scan (pk_propose / pk_propose_odom) -- the same dt bookkeeping, the same draw counter.  Odometry
+        mode: the particles move by the change between the odometry pose they were last moved up to and the latest one; no
+        change: a plain observe."""
+        with self._lock:
+            scan = ros_view.last_sensor_reading
+            blobs = _blob_matrix(scan.observes)
+            self._filter.set_measurement_noise(self.Qt)
+            fresh = self._threshold is None
+            want = self._proposal_ids
+            z = None
+            if self._motion == "twist":
+                dt = msgs.now() - self.last_update
+                v, w = float(self.last_control.linear.x), float(self.last_control.angular.z)
+                z = self._noise(self.num_particles)
+                ids = self._filter.propose(v, w, dt.to_sec(), blobs, z=z, seed=self._seed, draw=self._draw, fresh=fresh, return_ids=want)
+                self._draw += 1
+                self.last_update = self.last_update + dt
+            else:
+                self._motion_update(self.last_control)  # (records the control and its time, moves nothing)
+                prev, now = self._odom_applied, self._odom_prev
+                delta = None if prev is None or now is None else _lib.odom_delta(prev, now, self._odom_min_trans)
+                self._odom_applied = now
+                if delta is None or _odom.is_zero(delta):
+                    ids = self._filter.observe(blobs, fresh=fresh, return_ids=want)
+                else:
+                    z = self._noise(self.num_particles)
+                    ids = self._filter.propose_odom(delta, self._odom_alphas, blobs, z=z, seed=self._seed, draw=self._draw, fresh=fresh,
+                                                    return_ids=want)
+                    self._draw += 1
+            if want:
+                self.last_ids = ids
+            self._touch()
+            if self._publish:
+                self._publish_all(self.particle_track_pub, self._poses())
+            self.low_variance_resample()
 
     def _new_landmarks(self, blobs, ids):
         """add_hypothesis (:546-564) for every unmatched blob of every particle, in scan order, with the working pairing
@@ -951,6 +1012,10 @@ class FastSLAM(object):
             prev = self._odom_prev
             delta = None if prev is None else _lib.odom_delta(prev, now, self._odom_min_trans)
             self._odom_prev = now  # (only once the delta was formed: a refused message leaves the stored pose as it was)
+            if self._proposal == "measurement":  # the message is stored: cam_cb moves by it, conditioned on its scan
+                if self._odom_applied is None:
+                    self._odom_applied = now
+                return
             if delta is None or _odom.is_zero(delta):
                 return
             self._filter.motion_odom(delta, self._odom_alphas, z=self._noise(self.num_particles), seed=self._seed, draw=self._draw)

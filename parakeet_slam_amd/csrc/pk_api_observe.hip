@@ -762,6 +762,55 @@ static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const Obse
   return PK_OK;
 }
 
+// A scan with supplied ids on the device, in one block: ctl | blobs (4B doubles) | first (Lp int32) | next (B int32), and with
+// `with_ids` the id row itself behind them (B int32; k_propose reads it).  first / next: the landmark -> blob chains shared by all
+// particles, in scan order (prkt_core_v2.py:88).  The one place that lays this block out, for pk_observe and pk_propose alike.
+struct KnownScan {
+  size_t o_blobs = 0, o_first = 0, o_next = 0, o_ids = 0;
+  int n_unmatched = 0;            // blobs with id 0
+  bool single_sightings = true;   // no landmark is matched by more than one blob
+};
+static int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, bool with_ids, KnownScan* out) {
+  int rc;
+  const MapLayout& lay = f->d.lay;
+  KnownScan k;
+  k.o_blobs = kCtlBytes;
+  k.o_first = k.o_blobs + (size_t)B * 4 * sizeof(double);
+  k.o_next = k.o_first + (size_t)lay.Lp * sizeof(int32_t);
+  k.o_ids = k.o_next + (size_t)B * sizeof(int32_t);
+  const size_t total = k.o_ids + (with_ids ? (size_t)B * sizeof(int32_t) : 0);
+  unsigned char* st = nullptr;
+  int slot = 0;
+  if ((rc = take_stage(f, total, &st, &slot))) return rc;
+  if ((rc = ensure_scan_capacity(f, total))) return rc;
+  memset(st, 0, kCtlBytes);
+  if (B > 0) memcpy(st + k.o_blobs, blobs, (size_t)B * 4 * sizeof(double));
+  if (with_ids && B > 0) memcpy(st + k.o_ids, ids, (size_t)B * sizeof(int32_t));
+  int32_t* first = reinterpret_cast<int32_t*>(st + k.o_first);
+  int32_t* next = reinterpret_cast<int32_t*>(st + k.o_next);
+  std::vector<int32_t> last((size_t)lay.Lp, -1);
+  for (int l = 0; l < lay.Lp; ++l) first[l] = -1;
+  for (int b = 0; b < B; ++b) {
+    next[b] = -1;
+    int id = ids[b];
+    if (id == 0) {
+      ++k.n_unmatched;
+      continue;
+    }
+    if (first[id - 1] < 0) {
+      first[id - 1] = b;
+    } else {
+      next[last[id - 1]] = b;
+      k.single_sightings = false;
+    }
+    last[id - 1] = b;
+  }
+  if ((rc = upload_scan(f, st, total))) return rc;
+  if ((rc = note_upload(f, slot))) return rc;
+  *out = k;
+  return PK_OK;
+}
+
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out,
                         bool reset) {
   if (!f) return fail(PK_ERR_INVALID, "pk_observe: NULL handle");
@@ -793,47 +842,15 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   if (ids) {
     if ((rc = ct_end(f))) return rc;  // (another route: k_observe streams whole slots)
     f->staged.valid = false;  // a staged ML scan does not survive another observe
-    // block: ctl | blobs (4B doubles) | first (Lp int32) | next (B int32)
-    const size_t o_blobs = kCtlBytes;
-    const size_t o_first = o_blobs + (size_t)B * 4 * sizeof(double);
-    const size_t o_next = o_first + (size_t)lay.Lp * sizeof(int32_t);
-    const size_t total = o_next + (size_t)B * sizeof(int32_t);
-    unsigned char* st = nullptr;
-    int slot = 0;
-    if ((rc = take_stage(f, total, &st, &slot))) return rc;
-    if ((rc = ensure_scan_capacity(f, total))) return rc;
-    memset(st, 0, kCtlBytes);
-    if (B > 0) memcpy(st + o_blobs, blobs, (size_t)B * 4 * sizeof(double));
-    // landmark -> blob chains shared by all particles, in scan order (prkt_core_v2.py:88)
-    int32_t* first = reinterpret_cast<int32_t*>(st + o_first);
-    int32_t* next = reinterpret_cast<int32_t*>(st + o_next);
-    std::vector<int32_t> last((size_t)lay.Lp, -1);
-    for (int l = 0; l < lay.Lp; ++l) first[l] = -1;
-    int n0 = 0;
-    ex.single_sightings = true;
-    for (int b = 0; b < B; ++b) {
-      next[b] = -1;
-      int id = ids[b];
-      if (id == 0) {
-        ++n0;
-        continue;
-      }
-      if (first[id - 1] < 0) {
-        first[id - 1] = b;
-      } else {
-        next[last[id - 1]] = b;
-        ex.single_sightings = false;
-      }
-      last[id - 1] = b;
-    }
-    if ((rc = upload_scan(f, st, total))) return rc;
-    if ((rc = note_upload(f, slot))) return rc;
+    KnownScan ks;
+    if ((rc = upload_known_scan(f, blobs, B, ids, false, &ks))) return rc;
+    ex.single_sightings = ks.single_sightings;
     ex.gmax_key = ctl_gmax_key(f);
     {
       Span t(f, PK_T_OBSERVE);
-      launch_observe(f->stream, f->d, reinterpret_cast<const double*>(f->scan_dev + o_blobs), nullptr, B,
-                     reinterpret_cast<const int32_t*>(f->scan_dev + o_first),
-                     reinterpret_cast<const int32_t*>(f->scan_dev + o_next), n0, nullptr, f->qt, ex);
+      launch_observe(f->stream, f->d, reinterpret_cast<const double*>(f->scan_dev + ks.o_blobs), nullptr, B,
+                     reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_first),
+                     reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_next), ks.n_unmatched, nullptr, f->qt, ex);
     }
     PK_LAUNCH_CHECK("pk_observe");
     observe_done(f);
@@ -910,6 +927,40 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
     PK_HIP(hipStreamSynchronize(f->stream));
   }
   return PK_OK;
+}
+
+// A proposal step's scan (pk_api_propose.hip) on the device, ahead of k_propose: supplied ids as pk_observe uploads them -- the block
+// ctl | blobs | first | next, and behind it the id row itself -- or the bearing model's association at the live (predicted) poses,
+// which leaves tentative ids in ids_dev and touches no state.  The caller has checked the blobs, the ids and the filter.
+int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out) {
+  int rc;
+  *out = ProposalScan();
+  f->ct_updated = true;
+  if (ids) {
+    if ((rc = ct_end(f))) return rc;
+    f->staged.valid = false;
+    KnownScan ks;
+    if ((rc = upload_known_scan(f, blobs, B, ids, true, &ks))) return rc;
+    f->gmax_fused = false;
+    out->blobs = reinterpret_cast<const double*>(f->scan_dev + ks.o_blobs);
+    out->first = reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_first);
+    out->next = reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_next);
+    out->ids = reinterpret_cast<int32_t*>(f->scan_dev + ks.o_ids);
+    return PK_OK;
+  }
+  AssocLaunch al;
+  if ((rc = enqueue_association(f, blobs, B, false, false, &al, false, true))) return rc;
+  if (al.plan.onepass()) return fail(PK_ERR_UNSUPPORTED, "pk_propose: the scan did not take the general association");
+  if ((rc = ct_end(f))) return rc;
+  out->blobs = al.blobs;
+  out->dir = al.dir;
+  out->ids = f->ids_dev;
+  return PK_OK;
+}
+// ... and behind its observe launch
+void proposal_observed(pk_filter* f, bool known) {
+  observe_done(f);
+  f->route = known ? PK_ROUTE_KNOWN_IDS : PK_ROUTE_ML_GENERAL;
 }
 
 extern "C" {

@@ -226,4 +226,40 @@ __device__ __forceinline__ Landmark<double> load_landmark_nocount(const double* 
   return m;
 }
 
+// ------------------------------------------------------------------ settling a tentative match
+// Is probability_of_match(...) > 0 for a pair that already passed both gates (:433, :441)?
+// The association kernel leaves this to us for blobs with a single gate-passing landmark,
+// because the landmark's covariance is in registers here.  pr = (500 exp(a1)) (500 exp(a2))
+// / 250000 with a1, a2 the two log-pdfs; whenever a1 + a2 is far from the float64 underflow
+// edge the answer is known without evaluating a single exp/log; otherwise evaluate it
+// exactly as the reference does.  pse = atan2(f.my - sy, f.mx - sx).  MODEL = kModelBearing: (ux, uy) is the world-frame ray and
+// there is no half-plane test.
+template <int MODEL = kModelReference>
+__device__ __forceinline__ bool match_is_positive(const Landmark<double>& f, double sx, double sy, double pse,
+                                                  const BlobT<double>& z, double ux, double uy) {
+  if constexpr (MODEL == kModelReference)
+    if (fabs(pse - z.bearing) > Consts<double>::half_pi) return false;  // :473-475 -> bp = 0
+  double nx, ny;
+  closest_point<double, MODEL>(f.mx, f.my, sx, sy, ux, uy, nx, ny);
+  const double ex = nx - f.mx, ey = ny - f.my;
+  const double det2 = f.pxx * f.pyy - f.pxy * f.pxy;
+  const double maha2 = (f.pyy * ex * ex - 2.0 * f.pxy * ex * ey + f.pxx * ey * ey) / det2;
+  double det3;
+  const Sym3<double> inv = sym3_inverse(Sym3<double>{f.crr, f.crg, f.crb, f.cgg, f.cgb, f.cbb}, det3);
+  const double maha3 = sym3_quad(inv, z.r - f.mr, z.g - f.mg, z.b - f.mb);
+  // log det <= 138.2 for det <= 1e60, so a1 + a2 >= -0.5 (9.2 + 276.4 + 800) > -543: no underflow
+  if (det2 > 0.0 && det2 < 1e60 && det3 > 0.0 && det3 < 1e60 && maha2 >= 0.0 && maha3 >= 0.0 &&
+      maha2 + maha3 < 800.0)
+    return true;
+  const double bp = 500.0 * exp(-0.5 * (2.0 * Consts<double>::log_two_pi + log(det2) + maha2));
+  const double cp = 500.0 * exp(-0.5 * (3.0 * Consts<double>::log_two_pi + log(det3) + maha3));
+  return bp * cp / 250000.0 > 0.0;
+}
+
+__device__ __forceinline__ BlobT<double> load_blob(const double* blobs, int b) {
+  const double2 z01 = *reinterpret_cast<const double2*>(blobs + 4 * (size_t)b);
+  const double2 z23 = *reinterpret_cast<const double2*>(blobs + 4 * (size_t)b + 2);
+  return BlobT<double>{z01.x, z01.y, z23.x, z23.y};
+}
+
 }  // namespace pk

@@ -7,6 +7,7 @@
 //                       settled rows, the best particle
 //   pk_api_adaptive.hip adaptive resampling: the gated resample and step, the weight sums, the weighted pose summary
 //   pk_api_mapmatch.hip the discovered landmarks: the matched moments and the finished estimate
+//   pk_api_propose.hip  the measurement-informed proposal: pk_propose, pk_propose_odom, pk_proposal_download
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -368,6 +369,16 @@ struct pk_filter {
   GrowState grow{};                 // section 8(f4) on the device (pk_grow_enable): per-particle new-landmark bookkeeping
   bool grow_on = false;
   RetireState retire{};             // pk_grow_retire (pk_api_retire.hip): the clocks of the retirement rule -- nothing until it is switched on
+  // the measurement-informed proposal (pk_propose / pk_propose_odom; pk_api_propose.hip): nothing until the first call, then
+  // 84 P bytes -- ten rows of P doubles and one of P int32
+  struct Proposal {
+    double* pose = nullptr;         // [3][P] the poses before the move (x | y | h)
+    double* zero = nullptr;         // [P][3] the normals of the predicted pose: zeros
+    double* xi = nullptr;           // [P][3] k_propose's normals
+    double* dlogw = nullptr;        // [P] its weight increments
+    int32_t* used = nullptr;        // [P] the matches it used
+    bool valid = false;             // the last call's results are there (pk_proposal_download)
+  } prop;
   int32_t* anc = nullptr;           // P
   unsigned char* slot_tmp = nullptr;  // one slot
   // timing
@@ -518,6 +529,17 @@ int ct_maps_untouched(pk_filter* f, bool* untouched);
 void blob_directions(const double* blobs, int B, double* dir);
 int stage_ml_scan(pk_filter* f, const double* blobs, int B);
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out, bool reset);
+// a proposal step's scan on the device (pk_api_propose.hip): where its parts lie.  first / next: supplied ids' chains (the ids
+// are final); dir: the rays that settle tentative ids; ids: one row of B (supplied) or ids_dev's [P][B]
+struct ProposalScan {
+  const double* blobs = nullptr;
+  const double* dir = nullptr;
+  const int32_t* first = nullptr;
+  const int32_t* next = nullptr;
+  int32_t* ids = nullptr;
+};
+int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out);
+void proposal_observed(pk_filter* f, bool known);
 // what the bearing model (pk_set_measurement_model) has no kernels for, refused while it is on (a NULL handle passes)
 int refuse_bearing(const pk_filter* f, const char* who, const char* what);
 // pk_api_shard.hip

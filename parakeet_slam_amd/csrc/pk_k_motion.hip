@@ -46,8 +46,8 @@ void launch_motion(hipStream_t s, DeviceState& d, double v, double w, double dt,
                    const void* up_src_host_mapped, size_t up_bytes, double* pose_part_dev) {
   const int64_t n16 = up_dst_dev ? (int64_t)((up_bytes + 15) / 16) : 0;
   if (d.P == 0 && n16 == 0) return;
-  double sd = fabs(.05 * v) + fabs(.005 * w) + .0005;  // :185
-  double sh = fabs(.025 * w) + fabs(.005 * v) + .0005;  // :190,:193
+  double sd, sh;
+  motion_sigmas(v, w, &sd, &sh);
   int blocks = (int)((d.P + 255) / 256);
   int64_t ub = (n16 + 255) / 256;
   if (ub > 256) ub = 256;
@@ -62,8 +62,8 @@ void launch_motion(hipStream_t s, DeviceState& d, double v, double w, double dt,
 void launch_motion_range(hipStream_t s, DeviceState& d, double v, double w, double dt, uint64_t seed, uint64_t draw,
                          int64_t p0, int64_t p1) {
   if (p1 <= p0) return;
-  double sd = fabs(.05 * v) + fabs(.005 * w) + .0005;  // :185
-  double sh = fabs(.025 * w) + fabs(.005 * v) + .0005;  // :190,:193
+  double sd, sh;
+  motion_sigmas(v, w, &sd, &sh);
   const int64_t n = p1 - p0;
   int blocks = (int)((n + 255) / 256);
   hipLaunchKernelGGL(k_motion, dim3((unsigned)blocks), dim3(256), 0, s, d.x[d.cur] + p0, d.y[d.cur] + p0, d.h[d.cur] + p0, n, v, w,

@@ -40,47 +40,14 @@ struct ObserveArgs {
   Noise<double> qt;
 };
 
-// Is probability_of_match(...) > 0 for a pair that already passed both gates (:433, :441)?
-// The association kernel leaves this to us for blobs with a single gate-passing landmark,
-// because the landmark's covariance is in registers here.  pr = (500 exp(a1)) (500 exp(a2))
-// / 250000 with a1, a2 the two log-pdfs; whenever a1 + a2 is far from the float64 underflow
-// edge the answer is known without evaluating a single exp/log; otherwise evaluate it
-// exactly as the reference does.  pse = atan2(f.my - sy, f.mx - sx).  MODEL = kModelBearing: (ux, uy) is the world-frame ray and
-// there is no half-plane test.
-template <int MODEL = kModelReference>
-__device__ __forceinline__ bool match_is_positive(const Landmark<double>& f, double sx, double sy, double pse,
-                                                  const BlobT<double>& z, double ux, double uy) {
-  if constexpr (MODEL == kModelReference)
-    if (fabs(pse - z.bearing) > Consts<double>::half_pi) return false;  // :473-475 -> bp = 0
-  double nx, ny;
-  closest_point<double, MODEL>(f.mx, f.my, sx, sy, ux, uy, nx, ny);
-  const double ex = nx - f.mx, ey = ny - f.my;
-  const double det2 = f.pxx * f.pyy - f.pxy * f.pxy;
-  const double maha2 = (f.pyy * ex * ex - 2.0 * f.pxy * ex * ey + f.pxx * ey * ey) / det2;
-  double det3;
-  const Sym3<double> inv = sym3_inverse(Sym3<double>{f.crr, f.crg, f.crb, f.cgg, f.cgb, f.cbb}, det3);
-  const double maha3 = sym3_quad(inv, z.r - f.mr, z.g - f.mg, z.b - f.mb);
-  // log det <= 138.2 for det <= 1e60, so a1 + a2 >= -0.5 (9.2 + 276.4 + 800) > -543: no underflow
-  if (det2 > 0.0 && det2 < 1e60 && det3 > 0.0 && det3 < 1e60 && maha2 >= 0.0 && maha3 >= 0.0 &&
-      maha2 + maha3 < 800.0)
-    return true;
-  const double bp = 500.0 * exp(-0.5 * (2.0 * Consts<double>::log_two_pi + log(det2) + maha2));
-  const double cp = 500.0 * exp(-0.5 * (3.0 * Consts<double>::log_two_pi + log(det3) + maha3));
-  return bp * cp / 250000.0 > 0.0;
-}
-
-__device__ __forceinline__ BlobT<double> load_blob(const double* blobs, int b) {
-  const double2 z01 = *reinterpret_cast<const double2*>(blobs + 4 * (size_t)b);
-  const double2 z23 = *reinterpret_cast<const double2*>(blobs + 4 * (size_t)b + 2);
-  return BlobT<double>{z01.x, z01.y, z23.x, z23.y};
-}
-
+// (match_is_positive and load_blob: pk_device.hpp -- k_propose settles with them too)
 // All blobs matched to landmark l, in scan order (prkt_core_v2.py:88).
 // ML: the ids are tentative.  Association saw the state BEFORE any update (:84), so first
 // settle every blob of the chain against the untouched state (s_ids[b] = 0 drops it), then
 // apply the surviving ones sequentially.
 // MODEL = kModelBearing: (sh, ch, sn) = the particle's heading with its cosine and sine (one sincos per particle).
-template <bool KNOWN, int MODEL = kModelReference>
+// SETTLED (k_observe_proposed): the ids are final -- k_propose settled them at the predicted pose; there is no second settling.
+template <bool KNOWN, int MODEL = kModelReference, bool SETTLED = false>
 __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, double sx, double sy,
                                               const ObserveArgs& a, const int32_t* first,
                                               const int32_t* next, int32_t* s_ids, int32_t* gid, double sh = 0.0,
@@ -90,7 +57,7 @@ __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, doubl
   if (b0 < 0) return acc;
   const bool imm = a.immutable[l] != 0;
   const double pse = pk_atan2(lm.my - sy, lm.mx - sx);
-  if (!KNOWN) {
+  if (!KNOWN && !SETTLED) {
     for (int b = b0; b >= 0; b = next[b]) {
       const BlobT<double> z = load_blob(a.blobs, b);
       double2 dir = *reinterpret_cast<const double2*>(a.blobdir + 2 * (size_t)b);
@@ -119,9 +86,10 @@ __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, doubl
 }
 
 // The body of k_observe and of k_observe_bearing, its instance for the bearing model (a kernel of its own: the reference model's
-// kernels keep their names and what they compute).
-template <bool KNOWN, int NV, int MODEL>
-__device__ __forceinline__ void observe_body(const ObserveArgs& a) {
+// kernels keep their names and what they compute).  PROPOSED: k_observe_proposed, behind k_propose -- the ids are final and the
+// weight increment is dlogw[p].
+template <bool KNOWN, int NV, int MODEL, bool PROPOSED = false>
+__device__ __forceinline__ void observe_body(const ObserveArgs& a, const double* dlogw = nullptr) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ double red[kObsThreads / kWave];
   if (a.only_flagged && *a.n_flagged == 0u) return;  // workgroup-uniform: nobody was handed on
@@ -204,8 +172,8 @@ __device__ __forceinline__ void observe_body(const ObserveArgs& a) {
                          v[8].x, v[9].x, v[10].x, v[11].x, v[12].x, v[13].x, c.x};
       Landmark<double> Bq{v[0].y, v[1].y, v[2].y, v[3].y, v[4].y, v[5].y, v[6].y, v[7].y,
                           v[8].y, v[9].y, v[10].y, v[11].y, v[12].y, v[13].y, c.y};
-      if (l0 < a.L) acc += apply_blobs<KNOWN, MODEL>(A, l0, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
-      if (l0 + 1 < a.L) acc += apply_blobs<KNOWN, MODEL>(Bq, l0 + 1, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
+      if (l0 < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED>(A, l0, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
+      if (l0 + 1 < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED>(Bq, l0 + 1, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
       __builtin_nontemporal_store(d2v{A.mx, Bq.mx}, reinterpret_cast<d2v*>(df + (size_t)F_MX * Lp + l0));
       __builtin_nontemporal_store(d2v{A.my, Bq.my}, reinterpret_cast<d2v*>(df + (size_t)F_MY * Lp + l0));
       __builtin_nontemporal_store(d2v{A.mr, Bq.mr}, reinterpret_cast<d2v*>(df + (size_t)F_MR * Lp + l0));
@@ -226,7 +194,7 @@ __device__ __forceinline__ void observe_body(const ObserveArgs& a) {
     // one landmark per lane: half the registers, twice the waves in flight
     for (int l = tid; l < Lp; l += kObsThreads) {
       Landmark<double> A = load_landmark(sf, sc, Lp, l);
-      if (l < a.L) acc += apply_blobs<KNOWN, MODEL>(A, l, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
+      if (l < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED>(A, l, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
       __builtin_nontemporal_store(A.mx, &df[(size_t)F_MX * Lp + l]);
       __builtin_nontemporal_store(A.my, &df[(size_t)F_MY * Lp + l]);
       __builtin_nontemporal_store(A.mr, &df[(size_t)F_MR * Lp + l]);
@@ -246,7 +214,11 @@ __device__ __forceinline__ void observe_body(const ObserveArgs& a) {
   }
   double tot = block_sum<kObsThreads / kWave>(acc, red);
   if (tid == 0) {
-    const double v = (a.reset ? 0.0 : a.logw[p]) + tot + (double)n_unmatched * Consts<double>::log_no_match;
+    double v;
+    if constexpr (PROPOSED)
+      v = (a.reset ? 0.0 : a.logw[p]) + dlogw[p];
+    else
+      v = (a.reset ? 0.0 : a.logw[p]) + tot + (double)n_unmatched * Consts<double>::log_no_match;
     a.logw[p] = v;
     if (a.gmax_key) atomicMax(a.gmax_key + (p & (kGmaxKeys - 1)), double_to_key(v));  // sharded: same-address atomics serialise
     a.src[p] = (int32_t)p;
@@ -262,6 +234,10 @@ __global__ void __launch_bounds__(kObsThreads) k_observe(ObserveArgs a) {
 template <bool KNOWN, int NV>
 __global__ void __launch_bounds__(kObsThreads) k_observe_bearing(ObserveArgs a) {
   observe_body<KNOWN, NV, kModelBearing>(a);
+}
+template <bool KNOWN, int NV>
+__global__ void __launch_bounds__(kObsThreads) k_observe_proposed(ObserveArgs a, const double* dlogw) {
+  observe_body<KNOWN, NV, kModelBearing, true>(a, dlogw);
 }
 
 
@@ -352,7 +328,20 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
   a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
   // (behind a one-pass kernel few particles, if any, are flagged: 4 096 workgroups walk the flags)
   const unsigned grid = (unsigned)(ex.only_flagged && d.P > 4096 ? 4096 : d.P);
-  if (ex.model == kModelBearing) {  // the bearing model: k_observe's two shapes, no loop-free single-sighting kernel
+  if (ex.dlogw) {  // behind k_propose (bearing model): the same two shapes
+    if (ids_dev == nullptr) {
+      hipLaunchKernelGGL((k_observe_proposed<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a, ex.dlogw);
+    } else {
+      const size_t lds = observe_general_lds_bytes(d.lay.Lp, B);  // <= kMaxDynLds: checked by the caller
+      static bool attr_set[kMaxDevices] = {false};
+      if (first_time_on_this_device(attr_set)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_observe_proposed<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kMaxDynLds) != hipSuccess)
+          (void)hipGetLastError();
+      }
+      hipLaunchKernelGGL((k_observe_proposed<false, 1>), dim3(grid), dim3(kObsThreads), lds, s, a, ex.dlogw);
+    }
+  } else if (ex.model == kModelBearing) {  // the bearing model: k_observe's two shapes, no loop-free single-sighting kernel
     if (ids_dev == nullptr) {
       hipLaunchKernelGGL((k_observe_bearing<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a);
     } else {

@@ -1,5 +1,6 @@
 // Host-visible launchers of the gfx950 kernels (defined in pk_k_motion / pk_k_assoc / pk_k_observe / pk_k_resample .hip).
 #pragma once
+#include <cmath>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -85,6 +86,12 @@ constexpr int kScanBlock = 1024;  // particles per weight-scan block (256 thread
 void launch_motion(hipStream_t s, DeviceState& d, double v, double w, double dt, const double* z_dev,
                    uint64_t seed, uint64_t draw, int64_t global_offset, void* up_dst_dev = nullptr,
                    const void* up_src_host_mapped = nullptr, size_t up_bytes = 0, double* pose_part_dev = nullptr);
+// The twist model's sigmas of (v, w) (prkt_core_v2.py:185, :190, :193): drive, and the one both heading noises share.  The one place
+// that forms them: the motion launches and pk_propose (whose normals only give pk_motion's poses while the two agree to the bit).
+inline void motion_sigmas(double v, double w, double* sd, double* sh) {
+  *sd = fabs(.05 * v) + fabs(.005 * w) + .0005;   // :185
+  *sh = fabs(.025 * w) + fabs(.005 * v) + .0005;  // :190,:193
+}
 // pose_part_dev != NULL: the launch also leaves, per block of 256 particles, the sums of x, y, sin h, cos h of the moved particles
 // ([4] doubles per block, motion_pose_blocks(P) blocks): k_candidates reduces them to the particles' mean pose
 inline int64_t motion_pose_blocks(int64_t P) { return (P + 255) / 256; }
@@ -187,6 +194,8 @@ struct ObserveExtras {
   int model = 0;                                // launch_observe: the measurement model (pk_math.hpp: kModelReference / kModelBearing)
   int lean = 0;                                 // k_step_pub<2, 512>: lean groups take the lean body (option "pub_lean"); the scan's
   unsigned* lean_stats = nullptr;               //   figures (k_cand_entries), where the kernel counts the pairs that fell back: [6]
+  const double* dlogw = nullptr;                // launch_observe, bearing model: k_observe_proposed -- the ids are FINAL (k_propose settled
+                                                //   them) and the log-weight takes dlogw[p], not the updates' own importance factors
 };
 // The colour table (pk_k_colour.hip): tab[k][6][Lp], rows crr crg crb cgg cgb cbb as in a slot -- landmark l's
 // colour block after k updates from the one pk_upload_map broadcast (base[6][Lp]; the uploaded counts are 0, so a landmark's level is
@@ -225,6 +234,25 @@ void launch_observe_fast(hipStream_t s, DeviceState& d, int B, const double* exa
 void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev, int B,
                     const int32_t* first_dev, const int32_t* next_dev, int n_unmatched,
                     int32_t* ids_dev, const NoiseD& qt, const ObserveExtras& ex = ObserveExtras());
+// The measurement-informed proposal (pk_k_propose.hip): for every particle at its predicted pose (the live pose
+// arrays) the normals xi, the weight increment and the matches used; tentative ids (blobdir_dev != NULL) are settled in place.
+struct ProposeLaunch {
+  const double* blobs_dev = nullptr;
+  const double* blobdir_dev = nullptr;  // NULL: the ids are final
+  int B = 0;
+  int32_t* ids_dev = nullptr;           // [P][B], or one row of B for every particle (ids_shared; not written)
+  bool ids_shared = false;
+  const double* z_dev = nullptr;        // [P][3], or NULL: the Philox draws of (particle, seed, draw)
+  uint64_t seed = 0, draw = 0;
+  bool odom = false;
+  double u[3] = {0, 0, 0};              // (v, w, dt) or (rot1, trans, rot2)
+  double sigma[3] = {0, 0, 0};
+  NoiseD qt{};
+  double* xi_dev = nullptr;             // out [P][3]
+  double* dlogw_dev = nullptr;          // out [P]
+  int32_t* used_dev = nullptr;          // out [P]
+};
+void launch_propose(hipStream_t s, DeviceState& d, const ProposeLaunch& q);
 // ML observe for any L from the same hand-off, two sweeps over the particle's landmarks in
 // chunks (persistent workgroups; see k_observe_sweep).  plan.grid == 0: scan too large for its LDS tables.
 struct SweepPlan {
