@@ -492,7 +492,6 @@ __global__ void __launch_bounds__(NL == 1 ? 512 : 256, NL == 1 ? 4 : 3) k_step_p
         acc += pub_apply_loop<true>(qs, R->exact, R->order, qt, S[j], immutable[min(l0 + j, L - 1)] != 0, sx, sy, pse,
                                     reinterpret_cast<const char*>(ptab + Lpp), Lpp * 16, lc2, t0, PK_PROD_PTR(nprod));
         }
-        pub_fold_norms(acc, nprod, false);
         PK_STAMP(d2)
         PK_PSTAMP(8, d1, d2)
         if (l0 < Lp) {
@@ -542,7 +541,7 @@ __global__ void __launch_bounds__(NL == 1 ? 512 : 256, NL == 1 ? 4 : 3) k_step_p
       for (int i = 0; i + NL < NW; ++i) W[i] = W[i + NL];  // the words of the turn before it to the front
     }
     {
-      pub_fold_norms(acc, nprod, true);
+      pub_fold_norms(acc, nprod);
       const double ws = wave_sum(acc);  // the sum over the workgroup is finished behind the next barrier A
       if ((tid & (kWave - 1)) == 0) red[cur][tid / kWave] = ws;
       prev = p;

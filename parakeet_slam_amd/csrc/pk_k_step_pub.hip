@@ -936,8 +936,11 @@ __device__ __forceinline__ void pub_take(PubSlots& q, const double* pub, unsigne
 }
 
 // One logarithm per lane and particle for the importance factors' norms (:844-849; ekf_update's fro_prod; round 6): the product of the
-// squared Frobenius norms of the lane's updates is folded into the log-weight -- -1/4 log(prod) -- behind the lane's last update, or when
-// it leaves [1e-150, 1e150] (wave-uniform test, hardly ever).  The logarithm is 45 of an update's 300 float64 instructions: k_step_pub
+// squared Frobenius norms of the lane's updates is folded into the log-weight -- -1/4 log(prod) -- behind the lane's last update.
+// ekf_update looks at the product behind every single factor and keeps it a positive normal number whatever Qt and the covariances
+// are (a look once per landmark pair, at a window of [1e-150, 1e150], let eight factors of 3e40, Qt = 1e20 I, through to infinity:
+// log-weights of -inf from these kernels, -24 an update from the others), so there is nothing to look at in between.
+// The logarithm is 45 of an update's 300 float64 instructions: k_step_pub
 // 7.91 -> 7.71 ms at 100 000 x 2 000 (-2.4 %), k_step_pub_big 5.75 -> 5.71 ms at 20 000 x 5 000 (profiles/r06/ab_one_log_per_lane_*.log;
 // PK_DIAG_LOG_PER_UPDATE is the regression build).  The log-weights differ from a logarithm per update in the last bits only.
 #ifndef PK_DIAG_LOG_PER_UPDATE
@@ -945,16 +948,13 @@ __device__ __forceinline__ void pub_take(PubSlots& q, const double* pub, unsigne
 #else
 #define PK_PROD_PTR(p_) ((double*)nullptr)
 #endif
-__device__ __forceinline__ void pub_fold_norms(double& acc, double& prod, bool last) {
+__device__ __forceinline__ void pub_fold_norms(double& acc, double& prod) {
 #ifndef PK_DIAG_LOG_PER_UPDATE
-  if (last || __ballot(!(prod > 1e-150 && prod < 1e150)) != 0ull) {  // (NaN folds too, and stays what the sum of logarithms was: NaN)
-    acc -= 0.25 * log_few_ulp(prod);
-    prod = 1.0;
-  }
+  acc -= 0.25 * log_few_ulp(prod);  // (a NaN stays what the sum of logarithms was: NaN)
+  prod = 1.0;
 #else
   (void)acc;
   (void)prod;
-  (void)last;
 #endif
 }
 // The blobs taken, applied in scan order (:88): regs_apply with the take bits.
@@ -1707,7 +1707,7 @@ __device__ __forceinline__ void step_pub_body() {
               acc += THREADS == kPubSmallThreads ? pub_apply_loop(Q[i], ex, order, qt, S[i], imm, sx, sy, pse[i], nullptr, 0, 0, 0xFFFFu, PK_PROD_PTR(nprod))
                                                  : pub_apply<TAB>(Q[i], ex, order, qt, S[i], imm, sx, sy, pse[i], PK_PROD_PTR(nprod));
           }
-          pub_fold_norms(acc, nprod, q == NP - 1);
+          if constexpr (q == NP - 1) pub_fold_norms(acc, nprod);
         };
         auto do_store = [&](auto qc) {
           constexpr int q = decltype(qc)::value;
@@ -2336,7 +2336,6 @@ __global__ void __launch_bounds__(kPubThreads) k_step_pub_big(PubArgs a_unused) 
           acc += pub_apply_loop<true>(Q[1], R8->exact, R8->order, qt, SB, immutable[min(l0 + 1, L - 1)] != 0, sx, sy, pse[1],
                                       reinterpret_cast<const char*>(R8->prim + Lpp), Lpp * 16, lc2 + 1, tt.y, PK_PROD_PTR(nprod));
         }
-        pub_fold_norms(acc, nprod, false);
         PK_STAMP(d2)
         PK_PSTAMP(8, d1, d2)
         if (l0 < Lp) {
@@ -2379,7 +2378,7 @@ __global__ void __launch_bounds__(kPubThreads) k_step_pub_big(PubArgs a_unused) 
 #undef PK_BIG_STORE
 #undef PK_BIG_ROWS
 #undef PK_BIG_LOAD
-    pub_fold_norms(acc, nprod, true);
+    pub_fold_norms(acc, nprod);
     {
       const double ws = wave_sum(acc);  // the sum over the workgroup is finished behind the next barrier A
       if ((tid & (kWave - 1)) == 0) red[cur][tid / kWave] = ws;

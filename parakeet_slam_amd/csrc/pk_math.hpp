@@ -429,10 +429,29 @@ __device__ __forceinline__ T ekf_update(Landmark<T>& f, T sx, T sy, const BlobT<
     if (f.count & kPotentialBit) logw = (T)Consts<double>::log_no_match;
   } else if (fro_prod) {
     logw = T(-0.5) * Consts<T>::log_two_pi - T(0.5) * maha;
-    if (f.count & kPotentialBit)
-      logw = (T)Consts<double>::log_no_match;  // :111-112 "update as if the feature not seen"
-    else
-      *fro_prod *= fro2;
+    // The product is looked at after EVERY multiplication and is a positive normal number behind each: the caller takes its
+    // logarithm once, behind the lane's last update, and Qt is any finite matrix (1e20 I to make the filter ignore colour:
+    // fro2 = 3e40, the eight factors of a landmark pair 6.6e323; 1e-20 I: 1.6e-39, eight of them below the subnormals).  Where
+    // the product has left the normal numbers (infinite, zero or subnormal: one v_cmp_class and a branch out of line, hardly ever
+    // taken; the cost: DESIGN.md section 4) both its factors are split, x = m 2^e with m in [1/2, 1): the exponents go into the
+    // log-weight here, e ln 2 / 4 (one rounding, of a part of the terms -1/4 log(fro2) it stands for), and the product of the
+    // two m, in [1/4, 1), is the new product -- so it never is anything but a positive normal number, for any number of factors
+    // of any size.  An infinite, NaN or zero fro2 has m = fro2 (v_frexp_mant): the product becomes what it is, and the caller's
+    // logarithm gives what a logarithm per update gives, -inf, NaN, +inf.  (float64 only: a float product's subnormals would
+    // pass the test.)
+    static_assert(sizeof(T) == 8, "fro_prod: the test of the product is one of a double");
+    const bool potential = (f.count & kPotentialBit) != 0;
+    const T old = *fro_prod;
+    const T raw = old * fro2;
+    T p = potential ? old : raw;
+    if (potential) logw = (T)Consts<double>::log_no_match;  // :111-112 "update as if the feature not seen"
+    constexpr int kNotPositiveNormal = 0x3FF & ~0x100;     // (v_cmp_class: every class but +normal)
+    if (__builtin_expect(!potential && __builtin_amdgcn_class((double)raw, kNotPositiveNormal), 0)) {
+      const int e = __builtin_amdgcn_frexp_exp((double)old) + __builtin_amdgcn_frexp_exp((double)fro2);
+      p = (T)(__builtin_amdgcn_frexp_mant((double)old) * __builtin_amdgcn_frexp_mant((double)fro2));
+      logw -= T(0.25 * 0.69314718055994530941723212145818) * T(e);
+    }
+    *fro_prod = p;
   } else {
     logw = T(-0.5) * (Consts<T>::log_two_pi + T(0.5) * log_few_ulp(fro2)) - T(0.5) * maha;
     if (f.count & kPotentialBit) logw = (T)Consts<double>::log_no_match;  // :111-112 "update as if the feature not seen"

@@ -110,17 +110,29 @@ def cond_sym(m):
     return float(w[-1] / w[0]) if w[0] > 0 else math.inf
 
 
-def exact_update(row):
+def exact_update(row, cov=None, Qt=None):
     """One row of PK_MATH_EKF_UPDATE (the flags and prod are not read: this is the mutable, plain call) -> dict:
-    fields (14 mpf, the state afterwards), field_scales (14 floats), logw (mpf), logw_scale, fro2 (mpf), kappa, q (float)."""
+    fields (14 mpf, the state afterwards), field_scales (14 floats), logw (mpf), logw_scale, fro2 (mpf), kappa, q (float).
+
+    With cov (a full 5x5) and / or Qt (a full 4x4) given, those stand for the row's compact blocks (which are then not read), and
+    the pose, mean, blob and expected bearing of the row may be mpf as well as float (tests/scan_reference.py keeps a chain's state
+    unrounded); the dict then also holds mean, cov, mean_scale, cov_scale (all 5 / 5x5: the dense state afterwards and its
+    scales) and kappa_q, cond_2 of the whole 4x4 Q."""
     _ctx()
-    row = [float(v) for v in row]
+    full = cov is not None or Qt is not None
+    if not full:
+        row = [float(v) for v in row]
     sx, sy = mpf(row[E_SX]), mpf(row[E_SY])
-    mean64, cov64 = dense_cov(row[E_F:E_F + 14])
-    mu = [mpf(v) for v in mean64]
-    S = _mat(cov64.tolist())
-    Qt64 = dense_qt(row[E_QT:E_QT + 7])
-    Qt = _mat(Qt64.tolist())
+    if cov is None:
+        mean64, cov64 = dense_cov(row[E_F:E_F + 14])
+        mu = [mpf(v) for v in mean64]
+        S = _mat(cov64.tolist())
+    else:
+        mu = [mpf(v) for v in row[E_F:E_F + 5]]
+        S = _mat(cov)
+        cov64 = np.array([[float(v) for v in r] for r in S])
+    Qt64 = dense_qt(row[E_QT:E_QT + 7]) if Qt is None else np.array([[float(v) for v in r] for r in Qt])
+    Qt = _mat(Qt64.tolist()) if Qt is None else _mat(Qt)
     z = [mpf(v) for v in row[E_BLOB:E_BLOB + 4]]
     dx, dy = mu[0] - sx, mu[1] - sy
     q = dx * dx + dy * dy  # :785
@@ -146,9 +158,15 @@ def exact_update(row):
     KHS = _mul(_mul(_abs(K), _abs(H)), _abs(S))
     cov_scale = [abs(S[i][j]) + KHS[i][j] for i, j in COV_AT]
     C64 = cov64[2:, 2:] + Qt64[1:, 1:]
-    return dict(fields=new_mu + [new_S[i][j] for i, j in COV_AT], field_scales=[float(v) for v in mean_scale + cov_scale],
-                logw=logw, logw_scale=float(abs(log_norm) / 2 + maha / 2), fro2=fro2, kappa=cond_sym(C64), q=float(q),
-                asymmetry=float(max(abs(new_S[i][j] - new_S[j][i]) for i in range(5) for j in range(5))))
+    out = dict(fields=new_mu + [new_S[i][j] for i, j in COV_AT], field_scales=[float(v) for v in mean_scale + cov_scale],
+               logw=logw, logw_scale=float(abs(log_norm) / 2 + maha / 2), fro2=fro2, kappa=cond_sym(C64), q=float(q),
+               asymmetry=float(max(abs(new_S[i][j] - new_S[j][i]) for i in range(5) for j in range(5))))
+    if full:
+        Q64 = np.array([[float(v) for v in r] for r in Q])
+        out.update(mean=new_mu, cov=new_S, mean_scale=[float(v) for v in mean_scale],
+                   cov_scale=[[float(abs(S[i][j]) + KHS[i][j]) for j in range(5)] for i in range(5)],
+                   kappa_q=cond_sym(0.5 * (Q64 + Q64.T)))
+    return out
 
 
 def exact_match(row):

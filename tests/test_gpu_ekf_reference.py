@@ -160,6 +160,51 @@ def test_the_one_logarithm_form(lib):
     assert np.all(pot[:, er.O_PROD] == 0.75)
 
 
+def test_the_product_of_norms_never_leaves_the_normal_numbers(lib):
+    """fro_prod with a caller's product at either end of the doubles: p fro2 would be infinite, zero or subnormal (eight factors of
+    3e40, Qt = 1e20 I, were).  The product returned is a positive normal number, and together with the returned value it still
+    says what the plain form says: logw_one - 1/4 log(prod_out) = logw_plain - 1/4 log(p), within 4 units of the scale
+    logw_scale + 1/4 |log p| + 1/4 |log prod_out|.  The 4 is a count, not a measurement: both log-weights are doubles (half a
+    unit of their own size each), the term e ln 2 / 4 is rounded once with the sum it is added to (half a unit) and its constant
+    ln 2 / 4 is a rounded double (half a unit of e ln 2 / 4, which |log p| / 4 + |log prod_out| / 4 bounds): 2 units, doubled for
+    the sum that the one-logarithm form orders differently -- the same allowance test_the_one_logarithm_form makes.  Where the
+    product stays normal it is p fro2, bit for bit, as test_the_one_logarithm_form holds."""
+    ignored = typical()  # Qt's colour block 1e20 I, what a caller sets to make the filter ignore colour: fro2 = 3e40
+    ignored[:, [er.E_QT + 1, er.E_QT + 4, er.E_QT + 6]] = 1e20
+    rows = np.concatenate([typical(), np.array(er.draw_class("fresh")[0][:32]), np.array(er.draw_class("converged")[0][:32]), ignored])
+    plain = ekf(lib, rows, flags=0)
+    one = ekf(lib, rows, flags=er.FRO_PROD, prod=1.0)
+    fro2 = one[:, er.O_PROD]
+    assert np.all(fro2[-64:] > 2.9e40) and np.all(fro2[-64:] < 3.1e40)
+    mp = er._ctx()
+    tiny = float(np.finfo(np.float64).tiny)
+    worst, split = 0.0, 0
+    for p in (1.7e308, 3e40 ** 7, tiny, 1e3 * tiny):  # (3e40^7: the eighth factor of a landmark pair)
+        got = ekf(lib, rows, flags=er.FRO_PROD, prod=p)
+        out = got[:, er.O_PROD]
+        assert np.all(np.isfinite(out)) and np.all(out >= tiny), p
+        with np.errstate(over="ignore", under="ignore"):
+            whole = p * fro2
+        stays = np.isfinite(whole) & (whole >= tiny)
+        assert same_bits(out[stays], whole[stays]) and same_bits(got[stays, er.O_LOGW], one[stays, er.O_LOGW])
+        split += int((~stays).sum())
+        assert not stays[-64:].any() or p < 1.0  # (every one of the 3e40 takes the split path at the top)
+        assert (~stays)[96:128].sum() >= 16 or p != tiny  # (and the converged landmarks, fro2 about 0.04, at the very bottom)
+        for i in np.flatnonzero(~stays):
+            e = er.exact_update(rows[i])
+            lhs = mp.mpf(float(got[i, er.O_LOGW])) - mp.log(mp.mpf(float(out[i]))) / 4
+            rhs = mp.mpf(float(plain[i, er.O_LOGW])) - mp.log(mp.mpf(p)) / 4
+            scale = e["logw_scale"] + float(abs(mp.log(mp.mpf(p)))) / 4 + float(abs(mp.log(mp.mpf(float(out[i]))))) / 4
+            u = float(abs(lhs - rhs) / (mp.mpf(er.UNIT) * mp.mpf(scale)))
+            worst = max(worst, u)
+            assert u <= 4.0, (p, i, u)
+    assert split >= 128
+    print("split product against the plain form: worst %.3f units over %d points" % (worst, split))
+    record("ekf", "fro_prod_split_against_plain", _what=WHAT, worst_units=worst, asserted=4.0)
+    pot = ekf(lib, rows, flags=er.FRO_PROD, prod=1e300, count=rows[:, er.E_COUNT] + er.POTENTIAL)  # a potential landmark: left alone
+    assert np.all(pot[:, er.O_PROD] == 1e300) and np.all(pot[:, er.O_LOGW] == er.LOG_NO_MATCH)
+
+
 def test_the_count_and_the_potential_bit(lib):
     """+2 per update (:914, :930); a potential landmark weighs log(0.1) (:111-112), is updated like any other, and loses the bit
     exactly when its count passes 5 (:113-117)."""
