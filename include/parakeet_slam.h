@@ -270,6 +270,27 @@ int pk_grow_enable(pk_filter* f, int32_t preset_landmarks, int32_t reading_capac
 int pk_grow_download(pk_filter* f, int64_t p0, int64_t p1, int32_t* counters, double* readings, int32_t* slot_ids);
 int pk_grow_upload(pk_filter* f, int64_t p0, int64_t p1, const int32_t* counters, const double* readings, const int32_t* slot_ids);
 int pk_grow_shape(const pk_filter* f, int32_t* preset_landmarks, int32_t* spare_slots, int32_t* reading_capacity);
+/* Where, and how surely, the bookkeeping places a new feature ("Parallax-gated pairing").  It holds no
+ * per-particle state -- records, pack / adopt, the sharded exchange and pk_device_bytes are what they were -- and may be changed
+ * between any two scans; a filter that never calls it computes what it did, bit for bit.
+ *   PK_GROW_INIT_REFERENCE (default)  the reference's rule above: any crossing, identity position covariance; min_parallax is ignored.
+ *   PK_GROW_INIT_TRIANGULATED         a stored reading is a candidate only if its ray crosses the blob's (as above) AND the angle
+ *       between the two rays is min_parallax or more: |den| >= sin(min_parallax), den = ay bx - ax by the determinant ray_intersect
+ *       forms (:611-643), the sine formed once here in float64; a NaN fails.  Among the candidates the choice is unchanged (smallest
+ *       colour distance, then smallest index; pair_threshold; a free spare slot), and a blob with no candidate is stored as an
+ *       orphaned reading, so that a later scan can pair with it across a wider baseline.  The new feature's position covariance is
+ *       the triangulation's own, J diag(q00, q00) J' over the two world bearings t1, t3 (q00 = Qt[0][0] of the scan; the pose
+ *       uncertainty lives in the particles): with (s, c) their sines and cosines, (ox, oy) the crossing, (x1, y1) the reading's
+ *       pose and (px, py) the particle's,
+ *           sd = s3 c1 - c3 s1,  a = ((ox - x1) c1 + (oy - y1) s1) / sd,  b = ((ox - px) c3 + (oy - py) s3) / sd,
+ *           Pxx = q00 (a^2 c3^2 + b^2 c1^2),  Pxy = q00 (a^2 c3 s3 + b^2 c1 s1),  Pyy = q00 (a^2 s3^2 + b^2 s1^2).
+ *       Mean, colour mean, colour block (identity), count word and slot id are the reference rule's.
+ * PK_ERR_STATE without pk_grow_enable; PK_ERR_INVALID for another mode, a NaN, or min_parallax outside [0, pi / 2]; nothing changed
+ * either way.  pk_grow_init_mode reads both back (either pointer may be NULL; REFERENCE and 0 on a filter that never asked). */
+#define PK_GROW_INIT_REFERENCE 0
+#define PK_GROW_INIT_TRIANGULATED 1
+int pk_grow_init(pk_filter* f, int32_t mode, double min_parallax);
+int pk_grow_init_mode(const pk_filter* f, int32_t* mode, double* min_parallax);
 /* Growing maps that also shrink (the reference's hypothesis_set and potential_features only grow; off by default, and a filter
  * that never calls this does and holds what it did without it).  While a threshold is non-zero, one more kernel runs behind the
  * bookkeeping of every non-empty maximum-likelihood scan.  t counts those scans (uint32, wrapping; ages are differences modulo 2^32).

@@ -35,6 +35,8 @@ PK_ABI_VERSION = 1
 PK_MODEL_REFERENCE, PK_MODEL_BEARING = 0, 1  # pk_set_measurement_model
 MEASUREMENT_MODELS = {"reference": PK_MODEL_REFERENCE, "bearing": PK_MODEL_BEARING}
 PK_BEARING_SHAPES = {0: (23, 5), 1: (32, 17)}  # pk_probe_bearing: what -> (arity, outputs)
+PK_GROW_INIT_REFERENCE, PK_GROW_INIT_TRIANGULATED = 0, 1  # pk_grow_init
+LANDMARK_INITS = {"reference": PK_GROW_INIT_REFERENCE, "triangulated": PK_GROW_INIT_TRIANGULATED}
 
 
 def measurement_model_code(model):
@@ -176,6 +178,8 @@ SIGNATURES = {
     "pk_grow_download": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _dp, _ip]),
     "pk_grow_upload": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _dp, _ip]),
     "pk_grow_shape": (C.c_int, [_h, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pk_grow_init": (C.c_int, [_h, C.c_int32, C.c_double]),
+    "pk_grow_init_mode": (C.c_int, [_h, C.POINTER(C.c_int32), _dp]),
     "pk_grow_retire": (C.c_int, [_h, C.c_int32, C.c_int32]),
     "pk_grow_clocks_download": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _up, _ip, _ip, _up]),
     "pk_grow_clocks_upload": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _up, _ip, _ip, _up]),
@@ -822,6 +826,22 @@ class DeviceFilter(object):
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         check(self._lib.pk_grow_shape(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+    def grow_init(self, mode, min_parallax=0.0):
+        """How the bookkeeping places a new feature from the next scan on (pk_grow_init): "reference" (any crossing, identity
+        position covariance) or "triangulated" (crossings at ``min_parallax`` radians or more, the triangulation's own covariance)
+        -- or PK_GROW_INIT_*."""
+        if isinstance(mode, str):
+            if mode not in LANDMARK_INITS:
+                raise ValueError("grow_init: %r is neither %s" % (mode, " nor ".join(repr(k) for k in LANDMARK_INITS)))
+            mode = LANDMARK_INITS[mode]
+        check(self._lib.pk_grow_init(self._h, int(mode), float(min_parallax)))
+
+    def grow_init_mode(self):
+        """(mode's name, min_parallax) as pk_grow_init last took them; ("reference", 0.0) on a filter that never asked."""
+        m, a = C.c_int32(), C.c_double()
+        check(self._lib.pk_grow_init_mode(self._h, C.byref(m), C.byref(a)))
+        return {v: k for k, v in LANDMARK_INITS.items()}[int(m.value)], float(a.value)
 
     def grow_download(self, p0=0, p1=None, counters=True, readings=True, slot_ids=True):
         """(counters (n, 4) int32: readings stored / spare slots in use / next_id / readings dropped,

@@ -350,6 +350,24 @@ class FilterParticle(object):
             u = (y3 + by * v - y1) / ay
         return u >= 0 and v >= 0
 
+    @staticmethod
+    def _ray_determinant(b1, b3):
+        """The determinant ray_intersect forms for two world bearings: minus the sine of the angle between the rays."""
+        return math.sin(b1) * math.cos(b3) - math.cos(b1) * math.sin(b3)
+
+    @staticmethod
+    def _triangulated_covariance(x1, y1, t1, x3, y3, t3, ox, oy, q00):
+        """(Pxx, Pxy, Pyy) of the crossing (ox, oy) of the lines (x1, y1, t1) and (x3, y3, t3) whose bearings carry the variance
+        q00: J diag(q00, q00) J' with dX/dt1 = (u / sd) d3, dX/dt3 = -(v / sd) d1 (landmark_init="triangulated"; pk_grow_init)."""
+        s1, c1, s3, c3 = math.sin(t1), math.cos(t1), math.sin(t3), math.cos(t3)
+        sd = s3 * c1 - c3 * s1
+        u = (ox - x1) * c1 + (oy - y1) * s1
+        v = (ox - x3) * c3 + (oy - y3) * s3
+        a, b = u / sd, v / sd
+        aa, bb = a * a, b * b
+        return (q00 * (aa * (c3 * c3) + bb * (c1 * c1)), q00 * (aa * (c3 * s3) + bb * (c1 * s1)),
+                q00 * (aa * (s3 * s3) + bb * (s1 * s1)))
+
     def color_distance(self, blob1, blob2):
         """:645-654: Euclidean distance of the two colours."""
         return math.sqrt(math.pow(blob1.color.r - blob2.color.r, 2) + math.pow(blob1.color.g - blob2.color.g, 2) +
@@ -388,6 +406,21 @@ class FilterParticle(object):
         self.hypothesis_set[self.next_id] = ((state, blob,))
         self.next_id += 1
 
+
+
+def _check_landmark_init(landmark_init, min_parallax, new_landmarks, who="FastSLAM"):
+    """(name, min_parallax) of the landmark_init / min_parallax keywords, or ValueError -- before any device work."""
+    if landmark_init not in _lib.LANDMARK_INITS:
+        raise ValueError("%s(landmark_init=%r): 'reference' (default) or 'triangulated'" % (who, landmark_init))
+    try:
+        angle = float(min_parallax)
+    except (TypeError, ValueError):
+        raise ValueError("%s(min_parallax=%r): an angle in [0, pi / 2] radians" % (who, min_parallax))
+    if not (0.0 <= angle <= math.pi / 2):  # (a NaN fails)
+        raise ValueError("%s(min_parallax=%r): an angle in [0, pi / 2] radians" % (who, min_parallax))
+    if landmark_init != "reference" and not new_landmarks:
+        raise ValueError("%s(landmark_init=%r): new landmarks are initialised by a growing map (new_landmarks=True)" % (who, landmark_init))
+    return landmark_init, angle
 
 
 # ----------------------------------------------------------------------------- new-landmark bookkeeping: arrays <-> lists
@@ -549,6 +582,12 @@ class FastSLAM(object):
     ``reading_max_age=A`` / ``potential_max_idle=M`` (device bookkeeping, one GPU; 0: never, the default): behind every scan's
     bookkeeping each particle drops the readings at the head of its ring that are A scans old or older and retires the potential
     features that went unmatched for M scans, whose spare slots are free again (pk_grow_retire); ``retired()`` counts both.
+    ``landmark_init="triangulated"`` (default "reference": the rule above) with ``min_parallax`` (radians in [0, pi / 2], default
+    0.2): a stored reading is paired only if its ray meets the blob's at min_parallax or more -- a blob with no such reading is
+    stored, so that a later scan pairs with it across a wider baseline -- and the new feature starts with the triangulation's own
+    position covariance, J diag(Qt[0][0], Qt[0][0]) J' over the two bearings, in place of the identity (pk_grow_init; DESIGN.md
+    section 9, "Parallax-gated pairing").  Both bookkeeping modes apply it, ``save_state`` writes both values and ``load_state``
+    takes them from the snapshot (one without them: "reference").
     ``record_ids`` (default: only with bookkeeping="host"): keep ``last_ids`` / ``last_ancestors`` of every step.
 
     record_path=T (default 0: off): every resample records the generation it worked on and its ancestors in a ring of the last
@@ -606,6 +645,7 @@ class FastSLAM(object):
             return super(FastSLAM, cls).__new__(cls)  # __init__ raises the same TypeError with its own wording
         ba.apply_defaults()
         a = ba.arguments
+        _check_landmark_init(a["landmark_init"], a["min_parallax"], a["new_landmarks"])
         devices = a.get("devices")
         if devices is not None and len(list(devices)) > 1:
             from .multi import ShardedFastSLAM
@@ -639,7 +679,8 @@ class FastSLAM(object):
                                    publish_debug=a["publish_debug"], new_landmarks=a["new_landmarks"],
                                    spare_landmarks=a["spare_landmarks"], pair_threshold=a["pair_threshold"],
                                    reading_capacity=a["reading_capacity"], motion=a["motion"], odom_alphas=a["odom_alphas"],
-                                   odom_min_trans=a["odom_min_trans"], **extra)
+                                   odom_min_trans=a["odom_min_trans"], landmark_init=a["landmark_init"],
+                                   min_parallax=a["min_parallax"], **extra)
         if extra:
             raise TypeError("FastSLAM: %s only apply with devices=[...] naming several GPUs" % ", ".join(sorted(extra)))
         return super(FastSLAM, cls).__new__(cls)
@@ -648,7 +689,9 @@ class FastSLAM(object):
                  seed=0, publish_debug=None, new_landmarks=False, spare_landmarks=0, pair_threshold=30.0, devices=None,
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
-                 odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion"):
+                 odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion",
+                 landmark_init="reference", min_parallax=0.2):
+        self._landmark_init, self._min_parallax = _check_landmark_init(landmark_init, min_parallax, new_landmarks)
         if measurement_model not in _lib.MEASUREMENT_MODELS:
             raise ValueError("FastSLAM(measurement_model=%r): 'reference' (default) or 'bearing'" % (measurement_model,))
         if proposal not in ("motion", "measurement"):
@@ -717,6 +760,8 @@ class FastSLAM(object):
                 raise ValueError("%s -- FastSLAM(..., bookkeeping='host') keeps the new-landmark bookkeeping on the host, on any layout" % e)
             if any(self._retire):
                 self._filter.grow_retire(*self._retire)
+            if self._landmark_init != "reference":
+                self._filter.grow_init(self._landmark_init, self._min_parallax)
         else:
             self._nl_host = dict(
                 hyp=[[] for _ in range(P)],          # orphaned readings: (id, x, y, heading, bearing, r, g, b)  (:739-746)
@@ -969,6 +1014,8 @@ class FastSLAM(object):
         rule (class docstring).  New potential features are written into the particle's next spare slot."""
         poses = self._poses()
         scratch = FilterParticle()
+        tri = self._landmark_init == "triangulated"
+        sin_min, q00 = math.sin(self._min_parallax), float(np.asarray(self.Qt, dtype=np.float64)[0, 0])
         for i in np.nonzero((ids == 0).any(axis=1))[0]:
             i = int(i)
             x, y, h = float(poses[i, 0]), float(poses[i, 1]), float(poses[i, 2])
@@ -979,6 +1026,8 @@ class FastSLAM(object):
                 for rd in self._hyp[i]:  # find_nearest_reading :566-590 over the stored readings
                     if not scratch.ray_intersect(rd[1], rd[2], rd[4] + rd[3], x, y, float(z[0]) + h):  # :592-609
                         continue
+                    if tri and not (abs(scratch._ray_determinant(rd[4] + rd[3], float(z[0]) + h)) >= sin_min):  # the parallax gate
+                        continue
                     d = math.sqrt(math.pow(rd[5] - z[1], 2) + math.pow(rd[6] - z[2], 2) + math.pow(rd[7] - z[3], 2))
                     if d < best_d:
                         best, best_d = rd, d
@@ -987,16 +1036,21 @@ class FastSLAM(object):
                     xy = scratch._cross_lines(best[1], best[2], best[3] + best[4], x, y, h + float(z[0]))  # :688-737
                 if xy is not None:  # add_new_feature :656-686
                     slot = self._L0 + self._used[i] + len(fresh)
-                    fresh.append((slot, (xy[0], xy[1], (best[5] + z[1]) / 2, (best[6] + z[2]) / 2, (best[7] + z[3]) / 2)))
+                    pos = None
+                    if tri:
+                        pos = scratch._triangulated_covariance(best[1], best[2], best[3] + best[4], x, y, h + float(z[0]), xy[0], xy[1], q00)
+                    fresh.append((slot, (xy[0], xy[1], (best[5] + z[1]) / 2, (best[6] + z[2]) / 2, (best[7] + z[3]) / 2), pos))
                     self._slot_id[i][slot] = self._next_id[i]
                 else:  # add_orphaned_reading :739-746
                     self._hyp[i].append((self._next_id[i], x, y, h, float(z[0]), float(z[1]), float(z[2]), float(z[3])))
                 self._next_id[i] += 1
             if fresh:
                 m, c, k = self._filter.download_landmarks(i, i + 1)
-                for slot, mean in fresh:
+                for slot, mean, pos in fresh:
                     m[0, slot] = mean
                     c[0, slot] = np.identity(5)
+                    if pos is not None:
+                        c[0, slot, 0, 0], c[0, slot, 0, 1], c[0, slot, 1, 0], c[0, slot, 1, 1] = pos[0], pos[1], pos[1], pos[2]
                     k[0, slot] = _lib.PK_LANDMARK_POTENTIAL  # update_count 0, potential
                 self._filter.upload_landmarks(i, i + 1, m, c.reshape(1, -1, 25), k)
                 self._used[i] += len(fresh)
@@ -1215,6 +1269,8 @@ class FastSLAM(object):
                     extra.update(nl_clock_counters=kc,nl_clock_scan=sc, nl_clock_seen=se, nl_clock_idle=si, nl_clock_now=np.uint32(now))
             elif self._grow:
                 extra = _nl_snapshot(self._nl())
+            if self._grow:
+                extra.update(landmark_init=np.array(self._landmark_init), min_parallax=np.float64(self._min_parallax))
             if self._threshold is not None:  # the weights carry over: bit for bit, not through exp and log
                 extra["log_weights"] = self._filter.download_log_weights()
             if self._record_path:
@@ -1250,6 +1306,9 @@ class FastSLAM(object):
                 raise ValueError("snapshot: no new-landmark bookkeeping (nl_* arrays) for a filter with new_landmarks=True%s"
                                  % ("; it was written in the old pickled format" if "new_landmarks" in d.files else ""))
             have_nl = "nl_offsets" in d.files and self._grow
+            if self._grow:  # (a snapshot from before the fields: the reference's rule)
+                init = _check_landmark_init(str(d["landmark_init"]) if "landmark_init" in d.files else "reference",
+                                            float(d["min_parallax"]) if "min_parallax" in d.files else self._min_parallax, True, "snapshot")
             have_path = self._record_path and "path_ancestors" in d.files
             if have_path:
                 n = d["path_ancestors"].shape[0]
@@ -1299,6 +1358,10 @@ class FastSLAM(object):
             self._draw = int(d["draw"])
             if self._motion == "odometry":  # (a snapshot without the pose: the next message is the first)
                 self._odom_prev = tuple(float(v) for v in d["odom_prev"]) if have_odom else None
+            if self._grow:
+                self._landmark_init, self._min_parallax = init
+                if self._nl_device:
+                    self._filter.grow_init(*init)
             if have_nl and self._nl_device:
                 _, S, R = self._filter.grow_shape()
                 self._filter.grow_upload(0, P, *_nl_arrays_from_snapshot(d, P, self._L0, S, R))

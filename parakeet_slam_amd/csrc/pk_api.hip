@@ -980,6 +980,28 @@ int pk_grow_shape(const pk_filter* f, int32_t* preset_landmarks, int32_t* spare_
   return PK_OK;
 }
 
+// pk_grow_init: the rule by which the bookkeeping kernel places a new feature, from the next scan on (it keeps no per-particle state)
+int pk_grow_init(pk_filter* f, int32_t mode, double min_parallax) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_grow_init: NULL handle");
+  if (!f->grow_on) return fail(PK_ERR_STATE, "pk_grow_init: pk_grow_enable was not called on this filter");
+  if (mode != PK_GROW_INIT_REFERENCE && mode != PK_GROW_INIT_TRIANGULATED)
+    return fail(PK_ERR_INVALID, "pk_grow_init: mode %d is neither PK_GROW_INIT_REFERENCE nor PK_GROW_INIT_TRIANGULATED", mode);
+  if (!(min_parallax >= 0.0 && min_parallax <= M_PI / 2))  // (a NaN fails)
+    return fail(PK_ERR_INVALID, "pk_grow_init: min_parallax %g outside [0, pi / 2]", min_parallax);
+  static_assert(PK_GROW_INIT_REFERENCE == kGrowInitReference && PK_GROW_INIT_TRIANGULATED == kGrowInitTriangulated, "pk_kernels.hpp");
+  f->grow_init.mode = mode;
+  f->grow_init.min_parallax = min_parallax;
+  f->grow_init.sin_min = std::sin(min_parallax);
+  return PK_OK;
+}
+
+int pk_grow_init_mode(const pk_filter* f, int32_t* mode, double* min_parallax) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_grow_init_mode: NULL handle");
+  if (mode) *mode = f->grow_init.mode;
+  if (min_parallax) *min_parallax = f->grow_init.min_parallax;
+  return PK_OK;
+}
+
 // ---- probe ------------------------------------------------------------------------------
 int pk_probe(int32_t device, const double pose[3], const double mean[5], const double cov[25],
              const double blob[4], const double Qt[16], double* out) {

@@ -367,6 +367,7 @@ struct pk_filter {
   GateOutcome* ad_out = nullptr;    // what the last gated call decided, and the counters since pk_create
   int64_t ad_calls = 0;             // gated calls enqueued (pk_resample_stats: 0 -> nothing to report)
   GrowState grow{};                 // section 8(f4) on the device (pk_grow_enable): per-particle new-landmark bookkeeping
+  GrowInit grow_init{};             // pk_grow_init: where and how surely the bookkeeping places a new feature (no per-particle state)
   bool grow_on = false;
   RetireState retire{};             // pk_grow_retire (pk_api_retire.hip): the clocks of the retirement rule -- nothing until it is switched on
   // the measurement-informed proposal (pk_propose / pk_propose_odom; pk_api_propose.hip): nothing until the first call, then

@@ -17,12 +17,18 @@ namespace pk {
 // expressions in the same order; cos / sin are the device library's, within an ulp or two of the host's).
 #pragma clang fp contract(off)
 // :611-643 -- do the half-lines (x1, y1, b1) and (x3, y3, b3) meet (both ray parameters >= 0)
-__device__ __forceinline__ bool grow_ray_intersect(double x1, double y1, double b1, double x3, double y3, double b3) {
+// kGate (pk_grow_init, PK_GROW_INIT_TRIANGULATED): and is the angle between them min_parallax or more -- den is minus its sine; a
+// NaN fails
+template <bool kGate>
+__device__ __forceinline__ bool grow_ray_intersect(double x1, double y1, double b1, double x3, double y3, double b3, double sin_min) {
   double ax, ay, bx, by;
   sincos(b1, &ay, &ax);
   sincos(b3, &by, &bx);
   const double den = ay * bx - ax * by;
   if (den == 0.0) return false;
+  if constexpr (kGate) {
+    if (!(fabs(den) >= sin_min)) return false;
+  }
   const double v = (ax * y3 - ay * x3 + ay * x1 - ax * y1) / den;
   double u;
   if (fabs(ay) < fabs(ax))
@@ -31,10 +37,10 @@ __device__ __forceinline__ bool grow_ray_intersect(double x1, double y1, double 
     u = (y3 + by * v - y1) / ay;
   return u >= 0.0 && v >= 0.0;
 }
-// :688-737 -- intersection of the two LINES (world bearings h1, h3); false when parallel
+// :688-737 -- intersection of the two LINES (world bearings h1, h3); false when parallel.  (s1, c1), (s3, c3): the sine and cosine of
+// the two bearings, for the triangulated covariance
 __device__ __forceinline__ bool grow_cross_readings(double x1, double y1, double h1, double x3, double y3, double h3, double& ox,
-                                                    double& oy) {
-  double c1, s1, c3, s3;
+                                                    double& oy, double& s1, double& c1, double& s3, double& c3) {
   sincos(h1, &s1, &c1);
   sincos(h3, &s3, &c3);
   const double x2 = x1 + c1, y2 = y1 + s1, x4 = x3 + c3, y4 = y3 + s3;
@@ -50,12 +56,17 @@ __device__ __forceinline__ bool grow_cross_readings(double x1, double y1, double
 // those are taken one after the other, in scan order (each sees what the ones before it stored: the loop over the vote is
 // wave-uniform); the nearest-reading search of one blob runs over the stored readings lane-parallel, the first minimum wins as in the
 // reference's loop (strict <: the smallest distance, then the smallest index); lane 0 writes.
-__global__ void __launch_bounds__(256) k_new_landmarks(GrowState g, const double* __restrict__ x, const double* __restrict__ y,
-                                                       const double* __restrict__ h, const int32_t* __restrict__ ids,
-                                                       const double* __restrict__ blobs, int B, unsigned char* __restrict__ map,
-                                                       size_t slot_bytes, size_t count_off, int Lp, int64_t P,
-                                                       const unsigned* __restrict__ unm, int unm_words,
-                                                       const unsigned char* __restrict__ pflag) {
+//
+// kTri (pk_grow_init, PK_GROW_INIT_TRIANGULATED; DESIGN.md section 9, "Parallax-gated pairing"): a stored reading is a candidate only
+// if its ray meets the blob's at min_parallax or more (sin_min = sin(min_parallax), formed on the host), and the new feature's
+// position covariance is the triangulation's own, J diag(q00, q00) J' over the two bearings, in place of the identity.
+template <bool kTri>
+__device__ __forceinline__ void new_landmarks_body(const GrowState& g, const double* __restrict__ x, const double* __restrict__ y,
+                                                   const double* __restrict__ h, const int32_t* __restrict__ ids,
+                                                   const double* __restrict__ blobs, int B, unsigned char* __restrict__ map,
+                                                   size_t slot_bytes, size_t count_off, int Lp, int64_t P,
+                                                   const unsigned* __restrict__ unm, int unm_words,
+                                                   const unsigned char* __restrict__ pflag, double sin_min, double q00) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t p = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
   if (p >= P) return;  // wave-uniform
@@ -91,7 +102,7 @@ __global__ void __launch_bounds__(256) k_new_landmarks(GrowState g, const double
       double best_d = INFINITY;
       for (int r = lane; r < n; r += kWave) {  // find_nearest_reading :566-590 over the stored readings
         const double* rd = ring + 8 * r;
-        if (!grow_ray_intersect(rd[1], rd[2], rd[4] + rd[3], px, py, zb + ph)) continue;  // :592-609
+        if (!grow_ray_intersect<kTri>(rd[1], rd[2], rd[4] + rd[3], px, py, zb + ph, sin_min)) continue;  // :592-609
         const double d = sqrt((rd[5] - zr) * (rd[5] - zr) + (rd[6] - zg) * (rd[6] - zg) + (rd[7] - zc) * (rd[7] - zc));  // :645-654
         if (d < best_d) {
           best = r;
@@ -110,8 +121,8 @@ __global__ void __launch_bounds__(256) k_new_landmarks(GrowState g, const double
       bool made = false;
       if (best >= 0 && best_d < g.pair_threshold && used < g.S) {  // wave-uniform
         const double* rd = ring + 8 * best;
-        double ox, oy;
-        if (grow_cross_readings(rd[1], rd[2], rd[3] + rd[4], px, py, ph + zb, ox, oy)) {  // add_new_feature :656-686
+        double ox, oy, s1, c1, s3, c3;
+        if (grow_cross_readings(rd[1], rd[2], rd[3] + rd[4], px, py, ph + zb, ox, oy, s1, c1, s3, c3)) {  // add_new_feature :656-686
           if (lane == 0) {
             const int l = g.L0 + used;
             f[(size_t)F_MX * Lp + l] = ox;
@@ -119,9 +130,18 @@ __global__ void __launch_bounds__(256) k_new_landmarks(GrowState g, const double
             f[(size_t)F_MR * Lp + l] = (rd[5] + zr) / 2;
             f[(size_t)F_MG * Lp + l] = (rd[6] + zg) / 2;
             f[(size_t)F_MB * Lp + l] = (rd[7] + zc) / 2;
-            f[(size_t)F_PXX * Lp + l] = 1.0;  // identity covariance (:676)
-            f[(size_t)F_PXY * Lp + l] = 0.0;
-            f[(size_t)F_PYY * Lp + l] = 1.0;
+            if constexpr (kTri) {  // dX/dt1 = (u / sd) d3, dX/dt3 = -(v / sd) d1: the two bearings carry the measurement noise
+              const double sd = s3 * c1 - c3 * s1;
+              const double u = (ox - rd[1]) * c1 + (oy - rd[2]) * s1, v = (ox - px) * c3 + (oy - py) * s3;
+              const double a = u / sd, b2 = v / sd, aa = a * a, bb = b2 * b2;
+              f[(size_t)F_PXX * Lp + l] = q00 * (aa * (c3 * c3) + bb * (c1 * c1));
+              f[(size_t)F_PXY * Lp + l] = q00 * (aa * (c3 * s3) + bb * (c1 * s1));
+              f[(size_t)F_PYY * Lp + l] = q00 * (aa * (s3 * s3) + bb * (s1 * s1));
+            } else {
+              f[(size_t)F_PXX * Lp + l] = 1.0;  // identity covariance (:676)
+              f[(size_t)F_PXY * Lp + l] = 0.0;
+              f[(size_t)F_PYY * Lp + l] = 1.0;
+            }
             f[(size_t)F_CRR * Lp + l] = 1.0;
             f[(size_t)F_CRG * Lp + l] = 0.0;
             f[(size_t)F_CRB * Lp + l] = 0.0;
@@ -157,13 +177,37 @@ __global__ void __launch_bounds__(256) k_new_landmarks(GrowState g, const double
     cnt[3] = dropped;
   }
 }
+
+// the reference's rule: any crossing, identity covariance (what a filter that never calls pk_grow_init runs)
+__global__ void __launch_bounds__(256) k_new_landmarks(GrowState g, const double* __restrict__ x, const double* __restrict__ y,
+                                                       const double* __restrict__ h, const int32_t* __restrict__ ids,
+                                                       const double* __restrict__ blobs, int B, unsigned char* __restrict__ map,
+                                                       size_t slot_bytes, size_t count_off, int Lp, int64_t P,
+                                                       const unsigned* __restrict__ unm, int unm_words,
+                                                       const unsigned char* __restrict__ pflag) {
+  new_landmarks_body<false>(g, x, y, h, ids, blobs, B, map, slot_bytes, count_off, Lp, P, unm, unm_words, pflag, 0.0, 0.0);
+}
+// PK_GROW_INIT_TRIANGULATED: the parallax gate in the search, the propagated covariance in lane 0's write
+__global__ void __launch_bounds__(256) k_new_landmarks_tri(GrowState g, const double* __restrict__ x, const double* __restrict__ y,
+                                                           const double* __restrict__ h, const int32_t* __restrict__ ids,
+                                                           const double* __restrict__ blobs, int B, unsigned char* __restrict__ map,
+                                                           size_t slot_bytes, size_t count_off, int Lp, int64_t P,
+                                                           const unsigned* __restrict__ unm, int unm_words,
+                                                           const unsigned char* __restrict__ pflag, double sin_min, double q00) {
+  new_landmarks_body<true>(g, x, y, h, ids, blobs, B, map, slot_bytes, count_off, Lp, P, unm, unm_words, pflag, sin_min, q00);
+}
 #pragma clang fp contract(on)
 
-void launch_new_landmarks(hipStream_t s, DeviceState& d, GrowState& g, const int32_t* ids_dev, const double* blobs_dev, int B,
-                          const unsigned* unm_dev, int unm_words, const unsigned char* pflag_dev) {
+void launch_new_landmarks(hipStream_t s, DeviceState& d, GrowState& g, const GrowInit& init, double q00, const int32_t* ids_dev,
+                          const double* blobs_dev, int B, const unsigned* unm_dev, int unm_words, const unsigned char* pflag_dev) {
   if (d.P == 0 || B == 0) return;
-  hipLaunchKernelGGL(k_new_landmarks, dim3((unsigned)((d.P + 3) / 4)), dim3(256), 0, s, g, d.x[d.cur], d.y[d.cur], d.h[d.cur], ids_dev,
-                     blobs_dev, B, d.map[d.mcur], d.lay.slot_bytes, d.lay.count_off, d.lay.Lp, d.P, unm_dev, unm_words, pflag_dev);
+  const dim3 grid((unsigned)((d.P + 3) / 4)), block(256);
+  if (init.mode == kGrowInitTriangulated)
+    hipLaunchKernelGGL(k_new_landmarks_tri, grid, block, 0, s, g, d.x[d.cur], d.y[d.cur], d.h[d.cur], ids_dev, blobs_dev, B, d.map[d.mcur],
+                       d.lay.slot_bytes, d.lay.count_off, d.lay.Lp, d.P, unm_dev, unm_words, pflag_dev, init.sin_min, q00);
+  else
+    hipLaunchKernelGGL(k_new_landmarks, grid, block, 0, s, g, d.x[d.cur], d.y[d.cur], d.h[d.cur], ids_dev, blobs_dev, B, d.map[d.mcur],
+                       d.lay.slot_bytes, d.lay.count_off, d.lay.Lp, d.P, unm_dev, unm_words, pflag_dev);
 }
 
 // the bookkeeping follows the particles through the resample (:243: the deepcopy of the whole particle): slot k takes ancestor

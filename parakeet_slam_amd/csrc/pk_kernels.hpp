@@ -49,6 +49,15 @@ struct GrowState {
   int L0 = 0, S = 0, R = 0;                  // preset landmarks, spare slots, ring capacity
   double pair_threshold = 0.0;
 };
+// how the bookkeeping kernel places a new feature (pk_grow_init; DESIGN.md section 9, "Parallax-gated pairing"): kept beside
+// GrowState, not in it -- it holds nothing per particle, and the kernels that take GrowState by value keep their arguments
+constexpr int kGrowInitReference = 0;     // any crossing, identity position covariance: the reference's rule
+constexpr int kGrowInitTriangulated = 1;  // crossings at min_parallax or more, the triangulation's own covariance
+struct GrowInit {
+  int mode = kGrowInitReference;
+  double min_parallax = 0.0;  // as pk_grow_init received it
+  double sin_min = 0.0;       // sin(min_parallax), formed once on the host
+};
 // the bookkeeping of one particle behind its record in the sharded exchange: counters (16 B) | slot ids | readings
 __host__ __device__ inline size_t grow_tail_readings_off(int S) { return 16 + (((size_t)S * 4 + 15) & ~(size_t)15); }
 inline size_t grow_tail_bytes(const GrowState& g) { return g.R > 0 ? grow_tail_readings_off(g.S) + (size_t)g.R * 64 : 0; }
@@ -613,8 +622,10 @@ void launch_adopt_dev(hipStream_t s, DeviceState& d, const int64_t* hi_dev, int6
 void launch_iota(hipStream_t s, int32_t* p, int64_t n);
 // unm_dev != NULL: the unmatched blobs of particle p come from its bit row there (the one-pass kernels leave it) unless pflag_dev[p] != 0
 // (the fall-back kernels took the particle and left its ids in ids_dev's row)
-void launch_new_landmarks(hipStream_t s, DeviceState& d, GrowState& g, const int32_t* ids_dev, const double* blobs_dev, int B,
-                          const unsigned* unm_dev = nullptr, int unm_words = 0, const unsigned char* pflag_dev = nullptr);
+// init.mode picks the kernel's instance; q00 = Qt[0][0] of this scan (the triangulated covariance's bearing variance)
+void launch_new_landmarks(hipStream_t s, DeviceState& d, GrowState& g, const GrowInit& init, double q00, const int32_t* ids_dev,
+                          const double* blobs_dev, int B, const unsigned* unm_dev = nullptr, int unm_words = 0,
+                          const unsigned char* pflag_dev = nullptr);
 // anc >= 0: a particle of this filter; anc < 0: record -anc - 1 of buf (stride bytes apart, its bookkeeping tail_off bytes in)
 void launch_grow_gather(hipStream_t s, GrowState& g, const int32_t* anc_dev, int64_t P, const unsigned char* buf_dev = nullptr,
                         size_t stride = 0, size_t tail_off = 0);

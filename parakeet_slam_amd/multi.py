@@ -50,7 +50,8 @@ from . import odom as _odom
 from .msgs import Odometry, Twist
 
 
-def _worker_main(rank, world, device, store_path, backend, P_local, L, means, covs, imm, domain, shard_factory, conn, grow=None):
+def _worker_main(rank, world, device, store_path, backend, P_local, L, means, covs, imm, domain, shard_factory, conn, grow=None,
+                 grow_init=None):
     """One rank: joins the process group, builds its shard, serves the pipe.  Runs in a freshly spawned interpreter."""
     try:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: what RCCL needs on these hosts
@@ -70,6 +71,8 @@ def _worker_main(rank, world, device, store_path, backend, P_local, L, means, co
             sf.upload_map(means, covs.reshape(L, 25), imm)
         if grow is not None:  # (preset landmarks, reading capacity, pair threshold): section 8(f4) on every rank's device
             sf.grow_enable(*grow)
+            if grow_init is not None:  # (mode, min_parallax): pk_grow_init on every rank's device
+                sf.grow_init(*grow_init)
         probe = None  # a one-particle filter for motion_model, made on first use and kept
         conn.send(("ok", None))
         while True:
@@ -122,6 +125,9 @@ def _worker_main(rank, world, device, store_path, backend, P_local, L, means, co
                     conn.send(("ok", sf.download_landmarks(cmd[1], cmd[2])))
                 elif op == "grow":  # the new-landmark bookkeeping of local slots [j0, j1)
                     conn.send(("ok", sf.grow_download(cmd[1], cmd[2])))
+                elif op == "grow_init":
+                    sf.grow_init(cmd[1], cmd[2])
+                    conn.send(("ok", None))
                 elif op == "set_grow":
                     sf.grow_upload(0, P_local, *cmd[1:4])
                     conn.send(("ok", None))
@@ -216,7 +222,8 @@ class ShardedFastSLAM(object):
 
     new_landmarks=True with spare_landmarks=S: the working new-landmark initialisation of ``FastSLAM`` (:546-746, core.py) on
     every rank's device (pk_grow_enable); a particle that migrates in the resample takes its orphaned readings, id counter and
-    spare-slot ids along behind its map, so the filter grows the same maps whatever the number of GPUs.
+    spare-slot ids along behind its map, so the filter grows the same maps whatever the number of GPUs.  landmark_init /
+    min_parallax as in ``FastSLAM`` (pk_grow_init on every rank: the rule keeps no per-particle state, the records are unchanged).
 
     record_path (the path estimate of ``FastSLAM``) and settle_path (its trunk) are refused: lineages across ranks are not recorded.  So is
     resample_threshold (adaptive resampling): the ranks would have to all-reduce their weight sums for one verdict.
@@ -229,8 +236,12 @@ class ShardedFastSLAM(object):
     def __init__(self, preset_features=[], num_particles=50, devices=(0, 1), weight_domain="log", rng="device", seed=0,
                  backend="nccl", publish_debug=None, _shard_factory=None, new_landmarks=False, spare_landmarks=0,
                  pair_threshold=30.0, reading_capacity=64, record_path=0, resample_threshold=None, settle_path=None,
-                 motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS, odom_min_trans=_odom.DEFAULT_MIN_TRANS):
+                 motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS, odom_min_trans=_odom.DEFAULT_MIN_TRANS,
+                 landmark_init="reference", min_parallax=0.2):
         from . import _lib  # constants only; loads nothing
+        from .core import _check_landmark_init
+
+        self._landmark_init, self._min_parallax = _check_landmark_init(landmark_init, min_parallax, new_landmarks, "ShardedFastSLAM")
 
         self._motion, self._odom_alphas, self._odom_min_trans = _odom.check_keywords(motion, odom_alphas, odom_min_trans)
         self._odom_prev = None  # the last odometry pose (x, y, heading); None: the next message is the first
@@ -259,11 +270,15 @@ class ShardedFastSLAM(object):
         self._P_local = self.num_particles // world
         self._features = list(preset_features)
         L0 = len(self._features)
+        self._new_landmarks = bool(new_landmarks)
         self._grow = bool(new_landmarks) and int(spare_landmarks) > 0
         self._spare = int(spare_landmarks) if self._grow else 0
         if self._grow and _shard_factory is not None and not getattr(_shard_factory, "grows", False):
             raise ValueError("ShardedFastSLAM: new_landmarks needs shards that keep the bookkeeping (the HIP shards do; this "
                              "_shard_factory does not say it does)")
+        if self._grow and self._landmark_init != "reference" and _shard_factory is not None and not getattr(_shard_factory, "triangulates", False):
+            raise ValueError("ShardedFastSLAM: landmark_init=%r needs shards that know the rule (the HIP shards do; this "
+                             "_shard_factory does not say it does)" % (self._landmark_init,))
         self._L0 = L0
         L = L0 + self._spare  # every particle's map: the preset landmarks, then the spare slots
         self._L = L
@@ -278,7 +293,9 @@ class ShardedFastSLAM(object):
 
         means[L0:, 2:] = _Single.EMPTY_COLOUR  # a spare slot that holds nothing yet fails every colour gate
         self._reading_capacity = int(reading_capacity)
+        self._native_shards = _shard_factory is None or getattr(_shard_factory, "triangulates", False)
         grow = (L0, int(reading_capacity), float(pair_threshold)) if self._grow else None
+        grow_init = (self._landmark_init, self._min_parallax) if self._grow and self._landmark_init != "reference" else None
         self.Qt = np.identity(4) * 0.1  # prkt_core_v2.py:50-53
         self._domain = {"linear": _lib.PK_WEIGHTS_LINEAR, "log": _lib.PK_WEIGHTS_LOG}[weight_domain]
         self._rng, self._seed, self._draw = rng, int(seed), 0
@@ -302,7 +319,7 @@ class ShardedFastSLAM(object):
         for rk, dev in enumerate(self.devices):
             a, b = ctx.Pipe()
             p = ctx.Process(target=_worker_main, args=(rk, world, dev, self._store, backend, self._P_local, L, means, covs, imm,
-                                                       self._domain, _shard_factory, b, grow), daemon=True)
+                                                       self._domain, _shard_factory, b, grow, grow_init), daemon=True)
             p.start()
             self._conns.append(a)
             self._procs.append(p)
@@ -647,6 +664,8 @@ class ShardedFastSLAM(object):
 
                 g = self._all("grow", 0, self._P_local)
                 extra = _nl_snapshot_arrays(*[np.concatenate([q[a] for q in g])[self._where] for a in range(3)], L0=self._L0)
+            if self._new_landmarks:  # as FastSLAM.save_state writes them for a growing filter
+                extra.update(landmark_init=np.array(self._landmark_init), min_parallax=np.float64(self._min_parallax))
             if self._motion == "odometry" and self._odom_prev is not None:
                 extra["odom_prev"] = np.array(self._odom_prev, dtype=np.float64)
             np.savez_compressed(
@@ -678,6 +697,12 @@ class ShardedFastSLAM(object):
                     raise ValueError("snapshot: no new-landmark bookkeeping (nl_* arrays) for a filter with new_landmarks=True")
                 _nl_check_snapshot(d, P, self._L0, L, self._spare, self._reading_capacity)  # before anything is assigned
                 nl = _nl_arrays_from_snapshot(d, P, self._L0, self._spare, self._reading_capacity)
+                from .core import _check_landmark_init
+
+                init = _check_landmark_init(str(d["landmark_init"]) if "landmark_init" in d.files else "reference",
+                                            float(d["min_parallax"]) if "min_parallax" in d.files else self._min_parallax, True, "snapshot")
+                if init[0] != "reference" and not self._native_shards:
+                    raise ValueError("snapshot: landmark_init=%r needs shards that know the rule" % (init[0],))
             for r in range(len(self._conns)):
                 s = slice(r * Pl, (r + 1) * Pl)
                 self._post(r, ("set_state", d["poses"][s], d["means"][s] if L else None,
@@ -688,6 +713,11 @@ class ShardedFastSLAM(object):
                     s = slice(r * Pl, (r + 1) * Pl)
                     self._post(r, ("set_grow", nl[0][s], nl[1][s], nl[2][s]))
                 self._collect("set_grow")
+                if init != (self._landmark_init, self._min_parallax):
+                    for r in range(len(self._conns)):
+                        self._post(r, ("grow_init", init[0], init[1]))
+                    self._collect("grow_init")
+                    self._landmark_init, self._min_parallax = init
             self.Qt = d["Qt"].copy()
             self.last_control.linear.x = float(d["last_control"][0])
             self.last_control.angular.z = float(d["last_control"][1])

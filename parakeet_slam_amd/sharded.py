@@ -535,6 +535,10 @@ class ShardedFilter(object):
         self.split_step = False  # (the bookkeeping kernel wants the ids in HBM: whole observes on the general route)
         return self.f.grow_enable(preset_landmarks, reading_capacity, pair_threshold)
 
+    def grow_init(self, *a, **k):
+        self._complete()
+        return self.f.grow_init(*a, **k)
+
     def grow_download(self, *a, **k):
         self._complete()
         return self.f.grow_download(*a, **k)
