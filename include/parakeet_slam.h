@@ -182,6 +182,36 @@ int pk_set_measurement_noise(pk_filter* f, const double Qt[16]);
 int pk_set_measurement_model(pk_filter* f, int32_t model);
 int pk_measurement_model(const pk_filter* f, int32_t* model);
 
+/* Range-bearing scans ("Range-bearing scans"): an option of PK_MODEL_BEARING on the compact layout.  A scan may
+ * carry a range and a range variance per blob -- a depth camera, a stereo pair or a lidar front end beside the colour camera --, for
+ * all of its blobs or for some: NaN means "this blob has none", and such a blob is handled exactly as the bearing model handles it.
+ * For a blob with a finite range rho and variance q_rho, with u the blob's unit ray turned by the heading, n = (-uy, ux) and q00 = Qt[0][0]:
+ *   gates       unchanged (the wrapped bearing difference, the squared colour distance);
+ *   position    the 2x2 density at the MEASURED POINT s + rho u instead of the closest point on the ray, under
+ *               S = Sigma_xy + q_rho u u' + rho^2 q00 n n'; colour probability, factors, argmax and settling as ever;
+ *   update      the position part is the 2-D measurement (bearing, range): H = [[-dy / q, dx / q], [dx / r, dy / r]], r = sqrt(q) (both
+ *               rows (0, 0) at q = 0), S2 = H Sigma_xy H' + diag(q00, q_rho), innovation (wrap(bearing - zhat0), rho - r); the colour
+ *               block, immutable landmarks, the update count and potential features as ever;
+ *   weight      log w = -5/2 log 2 pi - 1/2 log(det S2 det(C + Qc)) - 1/2 (d' S2^-1 d + the colour term).
+ * A landmark matched by several blobs takes them in scan order, with ranges and without.
+ *
+ * pk_scan_ranges names the ranges of the NEXT scan: ranges[num_blobs] (NaN, or finite and > 0) and variances[num_blobs] (finite
+ * and > 0 wherever the range is finite; not read elsewhere).  They are consumed, on success or failure, by the next call that takes
+ * blobs -- pk_stage_scan, pk_observe, pk_observe_fresh, pk_associate, pk_step, pk_step_adaptive, pk_step_odom -- and a scan that
+ * pk_stage_scan staged keeps its ranges until it is observed or discarded.  num_blobs == 0 or ranges == NULL disarms.  Anything else
+ * is PK_ERR_INVALID, and nothing is armed.  Ranges are not state: no snapshot holds them.
+ * A scan in which no blob has a finite range stages, launches and computes what it would without the call; the first scan with one
+ * may grow the per-scan block (pk_device_bytes) by 32 bytes a blob.  Its route is PK_ROUTE_KNOWN_IDS or PK_ROUTE_ML_GENERAL as ever.
+ * While ranges are armed (or staged) the consuming call refuses, in this order, changes nothing, and the ranges are gone:
+ *   PK_ERR_INVALID      another num_blobs than the ranges were named for;
+ *   PK_ERR_UNSUPPORTED  a filter that is not on PK_MODEL_BEARING; the dense layout (the bearing model's own refusal); growing maps
+ *                       (pk_grow_enable: a new landmark is still placed from two bearings);
+ * and pk_propose / pk_propose_odom refuse them with PK_ERR_UNSUPPORTED before anything else (the proposal samples from the bearings).
+ * pk_scan_ranges_state: *armed = the num_blobs of the armed ranges (0: none), *staged = that of a staged scan that was given ranges
+ * (0: none); either pointer may be NULL. */
+int pk_scan_ranges(pk_filter* f, const double* ranges, const double* variances, int32_t num_blobs);
+int pk_scan_ranges_state(const pk_filter* f, int32_t* armed, int32_t* staged);
+
 /* FilterParticle.load_feature_list (prkt_core_v2.py:294-299) for every particle:
  * means[L*5] (x,y,r,g,b), covs[L*25] row-major 5x5, immutable[L] = Feature.__immutable__
  * (:883; NULL = all mutable).  update_count starts at 0.  Symmetric, block-diagonal covariances
@@ -818,6 +848,17 @@ int pk_probe_math(int32_t device, int32_t op, int64_t n, const double* in, doubl
  *              any other bit is PK_ERR_INVALID.  prod_in comes back unchanged.
  * PK_ERR_INVALID for any other `what`. */
 int pk_probe_bearing(int32_t device, int32_t what, int64_t n, const double* in, double* out);
+
+/* The same for range-bearing blobs (pk_scan_ranges): pk_probe_bearing's rows with the blob's range and its variance behind them.  A
+ * NaN range takes the bearing model's functions, as in the kernels.
+ *   what  calls                    arity -> outputs
+ *   0     the match probabilities  26 -> 5   in:  pk_probe_bearing's 23 | range | range variance | Qt[0][0]
+ *                                            out: probability_of_match | position | colour | the point the position density was
+ *                                                 taken at, x y (the measured point; the closest point for a NaN range)
+ *   1     the update               33 -> 16  in:  pk_probe_bearing's 31 without prod_in (... | zhat0 | flags) | range | range variance
+ *                                            out: log-weight | the 14 landmark fields | count
+ * PK_ERR_INVALID for any other `what`, and for flags beyond bits 0 and 1. */
+int pk_probe_range(int32_t device, int32_t what, int64_t n, const double* in, double* out);
 
 /* ---- instrumentation ----------------------------------------------------------
  * Kernel launches of the enabled PK_T_* slots are bracketed by hipEvents on the handle's

@@ -35,6 +35,7 @@ PK_ABI_VERSION = 1
 PK_MODEL_REFERENCE, PK_MODEL_BEARING = 0, 1  # pk_set_measurement_model
 MEASUREMENT_MODELS = {"reference": PK_MODEL_REFERENCE, "bearing": PK_MODEL_BEARING}
 PK_BEARING_SHAPES = {0: (23, 5), 1: (32, 17)}  # pk_probe_bearing: what -> (arity, outputs)
+PK_RANGE_SHAPES = {0: (26, 5), 1: (33, 16)}    # pk_probe_range: what -> (arity, outputs)
 PK_GROW_INIT_REFERENCE, PK_GROW_INIT_TRIANGULATED = 0, 1  # pk_grow_init
 LANDMARK_INITS = {"reference": PK_GROW_INIT_REFERENCE, "triangulated": PK_GROW_INIT_TRIANGULATED}
 
@@ -165,6 +166,9 @@ SIGNATURES = {
     "pk_probe": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pk_probe_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp]),
     "pk_probe_bearing": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp]),
+    "pk_probe_range": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _dp, _dp]),
+    "pk_scan_ranges": (C.c_int, [_h, _dp, _dp, C.c_int32]),
+    "pk_scan_ranges_state": (C.c_int, [_h, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pk_enable_timing": (C.c_int, [_h, C.c_int32]),
     "pk_reset_timings": (C.c_int, [_h]),
     "pk_timings": (C.c_int, [_h, _dp, _lp]),
@@ -316,6 +320,22 @@ class DeviceFilter(object):
         m = C.c_int32()
         check(self._lib.pk_measurement_model(self._h, C.byref(m)))
         return {v: k for k, v in MEASUREMENT_MODELS.items()}[int(m.value)]
+
+    def scan_ranges(self, ranges, variances=None):
+        """Name the ranges of the NEXT scan (pk_scan_ranges; bearing model): ``ranges[B]`` (NaN = this blob has none) and
+        ``variances[B]``; the next call that takes blobs consumes them.  ``None`` or an empty array disarms."""
+        if ranges is None or np.size(ranges) == 0:
+            check(self._lib.pk_scan_ranges(self._h, None, None, 0))
+            return
+        r = f64(ranges, (-1,))
+        v = None if variances is None else f64(variances, (r.shape[0],))
+        check(self._lib.pk_scan_ranges(self._h, dptr(r), None if v is None else dptr(v), r.shape[0]))
+
+    def scan_ranges_state(self):
+        """(armed, staged): the number of blobs of the armed ranges and of a staged scan that was given ranges; 0 = none."""
+        a, st = C.c_int32(), C.c_int32()
+        check(self._lib.pk_scan_ranges_state(self._h, C.byref(a), C.byref(st)))
+        return int(a.value), int(st.value)
 
     def upload_map(self, means, covs, immutable=None):
         m = f64(means, (self.L, 5))
@@ -985,6 +1005,17 @@ def probe_bearing(what, array, device=0):
     a = f64(array, (-1, arity))
     out = np.empty((a.shape[0], outputs), dtype=np.float64)
     check(lib.pk_probe_bearing(int(device), int(what), a.shape[0], dptr(a), dptr(out)))
+    return out
+
+
+def probe_range(what, array, device=0):
+    """The primitives of range-bearing blobs on the rows of ``array`` on the GPU (pk_probe_range): what 0 the match probabilities
+    (n x 26 -> n x 5), 1 the update (n x 33 -> n x 16)."""
+    lib = load()
+    arity, outputs = PK_RANGE_SHAPES.get(int(what), (1, 1))
+    a = f64(array, (-1, arity))
+    out = np.empty((a.shape[0], outputs), dtype=np.float64)
+    check(lib.pk_probe_range(int(device), int(what), a.shape[0], dptr(a), dptr(out)))
     return out
 
 

@@ -45,6 +45,46 @@ def _blob_row(blob):
     return np.array([blob.bearing, blob.color.r, blob.color.g, blob.color.b], dtype=np.float64)
 
 
+def _check_range_noise(range_noise, measurement_model, proposal, new_landmarks, who="FastSLAM"):
+    """range_noise=(sigma0, sigma1) of FastSLAM: None, or the two floats of a range's standard deviation sigma0 + sigma1 rho."""
+    if range_noise is None:
+        return None
+    try:
+        s0, s1 = (float(v) for v in range_noise)
+    except (TypeError, ValueError):
+        raise ValueError("%s(range_noise=%r): None, or (sigma0, sigma1) -- a range's standard deviation is sigma0 + sigma1 * range"
+                         % (who, range_noise))
+    if not (math.isfinite(s0) and math.isfinite(s1)) or s0 < 0.0 or s1 < 0.0:
+        raise ValueError("%s(range_noise=%r): sigma0 and sigma1 are finite and >= 0" % (who, range_noise))
+    if s0 == 0.0 and s1 == 0.0:
+        raise ValueError("%s(range_noise=%r): a range needs a variance > 0 -- sigma0 and sigma1 cannot both be 0" % (who, range_noise))
+    if measurement_model != "bearing":
+        raise ValueError("%s(range_noise=...): per-blob ranges are an option of measurement_model='bearing'; the reference model "
+                         "has no range" % who)
+    if proposal == "measurement":
+        raise ValueError("%s(range_noise=..., proposal='measurement'): the measurement-informed proposal samples the pose from the "
+                         "bearings alone; ranges go with proposal='motion'" % who)
+    if new_landmarks:
+        raise ValueError("%s(range_noise=..., new_landmarks=True): a growing map still places a new landmark from two bearings; "
+                         "ranges go with a preset map" % who)
+    return s0, s1
+
+
+def _scan_with_ranges(observes, range_noise, who="FastSLAM"):
+    """(observes for _blob_matrix, ranges or None): a (B, 5) array (bearing, r, g, b, range) is split -- and refused without
+    range_noise --; with range_noise, message objects are asked for an optional ``range`` attribute (absent, None or NaN: none)."""
+    if isinstance(observes, np.ndarray) and observes.ndim == 2 and observes.shape[1] == 5:
+        if range_noise is None:
+            raise ValueError("%s: a (B, 5) scan (bearing, r, g, b, range) needs range_noise=(sigma0, sigma1); this filter takes "
+                             "(B, 4) scans" % who)
+        return observes[:, :4], np.array(observes[:, 4], dtype=np.float64)
+    if range_noise is None or (isinstance(observes, np.ndarray) and observes.ndim == 2):
+        return observes, None
+    observes = list(observes)
+    ranges = np.array([float("nan") if getattr(b, "range", None) is None else float(b.range) for b in observes], dtype=np.float64)
+    return observes, ranges
+
+
 def _blob_matrix(observes):
     """The scan as a (B, 4) array of (bearing, r, g, b) -- blob_to_matrix (matrix.py:35-39) for every blob of
     ``ros_view.last_sensor_reading.observes`` (prkt_core_v2.py:82, :344).  Message objects are read in one flat pass (2 000 blobs:
@@ -629,6 +669,15 @@ class FastSLAM(object):
     the Gaussian density with det Q as the weight (pk_set_measurement_model; DESIGN.md section 4, "The bearing model").  It is the
     model that localises a robot that turns.  Its scans take the general kernels; one GPU only, the compact layout only.
     ``save_state`` writes the model's name and ``load_state`` refuses a snapshot taken with the other one.
+
+    range_noise=(sigma0, sigma1) (default None; measurement_model="bearing", proposal="motion", a preset map): scans may carry a
+    range per blob -- a depth camera, a stereo pair, a lidar front end -- for all blobs or for some (pk_scan_ranges; DESIGN.md section
+    4, "Range-bearing scans").  A scan is message objects with an optional ``range`` attribute (absent, None or NaN: this blob has
+    none), or a (B, 5) array (bearing, r, g, b, range).  A range rho gets the variance (sigma0 + sigma1 rho)^2, formed on the host.
+    A ranged blob is associated at its measured point and updates its landmark with the 2-D measurement (bearing, range): landmarks
+    of one colour on one ray are told apart, and a landmark's depth no longer waits for parallax.  The pose estimate does not gain
+    by it on the drives measured.  With range_noise=None a (B, 5) array is a ValueError, and a ``range`` attribute of message objects
+    is IGNORED.  Ranges are not state: snapshots do not change.
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -646,6 +695,7 @@ class FastSLAM(object):
         ba.apply_defaults()
         a = ba.arguments
         _check_landmark_init(a["landmark_init"], a["min_parallax"], a["new_landmarks"])
+        _check_range_noise(a["range_noise"], a["measurement_model"], a["proposal"], a["new_landmarks"])
         devices = a.get("devices")
         if devices is not None and len(list(devices)) > 1:
             from .multi import ShardedFastSLAM
@@ -690,10 +740,11 @@ class FastSLAM(object):
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
                  odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion",
-                 landmark_init="reference", min_parallax=0.2):
+                 landmark_init="reference", min_parallax=0.2, range_noise=None):
         self._landmark_init, self._min_parallax = _check_landmark_init(landmark_init, min_parallax, new_landmarks)
         if measurement_model not in _lib.MEASUREMENT_MODELS:
             raise ValueError("FastSLAM(measurement_model=%r): 'reference' (default) or 'bearing'" % (measurement_model,))
+        self._range_noise = _check_range_noise(range_noise, measurement_model, proposal, new_landmarks)
         if proposal not in ("motion", "measurement"):
             raise ValueError("FastSLAM(proposal=%r): 'motion' (default) or 'measurement'" % (proposal,))
         if proposal == "measurement" and measurement_model != "bearing":
@@ -938,8 +989,13 @@ class FastSLAM(object):
         with self._lock:
             self._motion_update(self.last_control)  # :75-77 (odometry mode: the poses are current up to the last /odom message)
             scan = ros_view.last_sensor_reading  # :82
-            blobs = _blob_matrix(scan.observes)
+            observes, ranges = _scan_with_ranges(scan.observes, self._range_noise)
+            blobs = _blob_matrix(observes)
             self._filter.set_measurement_noise(self.Qt)
+            if ranges is not None and len(blobs) and not np.isnan(ranges).all():
+                # the next observe consumes them (pk_scan_ranges); the variance of a range is formed here
+                sigma = self._range_noise[0] + self._range_noise[1] * ranges
+                self._filter.scan_ranges(ranges, sigma * sigma)
             # :73 weight = 1 (the reset is fused into the observe kernels: pk_observe_fresh; the motion
             # update in between does not read the weights), :84-124 association + EKF + weights
             # (adaptive resampling: no reset -- the weights carry over from a kept step, and a resample leaves them at 1)
@@ -978,7 +1034,7 @@ class FastSLAM(object):
         change: a plain observe."""
         with self._lock:
             scan = ros_view.last_sensor_reading
-            blobs = _blob_matrix(scan.observes)
+            blobs = _blob_matrix(_scan_with_ranges(scan.observes, None)[0])  # (a (B, 5) scan is refused: no range_noise here)
             self._filter.set_measurement_noise(self.Qt)
             fresh = self._threshold is None
             want = self._proposal_ids

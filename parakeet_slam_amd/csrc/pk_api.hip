@@ -862,6 +862,7 @@ int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed,
     return gate ? pk_resample_adaptive(f, u, weight_domain, *gate, nullptr) : pk_resample(f, u, weight_domain, nullptr);  // :137
   };
   int rc;
+  if ((rc = ranges_check(f, "pk_step", B))) return rc;  // (armed ranges this step cannot take: refused before anything moves)
   // Throughput mode with ML association: the host half of the scan upload first, then ONE launch
   // for the motion update and the upload of the scan block, then the observe kernels.
   if (f && !f->dense && !f->grow_on && !z && !ids && B > 0 && blobs && f->map_loaded && f->opt.upload_kernel && m.finite()) {
@@ -869,7 +870,9 @@ int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed,
     for (int i = 0; i < 4 * B && finite; ++i) finite = std::isfinite(blobs[i]);
     if (finite && B <= 65535) {
       if ((rc = use_device(f))) return rc;
-      if ((rc = stage_ml_scan(f, blobs, B))) return rc;
+      RangeScan rs;
+      if ((rc = ranges_take(f, "pk_step", B, &rs))) return rc;
+      if ((rc = stage_ml_scan(f, blobs, B, &rs))) return rc;
       pk_filter::Staged& sg = f->staged;
       void* dev_view = nullptr;
       if (hipHostGetDevicePointer(&dev_view, sg.st, 0) == hipSuccess && dev_view) {
@@ -891,7 +894,10 @@ int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed,
       (void)hipGetLastError();
     }
   }
-  if ((rc = m.odom ? motion_odom_checked(f, m.delta, m.sigma, z, seed, draw) : pk_motion(f, m.v, m.w, m.dt, z, seed, draw))) return rc;  // :75-77
+  if ((rc = m.odom ? motion_odom_checked(f, m.delta, m.sigma, z, seed, draw) : pk_motion(f, m.v, m.w, m.dt, z, seed, draw))) {  // :75-77
+    ranges_disarm(f);
+    return rc;
+  }
   if ((rc = observe_impl(f, blobs, B, ids, nullptr, reset))) return rc;   // :73 (reset fused) + :82-124
   return resample();
 }

@@ -343,8 +343,10 @@ static int ensure_handoff(pk_filter* f, int B, int slots, bool lists = true, boo
 
 // Host half of the ML scan upload: blobs, ray directions, exact records and the association tables
 // are laid out in a pinned staging slot (no device work; may synchronise only to grow buffers).
-// block: ctl | blobs (4B) | dir (2B) | exact (6B) doubles | tables
-int stage_ml_scan(pk_filter* f, const double* blobs, int B) {
+// block: ctl | blobs (4B) | dir (2B) | exact (6B) doubles | tables, and behind them -- only for a scan in which some blob has a
+// range (rs->any; pk_scan_ranges) -- the range rows (2B doubles in scan order, 2B in cell order): a scan without stages the bytes
+// it always staged.
+int stage_ml_scan(pk_filter* f, const double* blobs, int B, const RangeScan* rs) {
   int rc;
   if (B > 65535) return fail(PK_ERR_UNSUPPORTED, "maximum-likelihood association handles at most 65535 blobs per scan (got %d)", B);
   // the general EKF kernel (every ML route's last resort) builds per-particle chains in LDS
@@ -356,6 +358,9 @@ int stage_ml_scan(pk_filter* f, const double* blobs, int B) {
   pk_filter::Staged& sg = f->staged;
   sg.valid = false;
   sg.uploaded = false;
+  sg.with_ranges = rs && rs->armed;
+  sg.ranged = rs && rs->any;
+  const size_t rng_bytes = sg.ranged ? (size_t)B * 4 * sizeof(double) : 0;
   const int ncell_max = kGridMax * kGridMax * kGridMax;
   const size_t tab_max = (blob_grid_table_bytes(ncell_max, B, 9 * B + 16) + 15) & ~(size_t)15;
   const size_t o_blobs = kCtlBytes;
@@ -364,8 +369,8 @@ int stage_ml_scan(pk_filter* f, const double* blobs, int B) {
   const size_t o_tab = o_exact + (size_t)B * 6 * sizeof(double);
   unsigned char* st = nullptr;
   int slot = 0;
-  if ((rc = take_stage(f, o_tab + tab_max + 16, &st, &slot))) return rc;
-  if ((rc = ensure_scan_capacity(f, o_tab + tab_max + 16))) return rc;
+  if ((rc = take_stage(f, o_tab + tab_max + 16 + rng_bytes, &st, &slot))) return rc;
+  if ((rc = ensure_scan_capacity(f, o_tab + tab_max + 16 + rng_bytes))) return rc;
   memset(st, 0, kCtlBytes);
   memmove(st + o_blobs, blobs, (size_t)B * 4 * sizeof(double));
   double* dir = reinterpret_cast<double*>(st + o_dir);
@@ -385,6 +390,21 @@ int stage_ml_scan(pk_filter* f, const double* blobs, int B) {
   sg.B = B;
   sg.st = st;
   sg.slot = slot;
+  if (sg.ranged) {
+    double* rows = reinterpret_cast<double*>(st + staged_range_offset(sg));
+    memcpy(rows, rs->rv.data(), (size_t)B * 2 * sizeof(double));
+    double* cell = rows + 2 * (size_t)B;
+    if (sg.use_grid) {  // beside the exact records: row t is blob order[t]'s
+      const size_t cs_b = ((size_t)(sg.g.ncell + 1) * 2 + 15) & ~(size_t)15;
+      const uint16_t* order = reinterpret_cast<const uint16_t*>(st + o_tab + cs_b + (size_t)B * 16 + (size_t)sg.n9 * 2);
+      for (int t = 0; t < B; ++t) {
+        cell[2 * (size_t)t] = rs->rv[2 * (size_t)order[t]];
+        cell[2 * (size_t)t + 1] = rs->rv[2 * (size_t)order[t] + 1];
+      }
+    } else {
+      memcpy(cell, rows, (size_t)B * 2 * sizeof(double));
+    }
+  }
   sg.valid = true;
   return PK_OK;
 }
@@ -476,7 +496,7 @@ static ScanPlan plan_scan(const pk_filter* f, int B, bool use_grid, int ncell, i
 // Upload one scan for maximum-likelihood association (one block), plan it and enqueue what the plan wants of the association:
 // nothing (the one-pass kinds), k_candidates + k_assoc_grid, or k_assoc_brute.  `blobs` may be the staged copy itself (pk_observe_staged).
 static int enqueue_association(pk_filter* f, const double* blobs, int B, bool finalize, bool want_fast, AssocLaunch* out, bool grow = false,
-                        bool whole = false) {
+                        bool whole = false, const RangeScan* rs = nullptr) {
   int rc;
   pk_filter::Staged& sg = f->staged;
   const size_t o_blobs = kCtlBytes;
@@ -484,10 +504,10 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
   const size_t o_exact = o_dir + (size_t)B * 2 * sizeof(double);
   const size_t o_tab = o_exact + (size_t)B * 6 * sizeof(double);
   if (!(sg.valid && sg.B == B && blobs == reinterpret_cast<const double*>(sg.st + o_blobs)))
-    if ((rc = stage_ml_scan(f, blobs, B))) return rc;
+    if ((rc = stage_ml_scan(f, blobs, B, rs))) return rc;
   sg.valid = false;  // consumed
   if (!sg.uploaded) {
-    if ((rc = upload_scan(f, sg.st, sg.use_grid ? o_tab + sg.tab_bytes : o_exact))) return rc;
+    if ((rc = upload_scan(f, sg.st, staged_upload_bytes(sg)))) return rc;
     if ((rc = note_upload(f, sg.slot))) return rc;
   }
   sg.uploaded = false;
@@ -499,6 +519,10 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
   al.n9 = sg.n9;
   al.blobs = reinterpret_cast<const double*>(f->scan_dev + o_blobs);
   al.dir = reinterpret_cast<const double*>(f->scan_dev + o_dir);
+  if (sg.ranged) {
+    al.rng = reinterpret_cast<const double*>(f->scan_dev + staged_range_offset(sg));
+    al.rng_cell = al.rng + 2 * (size_t)B;
+  }
   if (sg.use_grid) {
     const size_t cs_b = ((size_t)(sg.g.ncell + 1) * 2 + 15) & ~(size_t)15;
     al.tables = f->scan_dev + o_tab;
@@ -520,11 +544,11 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
   if ((rc = ct_end(f))) return rc;  // (the general association reads the slots' colour rows)
   Span t(f, PK_T_ASSOC);
   if (plan.kind == ScanKind::Brute) {
-    launch_assoc_brute(f->stream, f->d, al.blobs, al.dir, B, f->ids_dev, f->model);
+    launch_assoc_brute(f->stream, f->d, al.blobs, al.dir, B, f->ids_dev, f->model, al.rng, f->qt.q00);
     return PK_OK;
   }
   if (f->model == PK_MODEL_BEARING) {
-    launch_assoc_grid_bearing(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, f->ids_dev, finalize);
+    launch_assoc_grid_bearing(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, f->ids_dev, finalize, al.rng_cell, f->qt.q00);
     return PK_OK;
   }
   FastHandoff fh{};
@@ -767,10 +791,12 @@ static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const Obse
 // particles, in scan order (prkt_core_v2.py:88).  The one place that lays this block out, for pk_observe and pk_propose alike.
 struct KnownScan {
   size_t o_blobs = 0, o_first = 0, o_next = 0, o_ids = 0;
+  size_t o_rng = 0;               // the range rows ([B][2] range, variance) of a scan in which some blob has one, behind everything else; 0: none
   int n_unmatched = 0;            // blobs with id 0
   bool single_sightings = true;   // no landmark is matched by more than one blob
 };
-static int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, bool with_ids, KnownScan* out) {
+static int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, bool with_ids, KnownScan* out,
+                             const RangeScan* rs = nullptr) {
   int rc;
   const MapLayout& lay = f->d.lay;
   KnownScan k;
@@ -778,7 +804,11 @@ static int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const
   k.o_first = k.o_blobs + (size_t)B * 4 * sizeof(double);
   k.o_next = k.o_first + (size_t)lay.Lp * sizeof(int32_t);
   k.o_ids = k.o_next + (size_t)B * sizeof(int32_t);
-  const size_t total = k.o_ids + (with_ids ? (size_t)B * sizeof(int32_t) : 0);
+  size_t total = k.o_ids + (with_ids ? (size_t)B * sizeof(int32_t) : 0);
+  if (rs && rs->any) {
+    k.o_rng = (total + 15) & ~(size_t)15;
+    total = k.o_rng + (size_t)B * 2 * sizeof(double);
+  }
   unsigned char* st = nullptr;
   int slot = 0;
   if ((rc = take_stage(f, total, &st, &slot))) return rc;
@@ -786,6 +816,7 @@ static int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const
   memset(st, 0, kCtlBytes);
   if (B > 0) memcpy(st + k.o_blobs, blobs, (size_t)B * 4 * sizeof(double));
   if (with_ids && B > 0) memcpy(st + k.o_ids, ids, (size_t)B * sizeof(int32_t));
+  if (k.o_rng) memcpy(st + k.o_rng, rs->rv.data(), (size_t)B * 2 * sizeof(double));
   int32_t* first = reinterpret_cast<int32_t*>(st + k.o_first);
   int32_t* next = reinterpret_cast<int32_t*>(st + k.o_next);
   std::vector<int32_t> last((size_t)lay.Lp, -1);
@@ -814,10 +845,20 @@ static int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out,
                         bool reset) {
   if (!f) return fail(PK_ERR_INVALID, "pk_observe: NULL handle");
+  int rc;
+  // the ranges of this scan (pk_scan_ranges): armed ones are consumed here, whatever follows; a staged scan brought its own, and
+  // is held to the same refusals once more (the filter may have changed since pk_stage_scan) -- refused, it is discarded
+  RangeScan rs;
+  const bool from_staged = f->staged.valid && B > 0 && blobs == reinterpret_cast<const double*>(f->staged.st + kCtlBytes);
+  if (!from_staged) {
+    if ((rc = ranges_take(f, "pk_observe", B, &rs))) return rc;
+  } else if (f->staged.with_ranges && (rc = refuse_ranges(f, "pk_observe", B, f->staged.B))) {
+    f->staged.valid = false;
+    return rc;
+  }
   if (B < 0 || (B > 0 && !blobs)) return fail(PK_ERR_INVALID, "pk_observe: bad blobs");
   if (!f->map_loaded) return fail(PK_ERR_STATE, "pk_observe: no map uploaded (pk_upload_map)");
   if (f->split.active) return fail(PK_ERR_STATE, "pk_observe: a split observe is in progress (pk_observe_staged_range with last = 1 ends it)");
-  int rc;
   if ((rc = use_device(f))) return rc;
   const MapLayout& lay = f->d.lay;
   const int L = lay.L;
@@ -843,7 +884,8 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
     if ((rc = ct_end(f))) return rc;  // (another route: k_observe streams whole slots)
     f->staged.valid = false;  // a staged ML scan does not survive another observe
     KnownScan ks;
-    if ((rc = upload_known_scan(f, blobs, B, ids, false, &ks))) return rc;
+    if ((rc = upload_known_scan(f, blobs, B, ids, false, &ks, &rs))) return rc;
+    if (ks.o_rng) ex.rng = reinterpret_cast<const double*>(f->scan_dev + ks.o_rng);
     ex.single_sightings = ks.single_sightings;
     ex.gmax_key = ctl_gmax_key(f);
     {
@@ -862,7 +904,8 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   // maximum-likelihood association on the device
   AssocLaunch al;
   // (ids wanted: the association kernel + k_observe; growing maps: a publish / subscribe kernel, or that)
-  if ((rc = enqueue_association(f, blobs, B, false, ids_out == nullptr, &al, grow, true))) return rc;
+  if ((rc = enqueue_association(f, blobs, B, false, ids_out == nullptr, &al, grow, true, &rs))) return rc;
+  ex.rng = al.rng;
   const ScanPlan& plan = al.plan;
   // the colour table's mode: this scan takes the table-mode kernel, or the mode ends here (the slots get their colour rows first)
   if (plan.colour_table ? (rc = ct_engage(f)) : (rc = ct_end(f))) return rc;
@@ -975,6 +1018,8 @@ int pk_observe_fresh(pk_filter* f, const double* blobs, int32_t B, const int32_t
 
 int pk_stage_scan(pk_filter* f, const double* blobs, int32_t B) {
   if (!f) return fail(PK_ERR_INVALID, "pk_stage_scan: NULL handle");
+  RangeScan rs;
+  if (int rr = ranges_take(f, "pk_stage_scan", B, &rs)) return rr;
   if (B < 1 || !blobs) return fail(PK_ERR_INVALID, "pk_stage_scan: needs at least one blob");
   if (!f->map_loaded) return fail(PK_ERR_STATE, "pk_stage_scan: no map uploaded (pk_upload_map)");
   for (int i = 0; i < 4 * B; ++i)
@@ -986,7 +1031,7 @@ int pk_stage_scan(pk_filter* f, const double* blobs, int32_t B) {
     return PK_OK;
   }
   f->dense_staged.clear();
-  return stage_ml_scan(f, blobs, B);
+  return stage_ml_scan(f, blobs, B, &rs);
 }
 
 int pk_observe_staged(pk_filter* f, int32_t fresh) {
@@ -1053,6 +1098,8 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
 
 int pk_associate(pk_filter* f, const double* blobs, int32_t B, int32_t* ids_out) {
   if (!f || !ids_out) return fail(PK_ERR_INVALID, "pk_associate: NULL argument");
+  RangeScan rs;
+  if (int rr = ranges_take(f, "pk_associate", B, &rs)) return rr;
   if (B < 0 || (B > 0 && !blobs)) return fail(PK_ERR_INVALID, "pk_associate: bad blobs");
   if (!f->map_loaded) return fail(PK_ERR_STATE, "pk_associate: no map uploaded (pk_upload_map)");
   if (B == 0) return PK_OK;
@@ -1064,7 +1111,7 @@ int pk_associate(pk_filter* f, const double* blobs, int32_t B, int32_t* ids_out)
   if ((rc = ensure_colour_rows(f))) return rc;  // (the colour table's mode goes on: nothing is updated)
   {
     const bool keep = f->ct_eligible, engaged = f->ct_engaged;  // (enqueue_association ends the mode where it launches the general association)
-    rc = enqueue_association(f, blobs, B, true, false, nullptr);
+    rc = enqueue_association(f, blobs, B, true, false, nullptr, false, false, &rs);
     f->ct_eligible = keep;
     f->ct_engaged = engaged;
   }

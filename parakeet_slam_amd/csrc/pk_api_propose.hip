@@ -53,6 +53,7 @@ int copy_poses(pk_filter* f, bool save) {
 int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const double* z, uint64_t seed, uint64_t draw,
                  const double* blobs, int32_t B, const int32_t* ids, bool fresh, int32_t* ids_out) {
   int rc;
+  if ((rc = refuse_ranges_proposal(f, who))) return rc;  // (armed ranges, pk_scan_ranges: refused and gone)
   if ((rc = refuse_proposal(f, who))) return rc;
   if (B < 0 || (B > 0 && !blobs)) return fail(PK_ERR_INVALID, "%s: bad blobs", who);
   if (!f->map_loaded) return fail(PK_ERR_STATE, "%s: no map uploaded (pk_upload_map)", who);

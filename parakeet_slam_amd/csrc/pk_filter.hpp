@@ -8,6 +8,7 @@
 //   pk_api_adaptive.hip adaptive resampling: the gated resample and step, the weight sums, the weighted pose summary
 //   pk_api_mapmatch.hip the discovered landmarks: the matched moments and the finished estimate
 //   pk_api_propose.hip  the measurement-informed proposal: pk_propose, pk_propose_odom, pk_proposal_download
+//   pk_api_range.hip    range-bearing scans: pk_scan_ranges, what consumes the armed ranges, their refusals
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -121,6 +122,16 @@ struct AssocLaunch {
   const double* dir = nullptr;
   const double* exact = nullptr;
   const unsigned short* order = nullptr;
+  // a scan with at least one ranged blob (pk_scan_ranges): its range rows [B][2] (range, variance) in scan order and in cell order
+  const double* rng = nullptr;
+  const double* rng_cell = nullptr;
+};
+
+// The ranges a consuming call took from the filter (ranges_take): rows [B][2] (range, variance; NaN range = none).  armed: ranges
+// were named for this scan at all; any: some blob has one -- only then does the scan stage them and take the range kernels.
+struct RangeScan {
+  bool armed = false, any = false;
+  std::vector<double> rv;
 };
 
 // What pk_set_option sets: every tuning knob with its default.  (Protocol state that an option name also reaches -- the loopback
@@ -250,7 +261,15 @@ struct pk_filter {
     bool use_grid = false;
     size_t tab_bytes = 0;
     bool uploaded = false;  // pk_step sent the block to the device together with the motion kernel
+    bool with_ranges = false;  // the scan was staged with ranges named for it (pk_scan_ranges) ...
+    bool ranged = false;       // ... of which at least one is finite: 32 B bytes of range rows lie behind the block (staged_upload_bytes)
   } staged;
+  // pk_scan_ranges: the ranges of the next scan, on the host until a call that takes blobs consumes them (pk_api_range.hip)
+  struct Ranges {
+    bool armed = false, any = false;
+    int32_t B = 0;
+    std::vector<double> rv;  // [B][2] range, variance
+  } rng;
   int route = PK_ROUTE_NONE;  // kernels used by the last observe
   unsigned* bcnt_dev = nullptr;  // [bcand_cap] entries of the blobs' inverse candidate lists
   uint4* brec_dev = nullptr;     // [bcand_cap] the lists
@@ -507,11 +526,15 @@ struct StepMotion {
 // else they carry over and pk_resample_adaptive ends it with the threshold *gate
 int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
               int32_t B, const int32_t* ids, double u, int32_t weight_domain, const double* gate);
-// bytes of a staged ML scan block that the device needs: ctl | blobs + directions | exact records | [tables]
-inline size_t staged_upload_bytes(const pk_filter::Staged& sg) {
+// bytes of a staged ML scan block that the device needs: ctl | blobs + directions | exact records | [tables] | [range rows]
+// (staged_range_offset: where the range rows of a ranged scan lie -- [B][2] in scan order, then [B][2] in cell order)
+inline size_t staged_range_offset(const pk_filter::Staged& sg) {
   const size_t o_exact = kCtlBytes + (size_t)sg.B * 6 * sizeof(double);
   const size_t o_tab = o_exact + (size_t)sg.B * 6 * sizeof(double);
   return sg.use_grid ? o_tab + sg.tab_bytes : o_exact;
+}
+inline size_t staged_upload_bytes(const pk_filter::Staged& sg) {
+  return staged_range_offset(sg) + (sg.ranged ? (size_t)sg.B * 4 * sizeof(double) : 0);
 }
 // the body pk_motion and pk_motion_odom share behind their argument checks: the copy of a supplied z, the PK_T_MOTION span, the
 // staged scan that rides the launch, pose_part_ok.  launch(z_dev, up_dst_dev, up_src_host_mapped, up_bytes) is the kernel's.
@@ -528,7 +551,7 @@ int colour_rows_for_download(pk_filter* f, int64_t p0, int64_t p1);
 int ct_end(pk_filter* f);
 int ct_maps_untouched(pk_filter* f, bool* untouched);
 void blob_directions(const double* blobs, int B, double* dir);
-int stage_ml_scan(pk_filter* f, const double* blobs, int B);
+int stage_ml_scan(pk_filter* f, const double* blobs, int B, const RangeScan* rs = nullptr);
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out, bool reset);
 // a proposal step's scan on the device (pk_api_propose.hip): where its parts lie.  first / next: supplied ids' chains (the ids
 // are final); dir: the rays that settle tentative ids; ids: one row of B (supplied) or ids_dev's [P][B]
@@ -543,6 +566,14 @@ int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* i
 void proposal_observed(pk_filter* f, bool known);
 // what the bearing model (pk_set_measurement_model) has no kernels for, refused while it is on (a NULL handle passes)
 int refuse_bearing(const pk_filter* f, const char* who, const char* what);
+// pk_api_range.hip: the armed ranges of the next scan (pk_scan_ranges).  ranges_take: what every call that takes blobs starts
+// with -- the ranges leave the filter whatever follows, and come back in *out unless the call is refused (refuse_ranges: the
+// refusals and their precedence); ranges_check: the refusals alone, ahead of a step's motion (the ranges stay unless it refuses)
+int refuse_ranges(const pk_filter* f, const char* who, int32_t B, int32_t armed_B);
+int ranges_take(pk_filter* f, const char* who, int32_t B, RangeScan* out);
+int ranges_check(pk_filter* f, const char* who, int32_t B);
+void ranges_disarm(pk_filter* f);
+int refuse_ranges_proposal(pk_filter* f, const char* who);
 // pk_api_shard.hip
 int refuse_balanced(const pk_filter* f, const char* who);
 int refuse_path(const pk_filter* f, const char* who);

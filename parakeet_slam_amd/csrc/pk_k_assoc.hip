@@ -5,6 +5,7 @@
 #include "pk_colour.hpp"
 #include "pk_device.hpp"
 #include "pk_pub_math.hpp"
+#include "pk_range_math.hpp"
 
 namespace pk {
 
@@ -22,13 +23,18 @@ struct AssocArgs {
   const double* blobdir;  // B x 2 unit ray direction (closest_point :510)
   int32_t* ids;           // P x B
   int L, Lp, B;
+  // the range instances alone (pk_scan_ranges): B x 2 (range, variance), NaN range = none -- in scan order for the brute-force
+  // kernel, in cell order beside the exact records for the grid kernel -- and Qt[0][0], which the measured point's covariance takes
+  const double* rng;
+  double q00;
 };
 
-template <int MODEL = kModelReference>
+// RANGE: a blob with a finite range takes the density of its measured point (pk_range_math.hpp); the colour probability as ever
+template <int MODEL = kModelReference, bool RANGE = false>
 __device__ __forceinline__ double match_probability_lazy(const double* f, const int* cnt, int Lp, int l,
                                                          Landmark<double>& lm, bool& have_cov, double sx,
                                                          double sy, double pse, const BlobT<double>& z,
-                                                         double ux, double uy) {
+                                                         double ux, double uy, BlobRange r = BlobRange{0.0, 0.0}, double q00 = 0.0) {
   if (!have_cov) {
     lm.pxx = f[F_PXX * Lp + l];
     lm.pxy = f[F_PXY * Lp + l];
@@ -41,13 +47,16 @@ __device__ __forceinline__ double match_probability_lazy(const double* f, const 
     lm.cbb = f[F_CBB * Lp + l];
     have_cov = true;
   }
+  if constexpr (RANGE)
+    if (r.has()) return match_value_range(lm, sx, sy, z, ux, uy, r.rho, r.qr, q00);
   double bp = 500.0 * prob_position_match<double, MODEL>(lm, sx, sy, pse, z.bearing, ux, uy);
   double cp = 500.0 * prob_color_match(lm, z.r, z.g, z.b);
   return bp * cp / 250000.0;
 }
 
 // MODEL = kModelBearing: the wrapped gate, the blob's ray turned by the heading (ch, sn) = (cos sh, sin sh)
-template <int PASS, int MODEL = kModelReference>
+// RANGE: the blob loop is uniform over the workgroup (every lane looks at blob b), so whether b has a range is wave-uniform
+template <int PASS, int MODEL = kModelReference, bool RANGE = false>
 __device__ __forceinline__ void assoc_pass(const AssocArgs& a, const double* f, const int* cnt, double sx,
                                            double sy, double sh, unsigned long long* best, int* bid, double ch = 1.0,
                                            double sn = 0.0) {
@@ -71,7 +80,11 @@ __device__ __forceinline__ void assoc_pass(const AssocArgs& a, const double* f, 
       if (fabs(color_distance2(lm.mr, lm.mg, lm.mb, z.r, z.g, z.b)) > 300.0) continue;  // :441
       double ux = a.blobdir[2 * b], uy = a.blobdir[2 * b + 1];
       if constexpr (MODEL == kModelBearing) rotate_ray(ux, uy, ch, sn, ux, uy);
-      double pr = match_probability_lazy<MODEL>(f, cnt, a.Lp, l, lm, have_cov, sx, sy, pse, z, ux, uy);
+      double pr;
+      if constexpr (RANGE)
+        pr = match_probability_lazy<MODEL, true>(f, cnt, a.Lp, l, lm, have_cov, sx, sy, pse, z, ux, uy, load_range(a.rng, b), a.q00);
+      else
+        pr = match_probability_lazy<MODEL>(f, cnt, a.Lp, l, lm, have_cov, sx, sy, pse, z, ux, uy);
       if (!(pr > 0.0)) continue;
       unsigned long long bits = (unsigned long long)__double_as_longlong(pr);
       if (PASS == 0) {
@@ -83,7 +96,7 @@ __device__ __forceinline__ void assoc_pass(const AssocArgs& a, const double* f, 
   }
 }
 
-template <int MODEL>
+template <int MODEL, bool RANGE = false>
 __device__ __forceinline__ void assoc_brute_body(const AssocArgs& a) {
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned long long* best = reinterpret_cast<unsigned long long*>(smem);
@@ -100,18 +113,19 @@ __device__ __forceinline__ void assoc_brute_body(const AssocArgs& a) {
   double ch = 1.0, sn = 0.0;
   if constexpr (MODEL == kModelBearing) sincos(sh, &sn, &ch);
   __syncthreads();
-  assoc_pass<0, MODEL>(a, f, cnt, sx, sy, sh, best, bid, ch, sn);
+  assoc_pass<0, MODEL, RANGE>(a, f, cnt, sx, sy, sh, best, bid, ch, sn);
   __syncthreads();
-  assoc_pass<1, MODEL>(a, f, cnt, sx, sy, sh, best, bid, ch, sn);
+  assoc_pass<1, MODEL, RANGE>(a, f, cnt, sx, sy, sh, best, bid, ch, sn);
   __syncthreads();
   for (int b = threadIdx.x; b < a.B; b += blockDim.x)
     a.ids[(size_t)p * a.B + b] = best[b] != 0ull ? bid[b] + 1 : 0;
 }
 __global__ void __launch_bounds__(256) k_assoc_brute(AssocArgs a) { assoc_brute_body<kModelReference>(a); }
 __global__ void __launch_bounds__(256) k_assoc_brute_bearing(AssocArgs a) { assoc_brute_body<kModelBearing>(a); }
+__global__ void __launch_bounds__(256) k_assoc_brute_range(AssocArgs a) { assoc_brute_body<kModelBearing, true>(a); }
 
 void launch_assoc_brute(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev, int B,
-                        int32_t* ids_dev, int model) {
+                        int32_t* ids_dev, int model, const double* rng_dev, double q00) {
   if (d.P == 0 || B == 0) return;
   AssocArgs a;
   a.ss = slot_source(d);
@@ -126,14 +140,19 @@ void launch_assoc_brute(hipStream_t s, DeviceState& d, const double* blobs_dev, 
   a.L = d.lay.L;
   a.Lp = d.lay.Lp;
   a.B = B;
+  a.rng = rng_dev;
+  a.q00 = q00;
   const size_t lds = assoc_brute_lds_bytes(B);  // <= kMaxDynLds: checked by the caller
   static bool attr_set[kMaxDevices] = {false};
   if (first_time_on_this_device(attr_set)) {
-    for (const void* fn : {reinterpret_cast<const void*>(k_assoc_brute), reinterpret_cast<const void*>(k_assoc_brute_bearing)})
+    for (const void* fn : {reinterpret_cast<const void*>(k_assoc_brute), reinterpret_cast<const void*>(k_assoc_brute_bearing),
+                           reinterpret_cast<const void*>(k_assoc_brute_range)})
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess)
         (void)hipGetLastError();
   }
-  if (model == kModelBearing)
+  if (model == kModelBearing && rng_dev)
+    hipLaunchKernelGGL(k_assoc_brute_range, dim3((unsigned)d.P), dim3(256), lds, s, a);
+  else if (model == kModelBearing)
     hipLaunchKernelGGL(k_assoc_brute_bearing, dim3((unsigned)d.P), dim3(256), lds, s, a);
   else
     hipLaunchKernelGGL(k_assoc_brute, dim3((unsigned)d.P), dim3(256), lds, s, a);
@@ -201,13 +220,19 @@ size_t blob_grid_table_bytes(int ncell, int B, int n9) {
 
 // probability_of_match (:383-455) of landmark l for the blob record rec = (bearing, r, g, b, ux, uy)
 // (MODEL = kModelBearing: the ray turned by the heading, (ch, sn) = (cos sh, sin sh))
-template <int MODEL = kModelReference>
+// RANGE: rv = the blob's (range, variance); a finite range takes probability_of_match_range
+template <int MODEL = kModelReference, bool RANGE = false>
 __device__ __forceinline__ double full_match_probability(const double* f, int Lp, int l, double sx, double sy,
-                                                         double sh, const double* rec, double ch = 1.0, double sn = 0.0) {
+                                                         double sh, const double* rec, double ch = 1.0, double sn = 0.0,
+                                                         const double* rv = nullptr, double q00 = 0.0) {
   const Landmark<double> lm = load_landmark_nocount(f, Lp, l);
   BlobT<double> z{rec[0], rec[1], rec[2], rec[3]};
   double ux = rec[4], uy = rec[5];
   if constexpr (MODEL == kModelBearing) rotate_ray(ux, uy, ch, sn, ux, uy);
+  if constexpr (RANGE) {
+    const BlobRange r = load_range(rv, 0);
+    if (r.has()) return probability_of_match_range(lm, sx, sy, sh, z, ux, uy, r.rho, r.qr, q00);
+  }
   return probability_of_match<double, MODEL>(lm, sx, sy, sh, z, ux, uy);
 }
 
@@ -226,7 +251,9 @@ __device__ unsigned long long pk_stamp_acc[16];
 // the GENERAL = true instance launched with only_flagged.
 // The body of k_assoc_grid and of k_assoc_grid_bearing, the GENERAL instance for the bearing model (MODEL = kModelBearing: both
 // bearing gates take the wrapped difference -- S1's fp32 screen against g.thrb32w --, the probabilities of S3 / S4 the turned ray).
-template <int THREADS, bool DUP, bool GENERAL, int SLOTS, int MODEL>
+// RANGE (k_assoc_grid_range): S1 and S2 test gates alone and are what they were; S3 and S4, whose lanes hold different blobs, take
+// the measured point's density for a blob with a finite range and the bearing model's for one without -- a per-lane choice.
+template <int THREADS, bool DUP, bool GENERAL, int SLOTS, int MODEL, bool RANGE = false>
 __device__ __forceinline__ void assoc_grid_body(const AssocGridArgs& ga) {
   static_assert(MODEL == kModelReference || GENERAL, "the bearing model has no hand-off instance");
   extern __shared__ __align__(16) unsigned char smem[];
@@ -576,7 +603,8 @@ __device__ __forceinline__ void assoc_grid_body(const AssocGridArgs& ga) {
       }
       if (valid) {
         lcand = cand[4 * t + k];
-        const double pr = full_match_probability<MODEL>(f, a.Lp, lcand, sx, sy, sh, ga.exact + 6 * (size_t)t, ch, sn);
+        const double pr = full_match_probability<MODEL, RANGE>(f, a.Lp, lcand, sx, sy, sh, ga.exact + 6 * (size_t)t, ch, sn,
+                                                                        RANGE ? a.rng + 2 * (size_t)t : nullptr, a.q00);
         if (pr > 0.0) {
           bits = (unsigned long long)__double_as_longlong(pr);
           atomicMax(&s3_best[slot], bits);
@@ -602,7 +630,7 @@ __device__ __forceinline__ void assoc_grid_body(const AssocGridArgs& ga) {
         const double mx = f[F_MX * a.Lp + l2], my = f[F_MY * a.Lp + l2];
         const double eb = pk_atan2(my - sy, mx - sx) - sh;
         if (fabs(MODEL == kModelBearing ? wrap_angle(zb - eb) : zb - eb) > 0.5) continue;
-        const double pr = full_match_probability<MODEL>(f, a.Lp, l2, sx, sy, sh, rec, ch, sn);
+        const double pr = full_match_probability<MODEL, RANGE>(f, a.Lp, l2, sx, sy, sh, rec, ch, sn, RANGE ? a.rng + 2 * (size_t)t : nullptr, a.q00);
         if (pr > pm) {
           pm = pr;
           best = l2;
@@ -627,6 +655,11 @@ __global__ void __launch_bounds__(THREADS) k_assoc_grid(AssocGridArgs ga) {
 template <int THREADS, bool DUP>
 __global__ void __launch_bounds__(THREADS) k_assoc_grid_bearing(AssocGridArgs ga) {
   assoc_grid_body<THREADS, DUP, true, kFastSlots, kModelBearing>(ga);
+}
+
+template <int THREADS, bool DUP>
+__global__ void __launch_bounds__(THREADS) k_assoc_grid_range(AssocGridArgs ga) {
+  assoc_grid_body<THREADS, DUP, true, kFastSlots, kModelBearing, true>(ga);
 }
 
 #ifdef PK_STAMPS
@@ -696,6 +729,8 @@ void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& gri
   a.h = d.h[d.cur];
   a.blobs = nullptr;
   a.blobdir = nullptr;
+  a.rng = nullptr;
+  a.q00 = 0.0;
   a.ids = ids_dev;
   a.L = d.lay.L;
   a.Lp = d.lay.Lp;
@@ -768,7 +803,7 @@ void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& gri
 
 // The bearing model: the general instance over every particle -- no hand-off, no candidate lists, no flags.
 void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9, const unsigned char* tables_dev,
-                               const double* exact_dev, int32_t* ids_dev, bool finalize) {
+                               const double* exact_dev, int32_t* ids_dev, bool finalize, const double* rng_cell_dev, double q00) {
   if (d.P == 0 || B == 0) return;
   AssocGridArgs ga{};
   AssocArgs& a = ga.a;
@@ -789,8 +824,24 @@ void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, int B, const BlobG
   ga.finalize = finalize ? 1 : 0;
   ga.n9 = n9;
   ga.cand_slots = kCandSlots;
+  a.rng = rng_cell_dev;
+  a.q00 = q00;
   const size_t lds = assoc_grid_lds_bytes(grid.ncell, B, n9);
   const bool big = lds > 40 * 1024;  // as launch_assoc_grid sizes its general instance
+  if (rng_cell_dev) {  // a scan with ranged blobs: the range instances, sized the same way
+    if (n9 > 0) {
+      if (big)
+        launch_assoc_grid_k<k_assoc_grid_range<512, true>, 512>(s, ga, lds, d.P);
+      else
+        launch_assoc_grid_k<k_assoc_grid_range<256, true>, 256>(s, ga, lds, d.P);
+    } else {
+      if (big)
+        launch_assoc_grid_k<k_assoc_grid_range<512, false>, 512>(s, ga, lds, d.P);
+      else
+        launch_assoc_grid_k<k_assoc_grid_range<256, false>, 256>(s, ga, lds, d.P);
+    }
+    return;
+  }
   if (n9 > 0) {
     if (big)
       launch_assoc_grid_k<k_assoc_grid_bearing<512, true>, 512>(s, ga, lds, d.P);

@@ -7,6 +7,7 @@
 #include "pk_device.hpp"
 #include "pk_filter.hpp"
 #include "pk_pub_math.hpp"
+#include "pk_range_math.hpp"
 
 namespace pk {
 
@@ -180,6 +181,59 @@ __global__ void __launch_bounds__(256) k_probe_bearing(const double* __restrict_
   }
 }
 
+// Range-bearing blobs (pk_probe_range): the rows of pk_probe_bearing with the blob's range and its variance behind them (and, for
+// the match, Qt[0][0], which the measured point's covariance takes).  A NaN range takes the bearing model's functions, as in the kernels.
+constexpr int kRangeMatchIn = 26, kRangeEkfIn = 33, kRangeEkfOut = 16;
+template <int WHAT>
+__global__ void __launch_bounds__(256) k_probe_range(const double* __restrict__ in, double* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if constexpr (WHAT == 0) {
+    const double* r = in + (int64_t)kRangeMatchIn * i;
+    const double sx = r[0], sy = r[1], heading = r[2];
+    const Landmark<double> lm = landmark_of_row(r + 3, 0);
+    const BlobT<double> z{r[17], r[18], r[19], r[20]};
+    const BlobRange br{r[23], r[24]};
+    const double q00 = r[25];
+    double sn, ch, wx, wy;
+    sincos(heading, &sn, &ch);
+    rotate_ray(r[21], r[22], ch, sn, wx, wy);
+    double* o = out + (int64_t)kMatchOut * i;
+    if (br.has()) {
+      o[0] = probability_of_match_range(lm, sx, sy, heading, z, wx, wy, br.rho, br.qr, q00);
+      o[1] = prob_position_match_range(lm, sx, sy, wx, wy, br.rho, br.qr, q00, o + 3);
+    } else {
+      const double pse = pk_atan2(lm.my - sy, lm.mx - sx);
+      o[0] = probability_of_match<double, kModelBearing>(lm, sx, sy, heading, z, wx, wy);
+      o[1] = prob_position_match<double, kModelBearing>(lm, sx, sy, pse, z.bearing, wx, wy, o + 3);
+    }
+    o[2] = prob_color_match(lm, z.r, z.g, z.b);
+  } else {
+    const double* r = in + (int64_t)kRangeEkfIn * i;
+    Landmark<double> lm = landmark_of_row(r + 3, (int)r[17]);
+    const BlobT<double> z{r[18], r[19], r[20], r[21]};
+    const Noise<double> qt = make_noise(r[22], r[23], r[24], r[25], r[26], r[27], r[28]);
+    const double pse = r[29];
+    const int flags = (int)r[30];
+    const bool immutable = (flags & 1) != 0;
+    const BlobRange br{r[31], r[32]};
+    const bool known = (flags & 2) != 0;  // (each call with its pointer known at compile time, as the kernels call it)
+    double logw;
+    if (br.has() && known)
+      logw = ekf_update_range(lm, r[0], r[1], r[2], z, br.rho, br.qr, qt, immutable, &pse);
+    else if (br.has())
+      logw = ekf_update_range(lm, r[0], r[1], r[2], z, br.rho, br.qr, qt, immutable);
+    else if (known)
+      logw = ekf_update<double, true, kModelBearing>(lm, r[0], r[1], z, qt, immutable, nullptr, &pse, nullptr, r[2]);
+    else
+      logw = ekf_update<double, true, kModelBearing>(lm, r[0], r[1], z, qt, immutable, nullptr, nullptr, nullptr, r[2]);
+    double* o = out + (int64_t)kRangeEkfOut * i;
+    o[0] = logw;
+    row_of_landmark(lm, o + 1);
+    o[15] = (double)lm.count;
+  }
+}
+
 namespace {
 
 template <int OP>
@@ -288,5 +342,39 @@ extern "C" int pk_probe_bearing(int32_t device, int32_t what, int64_t n, const d
   if (e == hipSuccess) e = hipMemcpy(out, dev + n_in, n_out * sizeof(double), hipMemcpyDeviceToHost);
   (void)hipFree(dev);
   if (e != hipSuccess) return fail(PK_ERR_HIP, "pk_probe_bearing: %s", hipGetErrorString(e));
+  return PK_OK;
+}
+
+extern "C" int pk_probe_range(int32_t device, int32_t what, int64_t n, const double* in, double* out) {
+  if (!in || !out) return fail(PK_ERR_INVALID, "pk_probe_range: NULL argument");
+  if (what != 0 && what != 1) return fail(PK_ERR_INVALID, "pk_probe_range: what = %d is neither 0 (the match probabilities) nor 1 (the update)", what);
+  if (n < 0 || n > 2147483647LL) return fail(PK_ERR_INVALID, "pk_probe_range: n = %lld out of range", (long long)n);
+  const int arity = what == 0 ? pk::kRangeMatchIn : pk::kRangeEkfIn, outputs = what == 0 ? pk::kMatchOut : pk::kRangeEkfOut;
+  if (what == 1)
+    for (int64_t i = 0; i < n; ++i) {
+      const double fl = in[(size_t)i * arity + 30];
+      if (!(fl == 0.0 || fl == 1.0 || fl == 2.0 || fl == 3.0))
+        return fail(PK_ERR_INVALID, "pk_probe_range: row %lld: flags take bit 0 (immutable) and bit 1 (zhat0 known) only", (long long)i);
+    }
+  int ndev = pk_device_count();
+  if (ndev <= 0) return fail(PK_ERR_HIP, "pk_probe_range: no HIP device visible (the HIP path has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(PK_ERR_INVALID, "pk_probe_range: device %d of %d", device, ndev);
+  if (n == 0) return PK_OK;
+  PK_HIP(hipSetDevice(device));
+  const size_t n_in = (size_t)n * arity, n_out = (size_t)n * outputs;
+  double* dev = nullptr;
+  PK_HIP(hipMalloc((void**)&dev, (n_in + n_out) * sizeof(double)));
+  hipError_t e = hipMemcpy(dev, in, n_in * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (what == 0)
+      hipLaunchKernelGGL(pk::k_probe_range<0>, grid, dim3(256), 0, nullptr, dev, dev + n_in, n);
+    else
+      hipLaunchKernelGGL(pk::k_probe_range<1>, grid, dim3(256), 0, nullptr, dev, dev + n_in, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dev + n_in, n_out * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(dev);
+  if (e != hipSuccess) return fail(PK_ERR_HIP, "pk_probe_range: %s", hipGetErrorString(e));
   return PK_OK;
 }

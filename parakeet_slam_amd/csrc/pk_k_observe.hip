@@ -5,6 +5,7 @@
 // Hand-written gfx950 (CDNA4, wave64) kernels of the FastSLAM particle update; see DESIGN.md
 // section 4.  No MFMA: the algebra is 2x2 / 3x3 and register resident (pk_math.hpp).
 #include "pk_device.hpp"
+#include "pk_range_math.hpp"
 
 namespace pk {
 
@@ -26,6 +27,7 @@ struct ObserveArgs {
   double* logw;
   const double* blobs;   // B x 4
   const double* blobdir; // ML: B x 2 unit ray directions (closest_point :510)
+  const double* rng;     // the range instances alone: B x 2 (range, variance) in scan order, NaN range = none (pk_scan_ranges)
   const int32_t* first;  // KNOWN: [L] first blob matched to landmark l, or -1
   const int32_t* next;   // KNOWN: [B] next blob matched to the same landmark, or -1
   int32_t* ids;          // ML: [P x B]; a tentative id whose probability is 0 is reset to 0
@@ -47,7 +49,10 @@ struct ObserveArgs {
 // apply the surviving ones sequentially.
 // MODEL = kModelBearing: (sh, ch, sn) = the particle's heading with its cosine and sine (one sincos per particle).
 // SETTLED (k_observe_proposed): the ids are final -- k_propose settled them at the predicted pose; there is no second settling.
-template <bool KNOWN, int MODEL = kModelReference, bool SETTLED = false>
+// RANGE (k_observe_range, bearing model): a blob with a finite range is settled and applied as a range-bearing measurement
+// (pk_range_math.hpp); one without takes the bearing model's path, decided blob by blob.  Each lane walks its OWN landmark's chain,
+// so the choice is per lane: a wave whose lanes hold ranged and unranged blobs at the same chain position runs both paths in turn.
+template <bool KNOWN, int MODEL = kModelReference, bool SETTLED = false, bool RANGE = false>
 __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, double sx, double sy,
                                               const ObserveArgs& a, const int32_t* first,
                                               const int32_t* next, int32_t* s_ids, int32_t* gid, double sh = 0.0,
@@ -62,7 +67,15 @@ __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, doubl
       const BlobT<double> z = load_blob(a.blobs, b);
       double2 dir = *reinterpret_cast<const double2*>(a.blobdir + 2 * (size_t)b);
       if constexpr (MODEL == kModelBearing) rotate_ray(dir.x, dir.y, ch, sn, dir.x, dir.y);
-      if (!match_is_positive<MODEL>(lm, sx, sy, pse, z, dir.x, dir.y)) {
+      bool positive;
+      if constexpr (RANGE) {
+        const BlobRange r = load_range(a.rng, b);
+        positive = r.has() ? match_is_positive_range(lm, sx, sy, z, dir.x, dir.y, r.rho, r.qr, a.qt.q00)
+                           : match_is_positive<MODEL>(lm, sx, sy, pse, z, dir.x, dir.y);
+      } else {
+        positive = match_is_positive<MODEL>(lm, sx, sy, pse, z, dir.x, dir.y);
+      }
+      if (!positive) {
         s_ids[b] = 0;
         gid[b] = 0;
       }
@@ -75,6 +88,14 @@ __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, doubl
       continue;
     }
     const BlobT<double> z = load_blob(a.blobs, b);
+    if constexpr (RANGE) {
+      const BlobRange r = load_range(a.rng, b);
+      if (r.has()) {
+        acc += ekf_update_range(lm, sx, sy, sh, z, r.rho, r.qr, a.qt, imm, fresh ? &pse : (const double*)nullptr);
+        fresh = imm;
+        continue;
+      }
+    }
     if constexpr (MODEL == kModelBearing)
       acc += ekf_update<double, true, MODEL>(lm, sx, sy, z, a.qt, imm, (EkfAux<double>*)nullptr, fresh ? &pse : (const double*)nullptr,
                                              (double*)nullptr, sh);
@@ -88,7 +109,7 @@ __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, doubl
 // The body of k_observe and of k_observe_bearing, its instance for the bearing model (a kernel of its own: the reference model's
 // kernels keep their names and what they compute).  PROPOSED: k_observe_proposed, behind k_propose -- the ids are final and the
 // weight increment is dlogw[p].
-template <bool KNOWN, int NV, int MODEL, bool PROPOSED = false>
+template <bool KNOWN, int NV, int MODEL, bool PROPOSED = false, bool RANGE = false>
 __device__ __forceinline__ void observe_body(const ObserveArgs& a, const double* dlogw = nullptr) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ double red[kObsThreads / kWave];
@@ -172,8 +193,8 @@ __device__ __forceinline__ void observe_body(const ObserveArgs& a, const double*
                          v[8].x, v[9].x, v[10].x, v[11].x, v[12].x, v[13].x, c.x};
       Landmark<double> Bq{v[0].y, v[1].y, v[2].y, v[3].y, v[4].y, v[5].y, v[6].y, v[7].y,
                           v[8].y, v[9].y, v[10].y, v[11].y, v[12].y, v[13].y, c.y};
-      if (l0 < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED>(A, l0, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
-      if (l0 + 1 < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED>(Bq, l0 + 1, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
+      if (l0 < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED, RANGE>(A, l0, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
+      if (l0 + 1 < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED, RANGE>(Bq, l0 + 1, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
       __builtin_nontemporal_store(d2v{A.mx, Bq.mx}, reinterpret_cast<d2v*>(df + (size_t)F_MX * Lp + l0));
       __builtin_nontemporal_store(d2v{A.my, Bq.my}, reinterpret_cast<d2v*>(df + (size_t)F_MY * Lp + l0));
       __builtin_nontemporal_store(d2v{A.mr, Bq.mr}, reinterpret_cast<d2v*>(df + (size_t)F_MR * Lp + l0));
@@ -194,7 +215,7 @@ __device__ __forceinline__ void observe_body(const ObserveArgs& a, const double*
     // one landmark per lane: half the registers, twice the waves in flight
     for (int l = tid; l < Lp; l += kObsThreads) {
       Landmark<double> A = load_landmark(sf, sc, Lp, l);
-      if (l < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED>(A, l, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
+      if (l < a.L) acc += apply_blobs<KNOWN, MODEL, PROPOSED, RANGE>(A, l, sx, sy, a, first, next, s_ids_mut, gid_mut, sh, ch, sn);
       __builtin_nontemporal_store(A.mx, &df[(size_t)F_MX * Lp + l]);
       __builtin_nontemporal_store(A.my, &df[(size_t)F_MY * Lp + l]);
       __builtin_nontemporal_store(A.mr, &df[(size_t)F_MR * Lp + l]);
@@ -234,6 +255,11 @@ __global__ void __launch_bounds__(kObsThreads) k_observe(ObserveArgs a) {
 template <bool KNOWN, int NV>
 __global__ void __launch_bounds__(kObsThreads) k_observe_bearing(ObserveArgs a) {
   observe_body<KNOWN, NV, kModelBearing>(a);
+}
+// ... and its instances for scans that hold at least one ranged blob (pk_scan_ranges)
+template <bool KNOWN, int NV>
+__global__ void __launch_bounds__(kObsThreads) k_observe_range(ObserveArgs a) {
+  observe_body<KNOWN, NV, kModelBearing, false, true>(a);
 }
 template <bool KNOWN, int NV>
 __global__ void __launch_bounds__(kObsThreads) k_observe_proposed(ObserveArgs a, const double* dlogw) {
@@ -312,6 +338,7 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
   a.logw = d.logw[d.cur];
   a.blobs = blobs_dev;
   a.blobdir = blobdir_dev;
+  a.rng = ex.rng;
   a.first = first_dev;
   a.next = next_dev;
   a.ids = ids_dev;
@@ -340,6 +367,19 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
           (void)hipGetLastError();
       }
       hipLaunchKernelGGL((k_observe_proposed<false, 1>), dim3(grid), dim3(kObsThreads), lds, s, a, ex.dlogw);
+    }
+  } else if (ex.model == kModelBearing && ex.rng) {  // a scan with ranged blobs: the bearing model's two shapes again
+    if (ids_dev == nullptr) {
+      hipLaunchKernelGGL((k_observe_range<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a);
+    } else {
+      const size_t lds = observe_general_lds_bytes(d.lay.Lp, B);  // <= kMaxDynLds: checked by the caller
+      static bool attr_set[kMaxDevices] = {false};
+      if (first_time_on_this_device(attr_set)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_observe_range<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kMaxDynLds) != hipSuccess)
+          (void)hipGetLastError();
+      }
+      hipLaunchKernelGGL((k_observe_range<false, 1>), dim3(grid), dim3(kObsThreads), lds, s, a);
     }
   } else if (ex.model == kModelBearing) {  // the bearing model: k_observe's two shapes, no loop-free single-sighting kernel
     if (ids_dev == nullptr) {

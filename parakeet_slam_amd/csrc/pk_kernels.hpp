@@ -117,7 +117,7 @@ void launch_reset_weights(hipStream_t s, DeviceState& d);
 // K2: maximum-likelihood association -> ids[P*B]
 // (a) reference kernel: every (landmark, blob) pair is gate-tested
 void launch_assoc_brute(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev,
-                        int B, int32_t* ids_dev, int model = 0);
+                        int B, int32_t* ids_dev, int model = 0, const double* rng_dev = nullptr, double q00 = 0.0);
 // (b) production kernel: blobs bucketed on the host into a 3-D colour grid whose cell edge
 // exceeds the colour gate radius sqrt(300), so a landmark only meets the blobs of its 27
 // neighbouring cells.  Tables (device): start u16[ncell+1] (16-byte padded) | rec32
@@ -203,6 +203,8 @@ struct ObserveExtras {
   int model = 0;                                // launch_observe: the measurement model (pk_math.hpp: kModelReference / kModelBearing)
   int lean = 0;                                 // k_step_pub<2, 512>: lean groups take the lean body (option "pub_lean"); the scan's
   unsigned* lean_stats = nullptr;               //   figures (k_cand_entries), where the kernel counts the pairs that fell back: [6]
+  const double* rng = nullptr;                  // launch_observe, bearing model: the scan's range rows ([B][2] range, variance, scan order;
+                                                //   pk_scan_ranges) -- set only when some blob has a range: k_observe_range
   const double* dlogw = nullptr;                // launch_observe, bearing model: k_observe_proposed -- the ids are FINAL (k_propose settled
                                                 //   them) and the log-weight takes dlogw[p], not the updates' own importance factors
 };
@@ -229,7 +231,8 @@ void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& gri
                        bool finalize, const FastHandoff& fh);
 // the bearing model's association (pk_math.hpp: kModelBearing): the general instance alone, every particle
 void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
-                               const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev, bool finalize);
+                               const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev, bool finalize,
+                               const double* rng_cell_dev = nullptr, double q00 = 0.0);
 // ML observe for L <= kFastMaxL straight from the hand-off: contested blobs are settled here,
 // with the landmark state in registers.  Particles flagged in fh.pflag are skipped (the general
 // k_observe, launched with only_flagged, takes them).
