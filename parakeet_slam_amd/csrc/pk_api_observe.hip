@@ -126,7 +126,10 @@ int colour_rows_for_download(pk_filter* f, int64_t p0, int64_t p1) {
   if (p0 == 0 && p1 == f->d.P) return ensure_colour_rows(f);
   {
     Span t(f, PK_T_MATERIALISE);
-    launch_colour_rows(f->stream, f->d, ct_view(f), f->ct_qt, nullptr, nullptr, p0, p1);
+    ParticleRange range;
+    range.p0 = p0;
+    range.p1 = p1;
+    launch_colour_rows(f->stream, f->d, ct_view(f), f->ct_qt, range);
   }
   PK_LAUNCH_CHECK("colour_rows_for_download");
   return PK_OK;
@@ -515,19 +518,21 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
   AssocLaunch al;
   al.plan = plan_scan(f, B, sg.use_grid, sg.g.ncell, sg.n9, want_fast, finalize, grow, whole);
   const ScanPlan& plan = al.plan;
-  al.grid = sg.g;
-  al.n9 = sg.n9;
-  al.blobs = reinterpret_cast<const double*>(f->scan_dev + o_blobs);
-  al.dir = reinterpret_cast<const double*>(f->scan_dev + o_dir);
+  ScanTables& scan = al.scan;
+  scan.B = B;
+  scan.grid = sg.g;
+  scan.n9 = sg.n9;
+  scan.blobs = reinterpret_cast<const double*>(f->scan_dev + o_blobs);
+  scan.dir = reinterpret_cast<const double*>(f->scan_dev + o_dir);
   if (sg.ranged) {
-    al.rng = reinterpret_cast<const double*>(f->scan_dev + staged_range_offset(sg));
-    al.rng_cell = al.rng + 2 * (size_t)B;
+    scan.rng = reinterpret_cast<const double*>(f->scan_dev + staged_range_offset(sg));
+    scan.rng_cell = scan.rng + 2 * (size_t)B;
   }
   if (sg.use_grid) {
     const size_t cs_b = ((size_t)(sg.g.ncell + 1) * 2 + 15) & ~(size_t)15;
-    al.tables = f->scan_dev + o_tab;
-    al.exact = reinterpret_cast<const double*>(f->scan_dev + o_exact);
-    al.order = reinterpret_cast<const unsigned short*>(f->scan_dev + o_tab + cs_b + (size_t)B * 16 + (size_t)sg.n9 * 2);
+    scan.tables = f->scan_dev + o_tab;
+    scan.exact = reinterpret_cast<const double*>(f->scan_dev + o_exact);
+    scan.order = reinterpret_cast<const unsigned short*>(f->scan_dev + o_tab + cs_b + (size_t)B * 16 + (size_t)sg.n9 * 2);
   }
   if (out) {
     *out = al;
@@ -544,11 +549,11 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
   if ((rc = ct_end(f))) return rc;  // (the general association reads the slots' colour rows)
   Span t(f, PK_T_ASSOC);
   if (plan.kind == ScanKind::Brute) {
-    launch_assoc_brute(f->stream, f->d, al.blobs, al.dir, B, f->ids_dev, f->model, al.rng, f->qt.q00);
+    launch_assoc_brute(f->stream, f->d, scan, f->ids_dev, f->model, f->qt.q00);
     return PK_OK;
   }
   if (f->model == PK_MODEL_BEARING) {
-    launch_assoc_grid_bearing(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, f->ids_dev, finalize, al.rng_cell, f->qt.q00);
+    launch_assoc_grid_bearing(f->stream, f->d, scan, f->ids_dev, finalize, f->qt.q00);
     return PK_OK;
   }
   FastHandoff fh{};
@@ -560,13 +565,18 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
     if (plan.cand_slots) {  // (a list that overflows leaves the scan to the grid walk)
       if ((rc = dev_lazy(f, &f->cand_dev, ((size_t)f->d.lay.Lp + kCandSpare) * 3))) return rc;
       launch_summary_partials(f->stream, f->d, f->partial, f->out4);  // the reference pose: the particles' mean
-      launch_candidates(f->stream, f->d, B, al.exact, 0, f->cand_dev, ctl_cand_over(f), nullptr, nullptr, nullptr, plan.cand_slots, f->out4);
+      CandidatesLaunch cl{};
+      cl.rec = f->cand_dev;
+      cl.over = ctl_cand_over(f);
+      cl.slots = plan.cand_slots;
+      cl.pose_sums4 = f->out4;
+      launch_candidates(f->stream, f->d, scan, cl);
       cand.rec = f->cand_dev;
       cand.over = ctl_cand_over(f);
       cand.slots = plan.cand_slots;
     }
   }
-  launch_assoc_grid(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, f->ids_dev, finalize, fh, cand);
+  launch_assoc_grid(f->stream, f->d, scan, f->ids_dev, finalize, fh, cand);
   return PK_OK;
 }
 
@@ -604,10 +614,13 @@ static int dense_observe(pk_filter* f, const double* blobs, int32_t B, const int
   ex.gmax_key = ctl_gmax_key(f);
   {
     Span t(f, update ? PK_T_OBSERVE : PK_T_ASSOC);
-    launch_observe_dense(f->stream, f->d, reinterpret_cast<const double*>(f->scan_dev + o_blobs),
-                         reinterpret_cast<const double*>(f->scan_dev + o_dir), B,
-                         ids ? reinterpret_cast<const int32_t*>(f->scan_dev + o_ids) : nullptr,
-                         (ids_out && !ids) ? f->ids_dev : nullptr, f->qt16, update, ex);
+    ScanTables scan;
+    scan.B = B;
+    scan.blobs = reinterpret_cast<const double*>(f->scan_dev + o_blobs);
+    scan.dir = reinterpret_cast<const double*>(f->scan_dev + o_dir);
+    const int32_t* ids_in = ids ? reinterpret_cast<const int32_t*>(f->scan_dev + o_ids) : nullptr;
+    int32_t* ids_to = (ids_out && !ids) ? f->ids_dev : nullptr;
+    launch_observe_dense(f->stream, f->d, scan, ids_in, ids_to, f->qt16, update, ex);
   }
   PK_LAUNCH_CHECK("pk_observe (dense)");
   if (update) {
@@ -660,41 +673,73 @@ static int ensure_list_buffers(pk_filter* f, const ScanPlan& plan, int B) {
 }
 // ref: the particle whose MAP the candidate lists are made from -- particle 0, or in a split step the first particle of the range
 // that has been filled already (the slots at either end still hold the old generation then)
-static int onepass_prepare(pk_filter* f, const AssocLaunch& al, int B, CandTable* cand, int64_t ref = 0) {
+static int onepass_prepare(pk_filter* f, const AssocLaunch& al, PubTables* pub, int64_t ref = 0) {
   int rc;
   const ScanPlan& plan = al.plan;
+  *pub = PubTables();
   f->pub_ecap = plan.ecap;
   if (!plan.cand_slots) return PK_OK;
-  if ((rc = ensure_list_buffers(f, plan, B))) return rc;
+  if ((rc = ensure_list_buffers(f, plan, al.scan.B))) return rc;
   Span t(f, PK_T_ASSOC);
+  CandidatesLaunch cl{};
+  cl.rec = f->cand_dev;
+  cl.over = ctl_cand_over(f);
+  cl.slots = plan.cand_slots;
+  cl.ref_particle = ref;
   // the reference pose: the particles' mean -- from the sums the motion launch left, or (poses touched since) two launches
-  const double* part = f->pose_part_ok ? f->pose_part : nullptr;
-  if (!part) launch_summary_partials(f->stream, f->d, f->partial, f->out4);
-  cand->rec = f->cand_dev;
-  cand->over = ctl_cand_over(f);
-  cand->slots = plan.cand_slots;
+  cl.pose_sums4 = f->out4;
+  if (f->pose_part_ok)
+    cl.pose_part = f->pose_part;
+  else
+    launch_summary_partials(f->stream, f->d, f->partial, f->out4);
+  CandTable& cand = pub->cand;
+  cand.rec = f->cand_dev;
+  cand.over = ctl_cand_over(f);
+  cand.slots = plan.cand_slots;
   if (!plan.publish) {
-    launch_candidates(f->stream, f->d, B, al.exact, ref, f->cand_dev, ctl_cand_over(f), nullptr, nullptr, nullptr, plan.cand_slots, f->out4, nullptr, nullptr, part);
+    launch_candidates(f->stream, f->d, al.scan, cl);
     return PK_OK;
   }
-  // candidate lists both ways, and the publish table's layout; the two-pass kernels also get the blobs' float records, the
-  // primary-blob table and the choice between their two instances
-  const bool big = plan.kind == ScanKind::PubBig;
-  uint4* far = plan.far ? f->far_dev : nullptr;
-  launch_candidates(f->stream, f->d, B, al.exact, ref, f->cand_dev, ctl_cand_over(f), f->bcnt_dev, f->brec_dev, ctl_n_stray(f), plan.cand_slots,
-                    f->out4, f->npass_dev, far, part, plan.colour_table ? ct_view(f) : ColourTable(), big ? nullptr : &f->ct_qt);
-  launch_cand_entries(f->stream, f->d, B, f->cand_dev, big ? f->erec_dev2 : f->erec_dev, f->bcnt_dev, f->brec_dev, f->binfo_dev, f->glist_dev,
-                      ctl_cand_over(f), ctl_skip_pub(f), ctl_skip_cand(f), plan.ecap, plan.cand_slots, big ? al.exact : nullptr,
-                      big ? f->gate4_dev : nullptr, f->npass_dev, plan.far, ctl_pub_stats(f), big ? ctl_skip_duo(f) : nullptr,
-                      big ? ctl_skip_big(f) : nullptr, plan.duo, big ? f->prim_dev : nullptr, plan.flag_fold ? f->fh.pflag : nullptr,
-                      plan.flag_fold ? ctl_n_flagged(f) : nullptr);
-  cand->far = far;
-  if (!big) cand->skip_cand = ctl_skip_cand(f);
+  // candidate lists both ways, and the publish table's layout
+  const bool big = plan.kind == ScanKind::PubBig;  // the two-pass kernels: sixteen-entry lists
+  pub->erec = big ? f->erec_dev2 : f->erec_dev;
+  pub->glist = f->glist_dev;
+  pub->bcnt = f->bcnt_dev;
+  pub->brec = f->brec_dev;
+  pub->binfo = f->binfo_dev;
+  pub->npass = f->npass_dev;
+  pub->stats = ctl_pub_stats(f);
+  pub->skip_pub = ctl_skip_pub(f);
+  pub->skip_cand = ctl_skip_cand(f);
+  pub->ecap = plan.ecap;
+  if (big) {  // ... which also get the blobs' float records, the primary-blob table and the choice between their two instances
+    pub->gate4 = f->gate4_dev;
+    pub->prim = f->prim_dev;
+    pub->skip_duo = ctl_skip_duo(f);
+    pub->skip_big = ctl_skip_big(f);
+  }
+  pub->duo = plan.duo;
+  cl.bcnt = pub->bcnt;
+  cl.brec = pub->brec;
+  cl.npass = pub->npass;
+  if (plan.far) cl.far = f->far_dev;
+  if (plan.colour_table) cl.ct = ct_view(f);
+  if (!big) cl.qt = &f->ct_qt;
+  launch_candidates(f->stream, f->d, al.scan, cl);
+  CandEntriesLaunch ce;
+  ce.pub = *pub;
+  ce.pruned = plan.far;
+  if (plan.flag_fold) {
+    ce.flag_all = f->fh.pflag;
+    ce.n_flagged = ctl_n_flagged(f);
+  }
+  launch_cand_entries(f->stream, f->d, al.scan, ce);
+  cand.far = cl.far;
+  if (!big) cand.skip_cand = ctl_skip_cand(f);
   return PK_OK;
 }
 // 2. the one-pass kernel on the particles [p0, p1) (k_step_fused: the whole range only)
-static int onepass_launch(pk_filter* f, const AssocLaunch& al, int B, const ObserveExtras& ex, const CandTable& cand, int64_t p0,
-                          int64_t p1, int reserve_cus = 0) {
+static int onepass_launch(pk_filter* f, const AssocLaunch& al, const ObserveExtras& ex, const PubTables& pub, const ParticleRange& range) {
   const ScanPlan& plan = al.plan;
   FastHandoff fh = f->fh;
   fh.n_flagged = ctl_n_flagged(f);
@@ -713,30 +758,26 @@ static int onepass_launch(pk_filter* f, const AssocLaunch& al, int B, const Obse
     case ScanKind::PubBig:
       // the scan goes to ONE of the two instances (k_cand_entries decided which: the two-workgroups-per-CU instance when its share of
       // LDS holds the scan's publish table); both are launched, one returns at once
-      if (plan.duo.tbytes > 0)
-        launch_step_pub_duo(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev2, f->glist_dev, ctl_skip_duo(f), ctl_pub_stats(f),
-                            plan.duo, f->gate4_dev, f->prim_dev, p0, p1, reserve_cus);
-      launch_step_pub_big(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev2, f->glist_dev, ctl_skip_big(f), plan.ecap, f->prim_dev,
-                          ctl_pub_stats(f), f->gate4_dev, p0, p1, reserve_cus);
+      if (plan.duo.tbytes > 0) launch_step_pub_duo(f->stream, f->d, al.scan, fh, f->qt, e1, pub, range);
+      launch_step_pub_big(f->stream, f->d, al.scan, fh, f->qt, e1, pub, range);
       break;
     case ScanKind::PubSmall:
     case ScanKind::Pub:
     case ScanKind::PubRegs:
-      launch_step_pub(f->stream, f->d, B, al.exact, al.order, fh, f->qt, e1, cand, f->erec_dev, f->glist_dev, ctl_skip_pub(f), plan.ecap, p0, p1,
-                      reserve_cus);
+      launch_step_pub(f->stream, f->d, al.scan, fh, f->qt, e1, pub, range);
       if (plan.kind != ScanKind::PubRegs) break;
       [[fallthrough]];  // (the stand-by: returns at once unless k_step_pub stood back)
     case ScanKind::Regs:
-      launch_step_regs(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, al.order, fh, f->qt, e1, f->opt.regs_warm, cand, p0, p1, reserve_cus);
+      launch_step_regs(f->stream, f->d, al.scan, fh, f->qt, e1, f->opt.regs_warm, pub.cand, range);
       break;
     case ScanKind::Fused:
-      launch_step_fused(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, al.order, fh, f->qt, e1);
+      launch_step_fused(f->stream, f->d, al.scan, fh, f->qt, e1);
       break;
     default:
       break;
   }
   // a scan the kernel stood back from (a list overflowed, the table did not fit): every particle to the fall-back kernels
-  if (plan.flag_range) launch_flag_range_if(f->stream, ctl_skip_pub(f), fh.pflag, fh.n_flagged, p0, p1);
+  if (plan.flag_range) launch_flag_range_if(f->stream, ctl_skip_pub(f), fh.pflag, fh.n_flagged, range.p0, range.end(f->d.P));
   return PK_OK;
 }
 // k_observe_sweep's per-workgroup result lists
@@ -745,7 +786,7 @@ static int ensure_sweep_results(pk_filter* f, const SweepPlan& plan) {
   return dev_reserve(f, &f->sweep_results, &f->sweep_cap, need, need);
 }
 // 3. what the one-pass kernel flagged, over all particles: second chance, then the general kernels (which swap the map buffers)
-static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const ObserveExtras& ex, const CandTable& cand) {
+static int onepass_finish(pk_filter* f, const AssocLaunch& al, const ObserveExtras& ex, const CandTable& cand) {
   int rc;
   FastHandoff fh = f->fh;
   fh.n_flagged = ctl_n_flagged(f);
@@ -756,7 +797,7 @@ static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const Obse
     // hand-off instance with eight slots and k_observe_sweep, both on the flagged particles only (timed with the other
     // fallbacks in the association slot: the observe slot holds the one-pass kernel alone, one span per launch)
     Span t(f, PK_T_ASSOC);
-    const SweepPlan plan = observe_sweep_plan(f->d, B);
+    const SweepPlan plan = observe_sweep_plan(f->d, al.scan.B);
     if ((rc = ensure_sweep_results(f, plan))) return rc;
     FastHandoff fr = f->fh;
     fr.slots = kSweepSlots;
@@ -765,12 +806,13 @@ static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const Obse
     fr.row_next = ctl_retry_rows(f);
     fr.row_cap = retry_rows(f);
     // (pruned candidate lists are the publish / subscribe kernels' alone: the hand-off instance walks the colour grid then)
-    launch_assoc_grid(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, f->ids_dev, false, fr, cand.far ? CandTable{} : cand);
+    const CandTable unpruned = cand.far ? CandTable() : cand;
+    launch_assoc_grid(f->stream, f->d, al.scan, f->ids_dev, false, fr, unpruned);
     ObserveExtras e3 = ex;
     e3.flip = false;
     e3.sweep_only_value = 2;
     e3.n_flagged = ctl_n_flagged(f);
-    launch_observe_sweep(f->stream, f->d, B, al.exact, al.order, fr, f->qt, e3, plan, f->sweep_results);
+    launch_observe_sweep(f->stream, f->d, al.scan, fr, f->qt, e3, plan, f->sweep_results);
     (void)host_word(f, &f->retry_seen);  // (without it the rows do not grow: no error)
     if (f->retry_seen) (void)hipMemcpyAsync(f->retry_seen, ctl_retry_rows(f), sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
     (void)hipGetLastError();
@@ -778,11 +820,11 @@ static int onepass_finish(pk_filter* f, const AssocLaunch& al, int B, const Obse
   // the particles still flagged (a landmark passing more blobs than any slot count): general kernels, both timed in the
   // association slot
   Span t(f, PK_T_ASSOC);
-  launch_assoc_grid(f->stream, f->d, B, al.grid, al.n9, al.tables, al.exact, f->ids_dev, false, fh);
+  launch_assoc_grid(f->stream, f->d, al.scan, f->ids_dev, false, fh);
   ObserveExtras e2 = ex;
   e2.only_flagged = f->fh.pflag;
   e2.n_flagged = ctl_n_flagged(f);
-  launch_observe(f->stream, f->d, al.blobs, al.dir, B, nullptr, nullptr, 0, f->ids_dev, f->qt, e2);
+  launch_observe(f->stream, f->d, al.scan, f->ids_dev, f->qt, e2);
   return PK_OK;
 }
 
@@ -841,6 +883,20 @@ static int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const
   *out = k;
   return PK_OK;
 }
+// ... and the device views of that block: a scan with supplied ids has B and the blobs alone
+static ScanTables known_scan_tables(const pk_filter* f, const KnownScan& ks, int B) {
+  ScanTables scan;
+  scan.B = B;
+  scan.blobs = reinterpret_cast<const double*>(f->scan_dev + ks.o_blobs);
+  return scan;
+}
+static KnownChains known_chains(const pk_filter* f, const KnownScan& ks) {
+  KnownChains c;
+  c.first = reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_first);
+  c.next = reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_next);
+  c.n_unmatched = ks.n_unmatched;
+  return c;
+}
 
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out,
                         bool reset) {
@@ -890,9 +946,7 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
     ex.gmax_key = ctl_gmax_key(f);
     {
       Span t(f, PK_T_OBSERVE);
-      launch_observe(f->stream, f->d, reinterpret_cast<const double*>(f->scan_dev + ks.o_blobs), nullptr, B,
-                     reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_first),
-                     reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_next), ks.n_unmatched, nullptr, f->qt, ex);
+      launch_observe(f->stream, f->d, known_scan_tables(f, ks, B), known_chains(f, ks), f->qt, ex);
     }
     PK_LAUNCH_CHECK("pk_observe");
     observe_done(f);
@@ -905,7 +959,7 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   AssocLaunch al;
   // (ids wanted: the association kernel + k_observe; growing maps: a publish / subscribe kernel, or that)
   if ((rc = enqueue_association(f, blobs, B, false, ids_out == nullptr, &al, grow, true, &rs))) return rc;
-  ex.rng = al.rng;
+  ex.rng = al.scan.rng;
   const ScanPlan& plan = al.plan;
   // the colour table's mode: this scan takes the table-mode kernel, or the mode ends here (the slots get their colour rows first)
   if (plan.colour_table ? (rc = ct_engage(f)) : (rc = ct_end(f))) return rc;
@@ -921,21 +975,21 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   }
   ex.gmax_key = ctl_gmax_key(f);
   if (plan.onepass()) {
-    CandTable cand;
-    if ((rc = onepass_prepare(f, al, B, &cand))) return rc;
-    if ((rc = onepass_launch(f, al, B, ex, cand, 0, f->d.P))) return rc;
+    PubTables pub;
+    if ((rc = onepass_prepare(f, al, &pub))) return rc;
+    if ((rc = onepass_launch(f, al, ex, pub, ParticleRange()))) return rc;
     if (plan.colour_table) {
       // what the kernel handed on (or the whole scan, where it stood back) goes to kernels that read whole slots: the SOURCE slots of
       // those particles get their colour rows from the table first -- a launch that returns in its first wave on the usual scan
       Span t(f, PK_T_ASSOC);
-      launch_colour_rows(f->stream, f->d, ct_view(f), f->ct_qt, f->fh.pflag, ctl_n_flagged(f));
+      launch_colour_rows(f->stream, f->d, ct_view(f), f->ct_qt, ParticleRange(), f->fh.pflag, ctl_n_flagged(f));
       (void)hipMemcpyAsync(f->ct_seen, f->ct_max_dev, sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
       (void)hipGetLastError();
       f->colour_rows_valid = false;
       f->ct_engaged = true;
       f->ct_scans += 1;
     }
-    if ((rc = onepass_finish(f, al, B, ex, cand))) return rc;
+    if ((rc = onepass_finish(f, al, ex, pub.cand))) return rc;
   } else {
     Span t(f, PK_T_OBSERVE);
     if (plan.lists) {  // the hand-off was written
@@ -944,20 +998,20 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
       if (plan.kind == ScanKind::HandoffSweep) {
         const SweepPlan sweep = observe_sweep_plan(f->d, B);
         if ((rc = ensure_sweep_results(f, sweep))) return rc;
-        launch_observe_sweep(f->stream, f->d, B, al.exact, al.order, f->fh, f->qt, e1, sweep, f->sweep_results);
+        launch_observe_sweep(f->stream, f->d, al.scan, f->fh, f->qt, e1, sweep, f->sweep_results);
       } else {
-        launch_observe_fast(f->stream, f->d, B, al.exact, al.order, f->fh, f->qt, e1);
+        launch_observe_fast(f->stream, f->d, al.scan, f->fh, f->qt, e1);
       }
       ex.only_flagged = f->fh.pflag;
       ex.n_flagged = ctl_n_flagged(f);
     }
-    launch_observe(f->stream, f->d, al.blobs, al.dir, B, nullptr, nullptr, 0, f->ids_dev, f->qt, ex);
+    launch_observe(f->stream, f->d, al.scan, f->ids_dev, f->qt, ex);
   }
   PK_LAUNCH_CHECK("pk_observe");
   observe_done(f);
   if (grow) {  // :92-95 for every particle, on the ids the association kernel left in HBM (every particle's slot is its own now)
     Span t(f, PK_T_OBSERVE);
-    launch_new_landmarks(f->stream, f->d, f->grow, f->grow_init, f->qt.q00, f->ids_dev, al.blobs, B, f->grow_bits ? f->unm_dev : nullptr,
+    launch_new_landmarks(f->stream, f->d, f->grow, f->grow_init, f->qt.q00, f->ids_dev, al.scan.blobs, B, f->grow_bits ? f->unm_dev : nullptr,
                          f->unm_words, f->grow_bits ? f->fh.pflag : nullptr);
     if (f->retire.on()) {  // pk_grow_retire: stale readings and unconfirmed features go, behind this scan's bookkeeping
       f->retire.t += 1u;
@@ -985,9 +1039,9 @@ int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* i
     KnownScan ks;
     if ((rc = upload_known_scan(f, blobs, B, ids, true, &ks))) return rc;
     f->gmax_fused = false;
-    out->blobs = reinterpret_cast<const double*>(f->scan_dev + ks.o_blobs);
-    out->first = reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_first);
-    out->next = reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_next);
+    out->scan = known_scan_tables(f, ks, B);
+    out->known = known_chains(f, ks);
+    out->known.n_unmatched = 0;  // (k_observe_proposed takes the weight from k_propose, unmatched blobs and all)
     out->ids = reinterpret_cast<int32_t*>(f->scan_dev + ks.o_ids);
     return PK_OK;
   }
@@ -995,8 +1049,7 @@ int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* i
   if ((rc = enqueue_association(f, blobs, B, false, false, &al, false, true))) return rc;
   if (al.plan.onepass()) return fail(PK_ERR_UNSUPPORTED, "pk_propose: the scan did not take the general association");
   if ((rc = ct_end(f))) return rc;
-  out->blobs = al.blobs;
-  out->dir = al.dir;
+  out->scan = al.scan;
   out->ids = f->ids_dev;
   return PK_OK;
 }
@@ -1068,13 +1121,11 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
     if (!pk_staged_takes_regs(f))
       return fail(PK_ERR_STATE, "pk_observe_staged_range: needs a staged scan that takes the register route (pk_staged_takes_regs)");
     const double* blobs = reinterpret_cast<const double*>(f->staged.st + kCtlBytes);
-    sp.B = f->staged.B;
     sp.reset = fresh != 0;
     sp.al = AssocLaunch();
-    if ((rc = enqueue_association(f, blobs, sp.B, false, true, &sp.al))) return rc;
+    if ((rc = enqueue_association(f, blobs, f->staged.B, false, true, &sp.al))) return rc;
     if (!sp.al.plan.ranged()) return fail(PK_ERR_STATE, "pk_observe_staged_range: the scan did not take the register route");
-    sp.cand = CandTable();
-    if ((rc = onepass_prepare(f, sp.al, sp.B, &sp.cand, p1 > p0 ? p0 : 0))) return rc;
+    if ((rc = onepass_prepare(f, sp.al, &sp.pub, p1 > p0 ? p0 : 0))) return rc;
     sp.active = true;
   } else if (!sp.active) {
     return fail(PK_ERR_STATE, "pk_observe_staged_range: no split observe in progress (first = 1)");
@@ -1083,13 +1134,17 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
   ex.reset = sp.reset;
   ex.gmax_key = ctl_gmax_key(f);
   // the first part of a split step runs while the exchange is in flight: it leaves some CUs to the collective's kernels
-  if (p1 > p0 && (rc = onepass_launch(f, sp.al, sp.B, ex, sp.cand, p0, p1, (first && !last) ? f->opt.split_reserve_cus : 0))) {
+  ParticleRange range;
+  range.p0 = p0;
+  range.p1 = p1;
+  if (first && !last) range.reserve_cus = f->opt.split_reserve_cus;
+  if (p1 > p0 && (rc = onepass_launch(f, sp.al, ex, sp.pub, range))) {
     sp.active = false;  // a failed piece ends the split observe: the filter is not left waiting for a "last" that cannot come
     return rc;
   }
   if (last) {
     sp.active = false;
-    if ((rc = onepass_finish(f, sp.al, sp.B, ex, sp.cand))) return rc;
+    if ((rc = onepass_finish(f, sp.al, ex, sp.pub.cand))) return rc;
     PK_LAUNCH_CHECK("pk_observe_staged_range");
     observe_done(f);
   }

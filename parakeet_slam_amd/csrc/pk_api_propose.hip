@@ -105,8 +105,8 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
   if (!rc) {
     Span t(f, PK_T_PROPOSE);
     ProposeLaunch pl;
-    pl.blobs_dev = sc.blobs;
-    pl.blobdir_dev = sc.dir;
+    pl.blobs_dev = sc.scan.blobs;
+    pl.blobdir_dev = sc.scan.dir;
     pl.B = B;
     pl.ids_dev = sc.ids;
     pl.ids_shared = ids != nullptr;
@@ -138,9 +138,9 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
     ex.gmax_key = ctl_gmax_key(f);
     ex.dlogw = q.dlogw;
     if (ids)
-      launch_observe(f->stream, f->d, sc.blobs, nullptr, B, sc.first, sc.next, 0, nullptr, f->qt, ex);
+      launch_observe(f->stream, f->d, sc.scan, sc.known, f->qt, ex);
     else
-      launch_observe(f->stream, f->d, sc.blobs, sc.dir, B, nullptr, nullptr, 0, sc.ids, f->qt, ex);
+      launch_observe(f->stream, f->d, sc.scan, sc.ids, f->qt, ex);
   }
   PK_LAUNCH_CHECK(who);
   proposal_observed(f, ids != nullptr);

@@ -113,18 +113,10 @@ struct ScanPlan {
   bool ranged() const { return kind >= ScanKind::Regs; }  // runs on particle ranges (pk_observe_staged_range)
 };
 
+// One uploaded maximum-likelihood scan and the kernels it gets (enqueue_association fills both)
 struct AssocLaunch {
+  ScanTables scan;
   ScanPlan plan;
-  BlobGrid grid{};
-  int n9 = 0;
-  const unsigned char* tables = nullptr;
-  const double* blobs = nullptr;
-  const double* dir = nullptr;
-  const double* exact = nullptr;
-  const unsigned short* order = nullptr;
-  // a scan with at least one ranged blob (pk_scan_ranges): its range rows [B][2] (range, variance) in scan order and in cell order
-  const double* rng = nullptr;
-  const double* rng_cell = nullptr;
 };
 
 // The ranges a consuming call took from the filter (ranges_take): rows [B][2] (range, variance; NaN range = none).  armed: ranges
@@ -291,8 +283,7 @@ struct pk_filter {
   struct Split {
     bool active = false;
     AssocLaunch al;
-    CandTable cand;
-    int B = 0;
+    PubTables pub;
     bool reset = false;
   } split;
   // The colour table (pk_colour.hpp): while every map descends from one pk_upload_map the colour block of a landmark is
@@ -553,13 +544,11 @@ int ct_maps_untouched(pk_filter* f, bool* untouched);
 void blob_directions(const double* blobs, int B, double* dir);
 int stage_ml_scan(pk_filter* f, const double* blobs, int B, const RangeScan* rs = nullptr);
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out, bool reset);
-// a proposal step's scan on the device (pk_api_propose.hip): where its parts lie.  first / next: supplied ids' chains (the ids
-// are final); dir: the rays that settle tentative ids; ids: one row of B (supplied) or ids_dev's [P][B]
+// a proposal step's scan on the device (pk_api_propose.hip): where its parts lie.  known: supplied ids' chains (the ids are
+// final); scan.dir: the rays that settle tentative ids; ids: one row of B (supplied) or ids_dev's [P][B]
 struct ProposalScan {
-  const double* blobs = nullptr;
-  const double* dir = nullptr;
-  const int32_t* first = nullptr;
-  const int32_t* next = nullptr;
+  ScanTables scan;
+  KnownChains known;
   int32_t* ids = nullptr;
 };
 int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out);

@@ -4,6 +4,7 @@
 // section 4.  No MFMA: the algebra is 2x2 / 3x3 and register resident (pk_math.hpp).
 #include "pk_colour.hpp"
 #include "pk_device.hpp"
+#include "pk_launch.hpp"
 #include "pk_pub_math.hpp"
 #include "pk_range_math.hpp"
 
@@ -124,33 +125,20 @@ __global__ void __launch_bounds__(256) k_assoc_brute(AssocArgs a) { assoc_brute_
 __global__ void __launch_bounds__(256) k_assoc_brute_bearing(AssocArgs a) { assoc_brute_body<kModelBearing>(a); }
 __global__ void __launch_bounds__(256) k_assoc_brute_range(AssocArgs a) { assoc_brute_body<kModelBearing, true>(a); }
 
-void launch_assoc_brute(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev, int B,
-                        int32_t* ids_dev, int model, const double* rng_dev, double q00) {
-  if (d.P == 0 || B == 0) return;
-  AssocArgs a;
-  a.ss = slot_source(d);
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.blobs = blobs_dev;
-  a.blobdir = blobdir_dev;
+void launch_assoc_brute(hipStream_t s, DeviceState& d, const ScanTables& scan, int32_t* ids_dev, int model, double q00) {
+  if (d.P == 0 || scan.B == 0) return;
+  AssocArgs a{};
+  fill_particles(a, d);
+  a.blobs = scan.blobs;
+  a.blobdir = scan.dir;
   a.ids = ids_dev;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  a.rng = rng_dev;
+  a.B = scan.B;
+  a.rng = scan.rng;
   a.q00 = q00;
-  const size_t lds = assoc_brute_lds_bytes(B);  // <= kMaxDynLds: checked by the caller
+  const size_t lds = assoc_brute_lds_bytes(scan.B);  // <= kMaxDynLds: checked by the caller
   static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    for (const void* fn : {reinterpret_cast<const void*>(k_assoc_brute), reinterpret_cast<const void*>(k_assoc_brute_bearing),
-                           reinterpret_cast<const void*>(k_assoc_brute_range)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess)
-        (void)hipGetLastError();
-  }
-  if (model == kModelBearing && rng_dev)
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_assoc_brute, k_assoc_brute_bearing, k_assoc_brute_range);
+  if (model == kModelBearing && scan.rng)
     hipLaunchKernelGGL(k_assoc_brute_range, dim3((unsigned)d.P), dim3(256), lds, s, a);
   else if (model == kModelBearing)
     hipLaunchKernelGGL(k_assoc_brute_bearing, dim3((unsigned)d.P), dim3(256), lds, s, a);
@@ -682,11 +670,7 @@ size_t assoc_grid_lds_bytes(int ncell, int B, int n9) {
 template <auto KERNEL, int THREADS>
 static void launch_assoc_grid_k(hipStream_t s, const AssocGridArgs& ga, size_t lds, int64_t P) {
   static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess)
-      (void)hipGetLastError();  // leave no sticky error behind for other users of the runtime
-  }
+  allow_dynamic_lds(attr_set, kMaxDynLds, KERNEL);
   // persistent grid = the workgroups that are resident at once (registers, LDS and the wave limit all
   // count: a workgroup that has to wait for a slot would run its particles after the others finished)
   static size_t asked_lds = ~(size_t)0;
@@ -715,37 +699,32 @@ static void launch_assoc_grid_t(hipStream_t s, const AssocGridArgs& ga, size_t l
   launch_assoc_grid_k<k_assoc_grid<THREADS, DUP, GENERAL, SLOTS>, THREADS>(s, ga, lds, P);
 }
 
-void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
-                       const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev, bool finalize,
-                       const FastHandoff& fh, const CandTable& cand) {
-  if (d.P == 0 || B == 0) return;
-  AssocGridArgs ga;
-  AssocArgs& a = ga.a;
-  a.ss = slot_source(d);
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.blobs = nullptr;
-  a.blobdir = nullptr;
-  a.rng = nullptr;
-  a.q00 = 0.0;
-  a.ids = ids_dev;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  ga.g = grid;
-  ga.tables = tables_dev;
-  ga.exact = exact_dev;
+// what both launchers of the grid kernels hand them: the particles, the scan's tables, where the ids go
+static AssocGridArgs assoc_grid_args(const DeviceState& d, const ScanTables& scan, int32_t* ids_dev, bool finalize) {
+  AssocGridArgs ga{};  // (a.blobs, a.blobdir: unused here; no hand-off, no candidate lists, no flags)
+  fill_particles(ga.a, d);
+  ga.a.ids = ids_dev;
+  ga.a.B = scan.B;
+  ga.g = scan.grid;
+  ga.tables = scan.tables;
+  ga.exact = scan.exact;
   ga.P = d.P;
   ga.finalize = finalize ? 1 : 0;
-  ga.n9 = n9;
+  ga.n9 = scan.n9;
+  ga.cand_slots = kCandSlots;
+  return ga;
+}
+
+void launch_assoc_grid(hipStream_t s, DeviceState& d, const ScanTables& scan, int32_t* ids_dev, bool finalize, const FastHandoff& fh,
+                       const CandTable& cand) {
+  if (d.P == 0 || scan.B == 0) return;
+  const int B = scan.B, n9 = scan.n9;
+  const BlobGrid& grid = scan.grid;
+  AssocGridArgs ga = assoc_grid_args(d, scan, ids_dev, finalize);
   ga.lmpass = fh.lmpass;
   ga.bcount = fh.bcount;
   ga.pflag = fh.pflag;
   ga.n_flagged = fh.n_flagged;
-  ga.only_flagged = nullptr;
   ga.cand_rec = cand.rec;
   ga.cand_over = cand.rec ? cand.over : nullptr;
   ga.cand_slots = cand.slots;
@@ -795,40 +774,16 @@ void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& gri
   }
 }
 
-void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
-                       const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev, bool finalize,
-                       const FastHandoff& fh) {
-  launch_assoc_grid(s, d, B, grid, n9, tables_dev, exact_dev, ids_dev, finalize, fh, CandTable{});
-}
-
 // The bearing model: the general instance over every particle -- no hand-off, no candidate lists, no flags.
-void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9, const unsigned char* tables_dev,
-                               const double* exact_dev, int32_t* ids_dev, bool finalize, const double* rng_cell_dev, double q00) {
-  if (d.P == 0 || B == 0) return;
-  AssocGridArgs ga{};
-  AssocArgs& a = ga.a;
-  a.ss = slot_source(d);
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.ids = ids_dev;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  ga.g = grid;
-  ga.tables = tables_dev;
-  ga.exact = exact_dev;
-  ga.P = d.P;
-  ga.finalize = finalize ? 1 : 0;
-  ga.n9 = n9;
-  ga.cand_slots = kCandSlots;
-  a.rng = rng_cell_dev;
-  a.q00 = q00;
-  const size_t lds = assoc_grid_lds_bytes(grid.ncell, B, n9);
+void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, const ScanTables& scan, int32_t* ids_dev, bool finalize, double q00) {
+  if (d.P == 0 || scan.B == 0) return;
+  const int n9 = scan.n9;
+  AssocGridArgs ga = assoc_grid_args(d, scan, ids_dev, finalize);
+  ga.a.rng = scan.rng_cell;
+  ga.a.q00 = q00;
+  const size_t lds = assoc_grid_lds_bytes(scan.grid.ncell, scan.B, n9);
   const bool big = lds > 40 * 1024;  // as launch_assoc_grid sizes its general instance
-  if (rng_cell_dev) {  // a scan with ranged blobs: the range instances, sized the same way
+  if (scan.rng_cell) {  // a scan with ranged blobs: the range instances, sized the same way
     if (n9 > 0) {
       if (big)
         launch_assoc_grid_k<k_assoc_grid_range<512, true>, 512>(s, ga, lds, d.P);
@@ -1046,41 +1001,32 @@ __global__ void __launch_bounds__(kCandThreads) k_candidates(CandArgs a) {
   }
 }
 
-void launch_candidates(hipStream_t s, DeviceState& d, int B, const double* exact_dev, int64_t ref_particle, uint4* rec_dev,
-                       unsigned* over_dev, unsigned* bcnt_dev, uint4* brec_dev, unsigned* stray_dev, int slots,
-                       const double* pose_sums4_dev, unsigned char* npass_dev, uint4* far_dev, const double* pose_part_dev,
-                       const ColourTable& ct, const NoiseD* qt) {
+void launch_candidates(hipStream_t s, DeviceState& d, const ScanTables& scan, const CandidatesLaunch& c) {
   if (d.P == 0 || d.lay.Lp == 0) return;
-  // (inverse lists as wide as the lists themselves: brec_dev holds B x slots u16.  bcnt_dev is all 0 and brec_dev all 0xFF when
+  assert(c.rec && c.over && (c.pose_sums4 || c.pose_part));
+  // (inverse lists as wide as the lists themselves: c.brec holds B x slots u16.  c.bcnt is all 0 and c.brec all 0xFF when
   // this is called: cleared at their allocation, and again by k_cand_entries behind its last read of them -- two memset
-  // launches per scan less.  stray_dev: unused since round 3, kept in the signature)
-  (void)stray_dev;
-  CandArgs a;
+  // launches per scan less)
+  const int slots = c.slots;
+  CandArgs a{};
+  fill_particles(a, d);
   a.inv_slots = slots;
-  a.bcnt = brec_dev ? bcnt_dev : nullptr;
-  a.blist = reinterpret_cast<unsigned short*>(brec_dev);
-  a.ss = slot_source(d);
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.exact = exact_dev;
-  a.rec = rec_dev;
-  a.over = over_dev;
-  a.ref = ref_particle;
-  a.pose4 = pose_sums4_dev;
-  a.part = pose_part_dev;
+  a.bcnt = c.brec ? c.bcnt : nullptr;
+  a.blist = reinterpret_cast<unsigned short*>(c.brec);
+  a.exact = scan.exact;
+  a.rec = c.rec;
+  a.over = c.over;
+  a.ref = c.ref_particle;
+  a.pose4 = c.pose_sums4;
+  a.part = c.pose_part;
   a.n_part = motion_pose_blocks(d.P);
-  a.npass = npass_dev;
-  a.far = far_dev;
-  a.count_off = d.lay.count_off;
-  a.ctab = qt ? ct.tab : nullptr;
-  a.ctab_depth = ct.depth;
-  a.qt = qt ? make_noise(qt->q00, qt->rr, qt->rg, qt->rb, qt->gg, qt->gb, qt->bb) : Noise<double>{};
+  a.npass = c.npass;
+  a.far = c.far;
+  a.ctab = c.qt ? c.ct.tab : nullptr;
+  a.ctab_depth = c.ct.depth;
+  a.qt = c.qt ? device_noise(*c.qt) : Noise<double>{};
   a.P = d.P;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
+  a.B = scan.B;
   if (slots > kCandSlots)
     hipLaunchKernelGGL(k_candidates<2 * kCandSlots>, dim3((unsigned)((d.lay.Lp + kCandSpare + 63) / 64)), dim3(kCandThreads), 0, s, a);
   else

@@ -4,6 +4,7 @@
 // listed, the lanes' order of sixteen-landmark groups, the float gate table of k_step_pub_big.  Hand-written gfx950 (CDNA4, wave64).
 // (Round 5: its own file; it used to stand at the head of pk_k_step_pub.hip.)
 #include "pk_device.hpp"
+#include "pk_launch.hpp"
 #include "pk_pub_math.hpp"
 #include "pk_pub_layout.hpp"
 
@@ -449,37 +450,37 @@ __global__ void __launch_bounds__(1024) k_cand_entries(CandEntriesArgs a) {
   }
 }
 
-void launch_cand_entries(hipStream_t s, const DeviceState& d, int B, const uint4* cand_dev, uint4* erec_dev, unsigned* bcnt_dev,
-                         uint4* brec_dev, unsigned* binfo_dev, unsigned* glist_dev, const unsigned* over_dev, unsigned* skip_pub_dev,
-                         unsigned* skip_cand_dev, int ecap, int slots, const double* exact_dev, float4* gate4_dev,
-                         const unsigned char* npass_dev, bool pruned, unsigned* stats_dev, unsigned* skip_duo_dev, unsigned* skip_big_dev,
-                         const DuoLimits& duo, uint4* prim_dev, unsigned char* flag_all_dev, unsigned* n_flagged_dev) {
-  CandEntriesArgs a;
-  a.flag_all = n_flagged_dev ? flag_all_dev : nullptr;
-  a.n_flagged = n_flagged_dev;
+void launch_cand_entries(hipStream_t s, const DeviceState& d, const ScanTables& scan, const CandEntriesLaunch& c) {
+  const PubTables& t = c.pub;
+  assert(t.cand.rec && t.cand.over && t.erec && t.bcnt && t.brec && t.binfo && t.glist && t.skip_pub && t.skip_cand);
+  const int slots = t.cand.slots;
+  const bool two_pass = t.gate4 != nullptr;  // the two-pass kernels' scan: the blobs' float records, and with sixteen-entry lists the primary-blob table
+  CandEntriesArgs a{};
+  a.flag_all = c.n_flagged ? c.flag_all : nullptr;
+  a.n_flagged = c.n_flagged;
   a.flag_P = d.P;
-  a.prim = (exact_dev && slots > kCandSlots) ? prim_dev : nullptr;
-  a.stats = stats_dev;
-  a.skip_duo = skip_duo_dev;
-  a.skip_big = skip_big_dev;
-  a.duo = duo;
-  a.pruned = pruned ? 1 : 0;
-  a.npass = npass_dev;
-  a.exact = exact_dev;
-  a.gate4 = exact_dev ? gate4_dev : nullptr;
-  a.cand = cand_dev;
-  a.erec = reinterpret_cast<unsigned short*>(erec_dev);
-  a.bcnt = bcnt_dev;
-  a.brec = reinterpret_cast<unsigned short*>(brec_dev);
-  a.binfo = binfo_dev;
-  a.glist = glist_dev;
-  a.over = over_dev;
-  a.skip_pub = skip_pub_dev;
-  a.skip_cand = skip_cand_dev;
+  a.prim = (two_pass && slots > kCandSlots) ? t.prim : nullptr;
+  a.stats = t.stats;
+  a.skip_duo = t.skip_duo;
+  a.skip_big = t.skip_big;
+  a.duo = t.duo;
+  a.pruned = c.pruned ? 1 : 0;
+  a.npass = t.npass;
+  a.exact = two_pass ? scan.exact : nullptr;
+  a.gate4 = t.gate4;
+  a.cand = t.cand.rec;
+  a.erec = reinterpret_cast<unsigned short*>(t.erec);
+  a.bcnt = t.bcnt;
+  a.brec = reinterpret_cast<unsigned short*>(t.brec);
+  a.binfo = t.binfo;
+  a.glist = t.glist;
+  a.over = t.cand.over;
+  a.skip_pub = t.skip_pub;
+  a.skip_cand = t.skip_cand;
   a.L = d.lay.L;
   a.Lp = d.lay.Lp;
-  a.B = B;
-  a.ecap = ecap;
+  a.B = scan.B;
+  a.ecap = t.ecap;
   if (slots > kCandSlots)
     hipLaunchKernelGGL(k_cand_entries<2 * kCandSlots>, dim3(1), dim3(1024), 0, s, a);
   else

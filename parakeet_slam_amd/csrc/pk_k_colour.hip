@@ -70,9 +70,9 @@ __global__ void __launch_bounds__(256) k_colour_rows(ColourRowsArgs a) {
   }
 }
 
-void launch_colour_rows(hipStream_t s, DeviceState& d, const ColourTable& ct, const NoiseD& qt, const unsigned char* pflag_dev,
-                        const unsigned* n_flagged_dev, int64_t p0, int64_t p1) {
-  if (p1 < 0) p1 = d.P;
+void launch_colour_rows(hipStream_t s, DeviceState& d, const ColourTable& ct, const NoiseD& qt, const ParticleRange& range,
+                        const unsigned char* pflag_dev, const unsigned* n_flagged_dev) {
+  const int64_t p0 = range.p0, p1 = range.end(d.P);
   if (!ct.tab || d.P == 0 || p0 < 0 || p1 > d.P || p0 >= p1) return;
   ColourRowsArgs a;
   a.map = d.map[d.mcur];

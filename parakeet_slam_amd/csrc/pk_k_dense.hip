@@ -9,6 +9,7 @@
 // workgroup per particle, brute-force maximum-likelihood association in the same kernel.  Correct, not fast:
 // 480 B per particle.landmark and O(B L) gate tests per particle.
 #include "pk_device.hpp"
+#include "pk_launch.hpp"
 
 namespace pk {
 
@@ -276,33 +277,20 @@ __global__ void __launch_bounds__(256) k_observe_dense(DenseArgs a) {
   }
 }
 
-void launch_observe_dense(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev, int B,
-                          const int32_t* ids_in_dev, int32_t* ids_out_dev, const double Qt[16], bool update,
-                          const ObserveExtras& ex) {
+void launch_observe_dense(hipStream_t s, DeviceState& d, const ScanTables& scan, const int32_t* ids_in_dev, int32_t* ids_out_dev,
+                          const double Qt[16], bool update, const ObserveExtras& ex) {
   if (d.P == 0) return;
+  const int B = scan.B;
   static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_observe_dense), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kMaxDynLds) != hipSuccess)
-      (void)hipGetLastError();
-  }
-  DenseArgs a;
-  a.ss = slot_source(d);
-  a.map_dst = update ? d.map[d.mcur ^ 1] : nullptr;
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.logw = d.logw[d.cur];
-  a.blobs = blobs_dev;
-  a.blobdir = blobdir_dev;
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_observe_dense);
+  DenseArgs a{};
+  fill_state(a, d);
+  if (!update) a.map_dst = nullptr;  // association only
+  a.blobs = scan.blobs;
+  a.blobdir = scan.dir;
   a.ids_in = ids_in_dev;
   a.ids_out = ids_out_dev;
-  a.immutable = d.immutable;
   for (int i = 0; i < 16; ++i) a.Qt[i] = Qt[i];
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
   a.B = B;
   a.reset = ex.reset ? 1 : 0;
   a.gmax_key = ex.gmax_key;

@@ -5,6 +5,7 @@
 // Hand-written gfx950 (CDNA4, wave64) kernels of the FastSLAM particle update; see DESIGN.md
 // section 4.  No MFMA: the algebra is 2x2 / 3x3 and register resident (pk_math.hpp).
 #include "pk_device.hpp"
+#include "pk_launch.hpp"
 #include "pk_range_math.hpp"
 
 namespace pk {
@@ -322,37 +323,31 @@ __global__ void __launch_bounds__(THREADS) k_observe_single(ObserveArgs a) {
 
 int g_observe_nv = 0;  // tuning: 0 = default per variant, 1 / 2 = landmarks per lane
 
-void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev, int B,
-                    const int32_t* first_dev, const int32_t* next_dev, int n_unmatched, int32_t* ids_dev,
-                    const NoiseD& qt, const ObserveExtras& ex) {
+// known.first != NULL: supplied ids (ids_dev NULL); else ids_dev's [P][B]
+static void observe_launch(hipStream_t s, DeviceState& d, const ScanTables& scan, const KnownChains& known, int32_t* ids_dev,
+                           const NoiseD& qt, const ObserveExtras& ex) {
   if (d.P == 0) return;
-  ObserveArgs a;
-  a.ss = slot_source(d);
-  a.map_dst = d.map[d.mcur ^ 1];
+  const int B = scan.B;
+  ObserveArgs a{};
+  fill_state(a, d);
   a.slot_bytes = d.lay.slot_bytes;
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.logw = d.logw[d.cur];
-  a.blobs = blobs_dev;
-  a.blobdir = blobdir_dev;
+  a.blobs = scan.blobs;
+  a.blobdir = scan.dir;
   a.rng = ex.rng;
-  a.first = first_dev;
-  a.next = next_dev;
+  a.first = known.first;
+  a.next = known.next;
   a.ids = ids_dev;
-  a.immutable = d.immutable;
-  a.n_unmatched = n_unmatched;
+  a.n_unmatched = known.n_unmatched;
   a.only_flagged = ex.only_flagged;
   a.n_flagged = ex.n_flagged;
   a.reset = ex.reset ? 1 : 0;
   a.gmax_key = ex.gmax_key;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
   a.B = B;
   a.P = d.P;
-  a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
+  a.qt = device_noise(qt);
+  static bool attr_set[kMaxDevices] = {false};  // the four instances that build their chains in LDS
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_observe_proposed<false, 1>, k_observe_range<false, 1>, k_observe_bearing<false, 1>,
+                    k_observe<false, 1>, k_observe<false, 2>);
   // (behind a one-pass kernel few particles, if any, are flagged: 4 096 workgroups walk the flags)
   const unsigned grid = (unsigned)(ex.only_flagged && d.P > 4096 ? 4096 : d.P);
   if (ex.dlogw) {  // behind k_propose (bearing model): the same two shapes
@@ -360,12 +355,6 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
       hipLaunchKernelGGL((k_observe_proposed<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a, ex.dlogw);
     } else {
       const size_t lds = observe_general_lds_bytes(d.lay.Lp, B);  // <= kMaxDynLds: checked by the caller
-      static bool attr_set[kMaxDevices] = {false};
-      if (first_time_on_this_device(attr_set)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_observe_proposed<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kMaxDynLds) != hipSuccess)
-          (void)hipGetLastError();
-      }
       hipLaunchKernelGGL((k_observe_proposed<false, 1>), dim3(grid), dim3(kObsThreads), lds, s, a, ex.dlogw);
     }
   } else if (ex.model == kModelBearing && ex.rng) {  // a scan with ranged blobs: the bearing model's two shapes again
@@ -373,12 +362,6 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
       hipLaunchKernelGGL((k_observe_range<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a);
     } else {
       const size_t lds = observe_general_lds_bytes(d.lay.Lp, B);  // <= kMaxDynLds: checked by the caller
-      static bool attr_set[kMaxDevices] = {false};
-      if (first_time_on_this_device(attr_set)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_observe_range<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kMaxDynLds) != hipSuccess)
-          (void)hipGetLastError();
-      }
       hipLaunchKernelGGL((k_observe_range<false, 1>), dim3(grid), dim3(kObsThreads), lds, s, a);
     }
   } else if (ex.model == kModelBearing) {  // the bearing model: k_observe's two shapes, no loop-free single-sighting kernel
@@ -386,12 +369,6 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
       hipLaunchKernelGGL((k_observe_bearing<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a);
     } else {
       const size_t lds = observe_general_lds_bytes(d.lay.Lp, B);  // <= kMaxDynLds: checked by the caller
-      static bool attr_set[kMaxDevices] = {false};
-      if (first_time_on_this_device(attr_set)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_observe_bearing<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kMaxDynLds) != hipSuccess)
-          (void)hipGetLastError();
-      }
       hipLaunchKernelGGL((k_observe_bearing<false, 1>), dim3(grid), dim3(kObsThreads), lds, s, a);
     }
   } else if (ids_dev == nullptr && ex.single_sightings && !ex.only_flagged && d.lay.Lp <= 1024 && g_observe_nv == 0) {
@@ -408,12 +385,6 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
       hipLaunchKernelGGL((k_observe<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a);
   } else {
     const size_t lds = observe_general_lds_bytes(d.lay.Lp, B);  // <= kMaxDynLds: checked by the caller
-    static bool attr_set[kMaxDevices] = {false};
-    if (first_time_on_this_device(attr_set)) {
-      for (const void* fn : {reinterpret_cast<const void*>(k_observe<false, 1>), reinterpret_cast<const void*>(k_observe<false, 2>)})
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess)
-          (void)hipGetLastError();
-    }
     if (g_observe_nv == 2)
       hipLaunchKernelGGL((k_observe<false, 2>), dim3(grid), dim3(kObsThreads), lds, s, a);
     else
@@ -423,6 +394,13 @@ void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, cons
     d.mcur ^= 1;
     d.alt = nullptr;  // every slot was rewritten into the particle's own map buffer
   }
+}
+void launch_observe(hipStream_t s, DeviceState& d, const ScanTables& scan, const KnownChains& known, const NoiseD& qt,
+                    const ObserveExtras& ex) {
+  observe_launch(s, d, scan, known, nullptr, qt, ex);
+}
+void launch_observe(hipStream_t s, DeviceState& d, const ScanTables& scan, int32_t* ids_dev, const NoiseD& qt, const ObserveExtras& ex) {
+  observe_launch(s, d, scan, KnownChains(), ids_dev, qt, ex);
 }
 
 }  // namespace pk

@@ -5,6 +5,7 @@
 // Hand-written gfx950 (CDNA4, wave64) kernels of the FastSLAM particle update; see DESIGN.md
 // section 4.  No MFMA: the algebra is 2x2 / 3x3 and register resident (pk_math.hpp).
 #include "pk_device.hpp"
+#include "pk_launch.hpp"
 
 // k_step_fused: where the lane's covariance rows are asked for -- 0: with the means, right behind the table words' requests
 // (rounds 1-3); 1 (default, round 4): when this wave's table words have ARRIVED (the rows of the early waves no longer stand in the
@@ -323,37 +324,18 @@ __global__ void __launch_bounds__(kFastThreads) k_observe_fast(FastArgs a) {
   }
 }
 
-void launch_observe_fast(hipStream_t s, DeviceState& d, int B, const double* exact_dev,
-                         const unsigned short* order_dev, const FastHandoff& fh, const NoiseD& qt,
+void launch_observe_fast(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
                          const ObserveExtras& ex) {
   if (d.P == 0) return;
-  FastArgs a;
-  a.ss = slot_source(d);
-  a.map_dst = d.map[d.mcur ^ 1];
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.logw = d.logw[d.cur];
-  a.exact = exact_dev;
-  a.order = order_dev;
+  FastArgs a{};
+  fill_state(a, d);
+  fill_scan(a, scan, ex, qt);
   a.lmpass = fh.lmpass;
   a.bcount = fh.bcount;
   a.pflag = fh.pflag;
-  a.immutable = d.immutable;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  a.reset = ex.reset ? 1 : 0;
-  a.gmax_key = ex.gmax_key;
-  a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
-  const size_t lds = observe_fast_lds_bytes(B);  // <= kMaxDynLds: checked by the caller
+  const size_t lds = observe_fast_lds_bytes(scan.B);  // <= kMaxDynLds: checked by the caller
   static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_observe_fast), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kMaxDynLds) != hipSuccess)
-      (void)hipGetLastError();
-  }
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_observe_fast);
   hipLaunchKernelGGL(k_observe_fast, dim3((unsigned)d.P), dim3(kFastThreads), lds, s, a);
 }
 
@@ -777,47 +759,23 @@ __global__ void __launch_bounds__(kFastThreads) __attribute__((amdgpu_waves_per_
   PK_FSTAMP_ADD(13, f0, f11)   // lifetime
 }
 
-void launch_step_fused(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
-                       const unsigned char* tables_dev, const double* exact_dev, const unsigned short* order_dev,
-                       const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const unsigned* pub_skipped_dev) {
+void launch_step_fused(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                       const ObserveExtras& ex, const unsigned* pub_skipped_dev) {
   if (d.P == 0) return;
   static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    for (const void* fn : {reinterpret_cast<const void*>(k_step_fused<false>), reinterpret_cast<const void*>(k_step_fused<true>)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess)
-        (void)hipGetLastError();
-  }
-  FusedArgs fa;
-  FastArgs& a = fa.f;
-  a.ss = slot_source(d);
-  a.map_dst = d.map[d.mcur ^ 1];
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.logw = d.logw[d.cur];
-  a.exact = exact_dev;
-  a.order = order_dev;
-  a.lmpass = nullptr;
-  a.bcount = nullptr;
-  a.pflag = nullptr;
-  a.immutable = d.immutable;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  a.reset = ex.reset ? 1 : 0;
-  a.gmax_key = ex.gmax_key;
-  a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
-  fa.g = grid;
-  fa.tables = tables_dev;
-  fa.h = d.h[d.cur];
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_step_fused<false>, k_step_fused<true>);
+  FusedArgs fa{};  // (f.lmpass, f.bcount, f.pflag: unused, null)
+  fill_state(fa, d);
+  fill_scan(fa, scan, ex, qt);
+  fa.g = scan.grid;
+  fa.tables = scan.tables;
   fa.pflag_out = fh.pflag;
   fa.n_flagged = fh.n_flagged;
-  fa.n9 = n9;
+  fa.n9 = scan.n9;
   fa.pub_skipped = pub_skipped_dev;
   // exact records + order table in LDS as well when two workgroups per CU still fit
-  const bool exact_lds = fused_lds_bytes(grid.ncell, B, n9, true) <= kFusedMaxLds;
-  const size_t lds = fused_lds_bytes(grid.ncell, B, n9, exact_lds);
+  const bool exact_lds = fused_lds_bytes(scan.grid.ncell, scan.B, scan.n9, true) <= kFusedMaxLds;
+  const size_t lds = fused_lds_bytes(scan.grid.ncell, scan.B, scan.n9, exact_lds);
   if (exact_lds)
     hipLaunchKernelGGL((k_step_fused<true>), dim3((unsigned)d.P), dim3(kFastThreads), lds, s, fa);
   else
@@ -1154,41 +1112,21 @@ __global__ void __launch_bounds__(kSweepThreads, 3) k_observe_sweep(SweepArgs a)
   }
 }
 
-void launch_observe_sweep(hipStream_t s, DeviceState& d, int B, const double* exact_dev,
-                          const unsigned short* order_dev, const FastHandoff& fh, const NoiseD& qt,
+void launch_observe_sweep(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
                           const ObserveExtras& ex, const SweepPlan& plan, uint4* results_dev) {
   if (d.P == 0 || plan.grid == 0) return;
   static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    for (const void* fn : {reinterpret_cast<const void*>(k_observe_sweep<kFastSlots>),
-                           reinterpret_cast<const void*>(k_observe_sweep<kSweepSlots>)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess)
-        (void)hipGetLastError();
-  }
-  SweepArgs a;
-  a.ss = slot_source(d);
-  a.map_dst = d.map[d.mcur ^ 1];
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.logw = d.logw[d.cur];
-  a.exact = exact_dev;
-  a.order = order_dev;
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_observe_sweep<kFastSlots>, k_observe_sweep<kSweepSlots>);
+  SweepArgs a{};
+  fill_state(a, d);
+  fill_scan(a, scan, ex, qt);
   a.lmpass = fh.lmpass;
   a.bcount = fh.bcount;
   a.pflag = fh.pflag;
   a.row_of = fh.row_of;
-  a.immutable = d.immutable;
   a.results = results_dev;
   a.P = d.P;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
   a.qcap = plan.qcap;
-  a.reset = ex.reset ? 1 : 0;
-  a.gmax_key = ex.gmax_key;
-  a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
   a.only_value = ex.sweep_only_value;
   a.n_flagged = ex.n_flagged;
   // never more workgroups than are resident at once (results_dev is sized for plan.grid)
@@ -2044,62 +1982,34 @@ __global__ void __launch_bounds__(PK_REGS_BOUND) k_step_regs(RegsArgs ra_unused)
   }
 }
 
-void launch_step_regs(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9, const unsigned char* tables_dev,
-                      const double* exact_dev, const unsigned short* order_dev, const FastHandoff& fh, const NoiseD& qt,
-                      const ObserveExtras& ex, int warm, const CandTable& cand, int64_t p0, int64_t p1, int reserve_cus) {
-  if (p1 < 0) p1 = d.P;
-  if (d.P == 0 || p1 <= p0) return;
+void launch_step_regs(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                      const ObserveExtras& ex, int warm, const CandTable& cand, const ParticleRange& range) {
+  // persistent grid: the workgroups that are resident at once (one per CU: 1024 lanes x 128 VGPRs)
+  const int64_t grid_n = persistent_grid(device_cu_count(), 1, range, d.P);
+  if (grid_n == 0) return;
   static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    for (const void* fn : {reinterpret_cast<const void*>(k_step_regs<false>), reinterpret_cast<const void*>(k_step_regs<true>)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess) (void)hipGetLastError();
-  }
-  RegsArgs ra;
-  FastArgs& a = ra.f;
-  a.ss = slot_source(d);
-  a.map_dst = d.map[d.mcur ^ 1];
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.logw = d.logw[d.cur];
-  a.exact = exact_dev;
-  a.order = order_dev;
-  a.lmpass = nullptr;
-  a.bcount = nullptr;
-  a.pflag = nullptr;
-  a.immutable = d.immutable;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  a.reset = ex.reset ? 1 : 0;
-  a.gmax_key = ex.gmax_key;
-  a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
-  ra.g = grid;
-  ra.tables = tables_dev;
-  ra.h = d.h[d.cur];
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_step_regs<false>, k_step_regs<true>);
+  RegsArgs ra{};  // (f.lmpass, f.bcount, f.pflag: unused, null)
+  fill_state(ra, d);
+  fill_scan(ra, scan, ex, qt);
+  ra.g = scan.grid;
+  ra.tables = scan.tables;
   ra.pflag_out = fh.pflag;
   ra.n_flagged = fh.n_flagged;
-  ra.n9 = n9;
+  ra.n9 = scan.n9;
   ra.warm = warm;
-  ra.P = p1;
-  ra.p_begin = p0;
+  ra.P = range.end(d.P);
+  ra.p_begin = range.p0;
   ra.cand = cand.rec;
   ra.cand_over = cand.rec ? cand.over : nullptr;
   ra.cand_skip = cand.rec ? (cand.skip_cand ? cand.skip_cand : cand.over) : nullptr;
-  // persistent grid: the workgroups that are resident at once (one per CU: 1024 lanes x 128 VGPRs)
-  const int n_cu = device_cu_count();
-  // reserve_cus: leave that many CUs without a workgroup -- this kernel's workgroups hold a CU's whole register file for the
-  // whole launch, and a collective that is to run meanwhile (the sharded filter's all-to-all) needs somewhere to run
-  int64_t grid_n = n_cu - (reserve_cus > 0 && reserve_cus < n_cu ? reserve_cus : 0);
-  if (grid_n > p1 - p0) grid_n = p1 - p0;
   if (cand.rec) {
-    hipLaunchKernelGGL(k_step_regs<true>, dim3((unsigned)grid_n), dim3(kRegsThreads), regs_cand_lds_bytes(d.lay.Lp, B), s, ra);
+    hipLaunchKernelGGL(k_step_regs<true>, dim3((unsigned)grid_n), dim3(kRegsThreads), regs_cand_lds_bytes(d.lay.Lp, scan.B), s, ra);
     // a scan in which some candidate list overflowed: every particle goes to the fall-back kernels (second chance on the
     // eight-slot hand-off, then the general kernels)
-    launch_flag_range_if(s, cand.over, fh.pflag, fh.n_flagged, p0, p1);
+    launch_flag_range_if(s, cand.over, fh.pflag, fh.n_flagged, range.p0, ra.P);
   } else {
-    hipLaunchKernelGGL(k_step_regs<false>, dim3((unsigned)grid_n), dim3(kRegsThreads), regs_lds_bytes(grid.ncell, B, n9), s, ra);
+    hipLaunchKernelGGL(k_step_regs<false>, dim3((unsigned)grid_n), dim3(kRegsThreads), regs_lds_bytes(scan.grid.ncell, scan.B, scan.n9), s, ra);
   }
 }
 

@@ -8,6 +8,7 @@
 // scattered 8-byte reads per row where the observe streams the whole slot, which is why it costs a fraction of that.  The sums
 // are reduced in a fixed order (each lane's blobs in scan order, the wave butterfly, the four waves' sums as block_sum adds them): no float
 // atomics, the same bits every run.  No scratch, 448 bytes of LDS.
+#include "pk_launch.hpp"
 #include "pk_motion_common.hpp"
 #include "pk_proposal.hpp"
 
@@ -110,13 +111,8 @@ __global__ void __launch_bounds__(kObsThreads) k_propose(ProposeArgs a) {
 
 void launch_propose(hipStream_t s, DeviceState& d, const ProposeLaunch& q) {
   if (d.P == 0) return;
-  ProposeArgs a;
-  a.ss = slot_source(d);
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
+  ProposeArgs a{};
+  fill_particles(a, d);
   a.blobs = q.blobs_dev;
   a.blobdir = q.blobdir_dev;
   a.ids = q.ids_dev;
@@ -136,11 +132,9 @@ void launch_propose(hipStream_t s, DeviceState& d, const ProposeLaunch& q) {
   a.xi = q.xi_dev;
   a.dlogw = q.dlogw_dev;
   a.used = q.used_dev;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
   a.B = q.B;
   a.P = d.P;
-  a.qt = make_noise(q.qt.q00, q.qt.rr, q.qt.rg, q.qt.rb, q.qt.gg, q.qt.gb, q.qt.bb);
+  a.qt = device_noise(q.qt);
   const unsigned grid = (unsigned)(d.P > 16384 ? 16384 : d.P);
   hipLaunchKernelGGL(k_propose, dim3(grid), dim3(kObsThreads), 0, s, a);
 }

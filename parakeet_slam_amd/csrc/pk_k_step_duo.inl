@@ -564,59 +564,24 @@ __global__ void __launch_bounds__(NL == 1 ? 512 : 256, NL == 1 ? 4 : 3) k_step_p
 #undef PK_DUO_L
 }
 
-void launch_step_pub_duo(hipStream_t s, DeviceState& d, int B, const double* exact_dev, const unsigned short* order_dev,
-                         const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const CandTable& cand, const uint4* erec_dev,
-                         const unsigned* glist_dev, const unsigned* skip_duo_dev, const unsigned* stats_dev, const DuoLimits& lim,
-                         const float4* gate4_dev, const uint4* prim_dev, int64_t p0, int64_t p1, int reserve_cus) {
-  if (p1 < 0) p1 = d.P;
-  if (d.P == 0 || p1 <= p0 || lim.tbytes <= 0 || !prim_dev || !stats_dev) return;
-  static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    for (const void* fn : {reinterpret_cast<const void*>(k_step_pub_duo<6, 1>), reinterpret_cast<const void*>(k_step_pub_duo<10, 1>)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDuoMaxDynLds) != hipSuccess) (void)hipGetLastError();
-    for (const void* fn : {reinterpret_cast<const void*>(k_step_pub_duo<6, 2>), reinterpret_cast<const void*>(k_step_pub_duo<10, 2>)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrioMaxDynLds) != hipSuccess) (void)hipGetLastError();
-  }
-  PubArgs a;
-  a.ss = slot_source(d);
-  a.map_dst = d.map[d.mcur ^ 1];
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.logw = d.logw[d.cur];
-  a.exact = exact_dev;
-  a.order = order_dev;
-  a.immutable = d.immutable;
-  a.cand = cand.rec;
-  a.erec = erec_dev;
-  a.glist = glist_dev;
-  a.skip = skip_duo_dev;
-  a.gate4 = gate4_dev;
-  a.far = cand.far;
-  a.prim = prim_dev;
-  a.unm = ex.unm;
-  a.unm_words = ex.unm_words;
-  a.pflag_out = fh.pflag;
-  a.n_flagged = fh.n_flagged;
-  a.P = p1;
-  a.p_begin = p0;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  a.ecap = lim.park_limit;  // (the kernel reads THIS scan's entry count from a.stats; this field: the overflow area's debug limit)
-  a.stats = stats_dev;
-  a.tbytes = lim.tbytes;
-  a.reset = ex.reset ? 1 : 0;
-  a.gmax_key = ex.gmax_key;
-  a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
-  const int n_cu = device_cu_count();
-  // persistent grid, TWO 512-lane (or THREE 256-lane) workgroups per CU; reserve_cus as in launch_step_regs
+void launch_step_pub_duo(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                         const ObserveExtras& ex, const PubTables& pub, const ParticleRange& range) {
+  const DuoLimits& lim = pub.duo;
+  // persistent grid, TWO 512-lane (or THREE 256-lane) workgroups per CU
   const int per_cu = lim.nl == 2 ? 3 : 2, th = lim.nl == 2 ? 256 : 512;
-  int64_t grid_n = per_cu * (int64_t)(n_cu - (reserve_cus > 0 && reserve_cus < n_cu ? reserve_cus : 0));
-  if (grid_n > p1 - p0) grid_n = p1 - p0;
-  const size_t lds = step_pub_duo_lds_bytes(B, lim);
+  const int64_t grid_n = persistent_grid(device_cu_count(), per_cu, range, d.P);
+  if (grid_n == 0 || lim.tbytes <= 0 || !pub.prim || !pub.stats) return;
+  static bool attr_set[kMaxDevices] = {false}, attr_set3[kMaxDevices] = {false};
+  allow_dynamic_lds(attr_set, kDuoMaxDynLds, k_step_pub_duo<6, 1>, k_step_pub_duo<10, 1>);
+  allow_dynamic_lds(attr_set3, kTrioMaxDynLds, k_step_pub_duo<6, 2>, k_step_pub_duo<10, 2>);
+  PubArgs a = pub_args(d, scan, fh, qt, ex, pub, range);
+  a.skip = pub.skip_duo;
+  a.gate4 = pub.gate4;
+  a.prim = pub.prim;
+  a.ecap = lim.park_limit;  // (the kernel reads THIS scan's entry count from a.stats; this field: the overflow area's debug limit)
+  a.stats = pub.stats;
+  a.tbytes = lim.tbytes;
+  const size_t lds = step_pub_duo_lds_bytes(scan.B, lim);
   const int nt = (d.lay.Lp + kDuoTurn - 1) / kDuoTurn;
   if (lim.nl == 2) {
     if (nt <= 6)

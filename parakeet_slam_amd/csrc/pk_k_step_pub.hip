@@ -46,6 +46,7 @@
 
 #include "pk_colour.hpp"
 #include "pk_device.hpp"
+#include "pk_launch.hpp"
 #include "pk_pub_math.hpp"
 #include "pk_pub_layout.hpp"
 
@@ -2399,58 +2400,39 @@ __global__ void __launch_bounds__(kPubThreads) k_step_pub_big(PubArgs a_unused) 
 #undef PK_BIG_WAIT_ALL
 }
 
-void launch_step_pub_big(hipStream_t s, DeviceState& d, int B, const double* exact_dev, const unsigned short* order_dev,
-                         const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const CandTable& cand, const uint4* erec_dev,
-                         const unsigned* glist_dev, const unsigned* skip_dev, int ecap, const uint4* prim_dev, const unsigned* stats_dev,
-                         const float4* gate4_dev, int64_t p0, int64_t p1, int reserve_cus) {
-  if (p1 < 0) p1 = d.P;
-  if (d.P == 0 || p1 <= p0) return;
-  static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    for (const void* fn : {reinterpret_cast<const void*>(k_step_pub_big<3>), reinterpret_cast<const void*>(k_step_pub_big<5>),
-                           reinterpret_cast<const void*>(k_step_pub_big<6>)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess) (void)hipGetLastError();
-  }
-  PubArgs a;
-  a.ss = slot_source(d);
-  a.map_dst = d.map[d.mcur ^ 1];
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.logw = d.logw[d.cur];
-  a.exact = exact_dev;
-  a.order = order_dev;
-  a.immutable = d.immutable;
-  a.cand = cand.rec;
-  a.erec = erec_dev;
-  a.glist = glist_dev;
-  a.skip = skip_dev;
-  a.gate4 = gate4_dev;
-  a.far = cand.far;
-  a.prim = prim_dev;
-  a.stats = stats_dev;
-  a.tbytes = 0;
+// What the three launchers of this file hand their kernel alike; `skip`, `ecap`, `stats` and the two-pass members are each one's own
+static PubArgs pub_args(const DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex,
+                        const PubTables& pub, const ParticleRange& range) {
+  PubArgs a{};
+  fill_state(a, d);
+  fill_scan(a, scan, ex, qt);
+  a.cand = pub.cand.rec;
+  a.far = pub.cand.far;
+  a.erec = pub.erec;
+  a.glist = pub.glist;
   a.unm = ex.unm;
   a.unm_words = ex.unm_words;
   a.pflag_out = fh.pflag;
   a.n_flagged = fh.n_flagged;
-  a.P = p1;
-  a.p_begin = p0;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  a.ecap = ecap;
-  a.reset = ex.reset ? 1 : 0;
-  a.gmax_key = ex.gmax_key;
-  a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
-  const int n_cu = device_cu_count();
-  // persistent grid, one workgroup per CU; reserve_cus as in launch_step_regs (the first part of a split step leaves CUs to
-  // the all-to-all's kernels)
-  int64_t grid_n = n_cu - (reserve_cus > 0 && reserve_cus < n_cu ? reserve_cus : 0);
-  if (grid_n > p1 - p0) grid_n = p1 - p0;
-  const size_t lds = step_pub_big_lds_bytes(B, ecap);
+  a.P = range.end(d.P);
+  a.p_begin = range.p0;
+  return a;
+}
+
+void launch_step_pub_big(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                         const ObserveExtras& ex, const PubTables& pub, const ParticleRange& range) {
+  // persistent grid, one workgroup per CU
+  const int64_t grid_n = persistent_grid(device_cu_count(), 1, range, d.P);
+  if (grid_n == 0) return;
+  static bool attr_set[kMaxDevices] = {false};
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_step_pub_big<3>, k_step_pub_big<5>, k_step_pub_big<6>);
+  PubArgs a = pub_args(d, scan, fh, qt, ex, pub, range);
+  a.skip = pub.skip_big;
+  a.gate4 = pub.gate4;
+  a.prim = pub.prim;
+  a.stats = pub.stats;
+  a.ecap = pub.ecap;
+  const size_t lds = step_pub_big_lds_bytes(scan.B, pub.ecap);
   const int nch = (d.lay.Lp + 2 * kPubThreads - 1) / (2 * kPubThreads);
   if (nch <= 3)
     hipLaunchKernelGGL(k_step_pub_big<3>, dim3((unsigned)grid_n), dim3(kPubThreads), lds, s, a);
@@ -2460,66 +2442,27 @@ void launch_step_pub_big(hipStream_t s, DeviceState& d, int B, const double* exa
     hipLaunchKernelGGL(k_step_pub_big<6>, dim3((unsigned)grid_n), dim3(kPubThreads), lds, s, a);
 }
 
-void launch_step_pub(hipStream_t s, DeviceState& d, int B, const double* exact_dev, const unsigned short* order_dev,
-                     const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const CandTable& cand, const uint4* erec_dev,
-                     const unsigned* glist_dev, const unsigned* skip_dev, int ecap, int64_t p0, int64_t p1, int reserve_cus) {
-  if (p1 < 0) p1 = d.P;
-  if (d.P == 0 || p1 <= p0) return;
-  static bool attr_set[kMaxDevices] = {false};
-  if (first_time_on_this_device(attr_set)) {
-    for (const void* fn : {reinterpret_cast<const void*>(k_step_pub<1, kPubSmallThreads>), reinterpret_cast<const void*>(k_step_pub<1, kPubThreads>),
-                           reinterpret_cast<const void*>(k_step_pub<2, kPubThreads>), reinterpret_cast<const void*>(k_step_pub<1, kPubThreads, true>),
-                           reinterpret_cast<const void*>(k_step_pub<2, kPubThreads, true>)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds) != hipSuccess) (void)hipGetLastError();
-  }
-  PubArgs a;
-  a.ss = slot_source(d);
-  a.map_dst = d.map[d.mcur ^ 1];
-  a.count_off = d.lay.count_off;
-  a.src = d.src[d.cur];
-  a.x = d.x[d.cur];
-  a.y = d.y[d.cur];
-  a.h = d.h[d.cur];
-  a.logw = d.logw[d.cur];
-  a.exact = exact_dev;
-  a.order = order_dev;
-  a.immutable = d.immutable;
-  a.cand = cand.rec;
-  a.erec = erec_dev;
-  a.glist = glist_dev;
-  a.skip = skip_dev;
-  a.gate4 = nullptr;
-  a.prim = nullptr;
-  a.stats = ex.lean_stats;
-  a.tbytes = 0;
-  a.unm = ex.unm;
-  a.unm_words = ex.unm_words;
-  a.far = cand.far;
-  a.pflag_out = fh.pflag;
-  a.n_flagged = fh.n_flagged;
-  a.P = p1;
-  a.p_begin = p0;
-  a.L = d.lay.L;
-  a.Lp = d.lay.Lp;
-  a.B = B;
-  a.ecap = ecap;
-  a.reset = ex.reset ? 1 : 0;
-  a.gmax_key = ex.gmax_key;
-  a.qt = make_noise(qt.q00, qt.rr, qt.rg, qt.rb, qt.gg, qt.gb, qt.bb);
-  const int n_cu = device_cu_count();
-  // persistent grid: one workgroup per CU (512 lanes x 256 VGPRs), three of the 256-lane instance (143 VGPRs; LDS permitting);
-  // reserve_cus as in launch_step_regs
+void launch_step_pub(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                     const ObserveExtras& ex, const PubTables& pub, const ParticleRange& range) {
+  // persistent grid: one workgroup per CU (512 lanes x 256 VGPRs), three of the 256-lane instance (143 VGPRs; LDS permitting)
   const bool small = d.lay.Lp <= 2 * kPubSmallThreads;
+  const size_t lds = step_pub_lds_bytes(scan.B, pub.ecap, small);
+  int per_cu = 1;
+  if (small) per_cu = (int)std::min<size_t>(3, std::max<size_t>(1, (160 * 1024 - 1024) / (lds + 256)));
+  const int64_t grid_n = persistent_grid(device_cu_count(), per_cu, range, d.P);
+  if (grid_n == 0) return;
+  static bool attr_set[kMaxDevices] = {false};
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_step_pub<1, kPubSmallThreads>, k_step_pub<1, kPubThreads>, k_step_pub<2, kPubThreads>,
+                    k_step_pub<1, kPubThreads, true>, k_step_pub<2, kPubThreads, true>);
+  PubArgs a = pub_args(d, scan, fh, qt, ex, pub, range);
+  a.skip = pub.skip_pub;
+  a.stats = ex.lean_stats;
+  a.ecap = pub.ecap;
   const bool tab = ex.ctab != nullptr && !small;
   a.ctab = tab ? ex.ctab : nullptr;
   a.ctab_max = ex.ctab_max;
   a.ctab_depth = ex.ctab_depth;
   a.lean = ex.lean;
-  const size_t lds = step_pub_lds_bytes(B, ecap, small);
-  int per_cu = 1;
-  if (small) per_cu = (int)std::min<size_t>(3, std::max<size_t>(1, (160 * 1024 - 1024) / (lds + 256)));
-  int64_t grid_n = (int64_t)(n_cu - (reserve_cus > 0 && reserve_cus < n_cu ? reserve_cus : 0)) * per_cu;
-  if (grid_n > p1 - p0) grid_n = p1 - p0;
   if (small)
     hipLaunchKernelGGL((k_step_pub<1, kPubSmallThreads>), dim3((unsigned)grid_n), dim3(kPubSmallThreads), lds, s, a);
   else if (d.lay.Lp <= 2 * kPubThreads) {

@@ -1,4 +1,4 @@
-// Host-visible launchers of the gfx950 kernels (defined in pk_k_motion / pk_k_assoc / pk_k_observe / pk_k_resample .hip).
+// Host-visible launchers of the gfx950 kernels (defined in the twenty pk_k_*.hip files; pk_k_step_duo.inl is part of pk_k_step_pub.hip).
 #pragma once
 #include <cmath>
 #include <hip/hip_runtime.h>
@@ -115,9 +115,7 @@ void launch_motion_odom_range(hipStream_t s, DeviceState& d, const double delta[
                               uint64_t draw, int64_t p0, int64_t p1);
 void launch_reset_weights(hipStream_t s, DeviceState& d);
 // K2: maximum-likelihood association -> ids[P*B]
-// (a) reference kernel: every (landmark, blob) pair is gate-tested
-void launch_assoc_brute(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev,
-                        int B, int32_t* ids_dev, int model = 0, const double* rng_dev = nullptr, double q00 = 0.0);
+// (a) reference kernel: every (landmark, blob) pair is gate-tested (launch_assoc_brute, below the scan's tables)
 // (b) production kernel: blobs bucketed on the host into a 3-D colour grid whose cell edge
 // exceeds the colour gate radius sqrt(300), so a landmark only meets the blobs of its 27
 // neighbouring cells.  Tables (device): start u16[ncell+1] (16-byte padded) | rec32
@@ -165,7 +163,41 @@ inline int device_cu_count() {
   if (known) n_cu[dev] = n;
   return n;
 }
-// Hand-off from the association kernel to k_observe_fast (all three NULL = not used).
+// The device view of one uploaded scan.  A maximum-likelihood scan (the observe's enqueue_association fills it, nobody else): the
+// blobs and their rays in scan order, the colour grid with its tables, the exact records and the order table in cell order, and --
+// only for a scan in which some blob has a range (pk_scan_ranges) -- the range rows [B][2] (range, variance) in scan order and in
+// cell order.  A scan with supplied ids has B and the blobs alone.
+struct ScanTables {
+  int B = 0;
+  const double* blobs = nullptr;  // [B][4]
+  const double* dir = nullptr;    // [B][2]
+  BlobGrid grid{};
+  int n9 = 0;
+  const unsigned char* tables = nullptr;
+  const double* exact = nullptr;  // [B][6]
+  const unsigned short* order = nullptr;
+  const double* rng = nullptr;
+  const double* rng_cell = nullptr;
+};
+// The particles [p0, p1) of a launch (p1 < 0: up to the last one), and how many CUs a persistent kernel leaves without a
+// workgroup: its workgroups hold their CUs for the whole launch, and a collective that is to run meanwhile (the all-to-all of the
+// sharded filter's split step) needs somewhere to run.
+struct ParticleRange {
+  int64_t p0 = 0, p1 = -1;
+  int reserve_cus = 0;
+  int64_t end(int64_t P) const { return p1 < 0 ? P : p1; }
+};
+// Workgroups of a persistent kernel that keeps per_cu of them on a CU, over the particles `r` of P: the ones resident at once (a
+// reserve outside (0, n_cu) is ignored), never more than particles; 0: the range is empty, nothing to launch.
+inline int64_t persistent_grid(int n_cu, int per_cu, const ParticleRange& r, int64_t P) {
+  const int64_t n = r.end(P) - r.p0;
+  if (P <= 0 || n <= 0) return 0;
+  const int64_t grid = (int64_t)(n_cu - (r.reserve_cus > 0 && r.reserve_cus < n_cu ? r.reserve_cus : 0)) * per_cu;
+  return grid > n ? n : grid;
+}
+void launch_assoc_brute(hipStream_t s, DeviceState& d, const ScanTables& scan, int32_t* ids_dev, int model = 0, double q00 = 0.0);
+// Hand-off from the association kernel to k_observe_fast (lmpass NULL and flags_only false, as a default-constructed one has
+// them = not used: the association's general instance takes every particle).
 struct FastHandoff {
   uint4* lmpass = nullptr;          // [rows][Lp] (slots = 4) or [rows][Lp][2] (slots = 8): see k_assoc_grid; rows = P, or with
                                     // `retry` the capped number of second-chance rows (row_of / row_next / row_cap below)
@@ -218,34 +250,35 @@ struct ColourTable {
 void launch_colour_table(hipStream_t s, const double* base_dev, double* tab_dev, int depth, int Lp, const NoiseD& qt);
 // The six colour rows of map slots written from the table at the slots' counts (levels beyond the table: the recurrence from its last
 // level).  pflag_dev == NULL: every slot of the live buffer; else the SOURCE slots of the particles whose flag is set, and nothing at
-// all while *n_flagged_dev == 0.  [p0, p1): the slots (or, with pflag_dev, the particles) covered; p1 < 0: all of them.
-void launch_colour_rows(hipStream_t s, DeviceState& d, const ColourTable& ct, const NoiseD& qt, const unsigned char* pflag_dev = nullptr,
-                        const unsigned* n_flagged_dev = nullptr, int64_t p0 = 0, int64_t p1 = -1);
+// all while *n_flagged_dev == 0.  range: the slots (or, with pflag_dev, the particles) covered (its reserve_cus is not looked at).
+void launch_colour_rows(hipStream_t s, DeviceState& d, const ColourTable& ct, const NoiseD& qt, const ParticleRange& range = ParticleRange(),
+                        const unsigned char* pflag_dev = nullptr, const unsigned* n_flagged_dev = nullptr);
 // *any_dev |= 1 when some landmark of some slot of the live buffer has a count other than 0.
 void launch_colour_counts_any(hipStream_t s, DeviceState& d, unsigned* any_dev);
 constexpr int kFastSlots = 4;   // gate-passing blobs a landmark can hand over to k_observe_fast; more -> general path
 constexpr int kSweepSlots = 8;  // ... to k_observe_sweep (large maps: a landmark's colour neighbourhood is busier)
 constexpr int kFastMaxL = 512;  // k_observe_fast / k_step_fused keep a particle's whole map in registers (one landmark per lane, 512 lanes)
-void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
-                       const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev,
-                       bool finalize, const FastHandoff& fh);
-// the bearing model's association (pk_math.hpp: kModelBearing): the general instance alone, every particle
-void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
-                               const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev, bool finalize,
-                               const double* rng_cell_dev = nullptr, double q00 = 0.0);
+// the bearing model's association (pk_math.hpp: kModelBearing): the general instance alone, every particle; a scan with
+// scan.rng_cell takes the range instances
+void launch_assoc_grid_bearing(hipStream_t s, DeviceState& d, const ScanTables& scan, int32_t* ids_dev, bool finalize, double q00 = 0.0);
 // ML observe for L <= kFastMaxL straight from the hand-off: contested blobs are settled here,
 // with the landmark state in registers.  Particles flagged in fh.pflag are skipped (the general
 // k_observe, launched with only_flagged, takes them).
 size_t observe_fast_lds_bytes(int B);  // dynamic LDS of k_observe_fast: must fit kMaxDynLds
-void launch_observe_fast(hipStream_t s, DeviceState& d, int B, const double* exact_dev,
-                         const unsigned short* order_dev, const FastHandoff& fh, const NoiseD& qt,
+void launch_observe_fast(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
                          const ObserveExtras& ex = ObserveExtras());
-// K3: EKF update + log-weight.  known: first/next chains shared by all particles (device
-// arrays, built on the host); otherwise built per particle in LDS from ids_dev.
-// ML ids are TENTATIVE: k_observe keeps a match only if its probability is > 0 (needs blobdir).
-void launch_observe(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev, int B,
-                    const int32_t* first_dev, const int32_t* next_dev, int n_unmatched,
-                    int32_t* ids_dev, const NoiseD& qt, const ObserveExtras& ex = ObserveExtras());
+// K3: EKF update + log-weight, from scan.blobs.  Supplied ids: the landmark -> blob chains shared by all particles (device arrays,
+// built on the host).  Otherwise ids_dev [P][B], from which the chains are built per particle in LDS: ML ids are TENTATIVE --
+// k_observe keeps a match only if its probability is > 0 (needs scan.dir) --, k_propose's are final (ex.dlogw).
+struct KnownChains {
+  const int32_t* first = nullptr;  // [Lp] first blob matched to landmark l, or -1
+  const int32_t* next = nullptr;   // [B] next blob matched to the same landmark, or -1
+  int n_unmatched = 0;             // blobs with id 0
+};
+void launch_observe(hipStream_t s, DeviceState& d, const ScanTables& scan, const KnownChains& known, const NoiseD& qt,
+                    const ObserveExtras& ex = ObserveExtras());
+void launch_observe(hipStream_t s, DeviceState& d, const ScanTables& scan, int32_t* ids_dev, const NoiseD& qt,
+                    const ObserveExtras& ex = ObserveExtras());
 // The measurement-informed proposal (pk_k_propose.hip): for every particle at its predicted pose (the live pose
 // arrays) the normals xi, the weight increment and the matches used; tentative ids (blobdir_dev != NULL) are settled in place.
 struct ProposeLaunch {
@@ -274,17 +307,15 @@ struct SweepPlan {
   size_t results_per_wg = 0;  // uint4 entries of global scratch per workgroup
 };
 SweepPlan observe_sweep_plan(const DeviceState& d, int B);
-void launch_observe_sweep(hipStream_t s, DeviceState& d, int B, const double* exact_dev,
-                          const unsigned short* order_dev, const FastHandoff& fh, const NoiseD& qt,
+void launch_observe_sweep(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
                           const ObserveExtras& ex, const SweepPlan& plan, uint4* results_dev);
 // K2 + K3 fused for L <= kFastMaxL and scan tables small enough for two workgroups per CU: gates,
 // settling and EKF update of a particle in one workgroup, no hand-off through HBM.  Writes fh.pflag /
 // fh.n_flagged (particles left to the general kernels).
 size_t fused_lds_bytes(int ncell, int B, int n9, bool exact_lds = false);
 constexpr size_t kFusedMaxLds = 78 * 1024;
-void launch_step_fused(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
-                       const unsigned char* tables_dev, const double* exact_dev, const unsigned short* order_dev,
-                       const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const unsigned* pub_skipped_dev = nullptr);
+void launch_step_fused(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                       const ObserveExtras& ex, const unsigned* pub_skipped_dev = nullptr);
 // Candidate lists from a reference particle (k_candidates).  All particles of a filter see the same scan and hold
 // nearly the same map (same initial map, same blobs matched), so the blobs that can pass a landmark's two gates
 // (prkt_core_v2.py:433, :441) are nearly the same for every particle.  Once per scan, for every landmark of ONE
@@ -313,16 +344,25 @@ struct CandTable {
   const uint4* far = nullptr;         // [Lp][1 + slots / 8] (Kb, Ib, n, 0) | far list: look-alikes k_candidates took off the lists (pk_pub_math.hpp), or NULL
   int slots = kCandSlots;             // entries per list: kCandSlots ([Lp][2] records) or twice that ([Lp][3]; no inverse lists)
 };
-// launch_assoc_grid whose hand-off instance takes its gates from the candidate lists (while no list overflowed)
-void launch_assoc_grid(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9,
-                       const unsigned char* tables_dev, const double* exact_dev, int32_t* ids_dev,
-                       bool finalize, const FastHandoff& fh, const CandTable& cand);
-// bcnt_dev / brec_dev: NULL, or u32[B] / u16[B][slots] (cleared / filled with 0xFF by this call); stray_dev: their count
-void launch_candidates(hipStream_t s, DeviceState& d, int B, const double* exact_dev, int64_t ref_particle, uint4* rec_dev,
-                       unsigned* over_dev, unsigned* bcnt_dev = nullptr, uint4* brec_dev = nullptr, unsigned* stray_dev = nullptr,
-                       int slots = kCandSlots, const double* pose_sums4_dev = nullptr, unsigned char* npass_dev = nullptr,
-                       uint4* far_dev = nullptr, const double* pose_part_dev = nullptr,  // pose_part_dev: the motion launch's per-block sums instead of pose_sums4_dev
-                       const ColourTable& ct = ColourTable(), const NoiseD* qt = nullptr);  // ct.tab: the reference's colour blocks come from the table
+// the grid kernel ((b) above); with cand.rec its hand-off instance takes its gates from the candidate lists (while no list overflowed)
+void launch_assoc_grid(hipStream_t s, DeviceState& d, const ScanTables& scan, int32_t* ids_dev, bool finalize, const FastHandoff& fh,
+                       const CandTable& cand = CandTable());
+// One launch of k_candidates.  rec and over have no default: without them there is nothing to launch.
+struct CandidatesLaunch {
+  uint4* rec;                           // out: the lists, [Lp + kCandSpare][2] or [..][3] (what CandTable::rec reads)
+  unsigned* over;                       // out: CandTable::over
+  int slots = kCandSlots;               // entries per list
+  int64_t ref_particle = 0;             // the particle whose map the lists are made from
+  const double* pose_sums4 = nullptr;   // the reference pose is the particles' mean: from launch_summary_partials' four sums,
+  const double* pose_part = nullptr;    //   or from the per-block sums the motion launch left (motion_pose_blocks)
+  unsigned* bcnt = nullptr;             // the inverse lists, u32[B] / u16[B][slots]: empty (0 / 0xFF) at the call, and emptied again
+  uint4* brec = nullptr;                //   by k_cand_entries behind its last read; both NULL: none are made
+  unsigned char* npass = nullptr;       // out [Lp + kCandSpare], or NULL
+  uint4* far = nullptr;                 // out: CandTable::far; NULL: no look-alike is taken off the lists
+  ColourTable ct;                       // ct.tab, and qt, the noise the table was built with: the reference's colour blocks come
+  const NoiseD* qt = nullptr;           //   from the table (its slot's rows may be stale); either missing: from its slot
+};
+void launch_candidates(hipStream_t s, DeviceState& d, const ScanTables& scan, const CandidatesLaunch& c);
 // K2 + K3 in one pass (pk_k_observe_ml.hip, pk_k_step_pub.hip).  (k_step_owner, a barrier-free variant in which every
 // landmark settled its blobs against the rivals named by the two-way lists, was measured at 56 ms against 13 and removed
 // in round 3: DESIGN.md section 4.)
@@ -334,10 +374,8 @@ size_t regs_cand_lds_bytes(int Lp, int B);
 // cand.rec != NULL: the candidate-list instance (returns at once when *cand.skip_cand != 0), and a scan in which a list
 // overflowed hands all its particles to the fall-back kernels (the grid-walk instance -- cand.rec == NULL, option
 // "cand_lists" = 0 -- still spills eight registers and is no default route's kernel any more)
-void launch_step_regs(hipStream_t s, DeviceState& d, int B, const BlobGrid& grid, int n9, const unsigned char* tables_dev,
-                      const double* exact_dev, const unsigned short* order_dev, const FastHandoff& fh, const NoiseD& qt,
-                      const ObserveExtras& ex, int warm, const CandTable& cand = CandTable(), int64_t p0 = 0, int64_t p1 = -1,
-                      int reserve_cus = 0);
+void launch_step_regs(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                      const ObserveExtras& ex, int warm, const CandTable& cand = CandTable(), const ParticleRange& range = ParticleRange());
 // K2 + K3 in one pass with STATIC publish / subscribe settling (pk_k_step_pub.hip): 512 < L <= kRegsMaxL, candidate lists
 // both ways (cand.rec, and the inverse lists that launch_cand_entries turns into the publish table's layout: erec, binfo).
 // 512-lane persistent workgroups, four landmarks per lane, two barriers per particle.  Returns at once when *skip != 0.
@@ -353,22 +391,44 @@ struct DuoLimits {
   int nl = 1;      // landmarks per lane and turn: 1 (512 lanes, two workgroups per CU) or 2 (256 lanes with a pair each, three per CU)
   int park_limit = -1;  // >= 0 (tests, option "pub_duo_park_limit"): the kernel treats its overflow area as this many places
 };
-void launch_cand_entries(hipStream_t s, const DeviceState& d, int B, const uint4* cand_dev, uint4* erec_dev, unsigned* bcnt_dev,
-                         uint4* brec_dev, unsigned* binfo_dev, unsigned* glist_dev, const unsigned* over_dev, unsigned* skip_pub_dev,
-                         unsigned* skip_cand_dev, int ecap, int slots = kCandSlots, const double* exact_dev = nullptr,
-                         float4* gate4_dev = nullptr, const unsigned char* npass_dev = nullptr, bool pruned = false,
-                         unsigned* stats_dev = nullptr, unsigned* skip_duo_dev = nullptr, unsigned* skip_big_dev = nullptr,
-                         const DuoLimits& duo = DuoLimits(), uint4* prim_dev = nullptr, unsigned char* flag_all_dev = nullptr,
-                         unsigned* n_flagged_dev = nullptr);  // flag_all_dev: [P] a scan nobody takes flags every particle in this very launch
+// What the publish / subscribe route shares: k_candidates and k_cand_entries write it once per scan (the observe's onepass_prepare
+// fills this, and decides there which members a scan's kernels get), the three k_step_pub* launchers read it.  A member that is
+// NULL switches its part off.
+struct PubTables {
+  CandTable cand;                    // the lists (every one-pass kind with lists has these; the rest: publish / subscribe alone)
+  uint4* erec = nullptr;             // [Lp + kCandSpare] ([..][2] with sixteen-entry lists): the publish entries of every list's blobs
+  unsigned* glist = nullptr;         // the blobs several landmarks list, compacted; their number; the octet orders
+  unsigned* bcnt = nullptr;          // the inverse lists (CandidatesLaunch::bcnt, brec) and k_cand_entries' scratch per blob
+  uint4* brec = nullptr;
+  unsigned* binfo = nullptr;
+  unsigned char* npass = nullptr;    // [Lp + kCandSpare] blobs inside the reference particle's own gates
+  unsigned* stats = nullptr;         // [7] k_cand_entries' figures of the scan
+  unsigned* skip_pub = nullptr;      // != 0 after k_cand_entries: k_step_pub stands back from this scan (a list overflowed, the table does not fit)
+  unsigned* skip_cand = nullptr;     // ... k_step_regs' candidate-list instance does
+  int ecap = 0;                      // entries of the publish table that fit LDS
+  // the two-pass kernels (sixteen-entry lists) alone, else NULL:
+  float4* gate4 = nullptr;           // [B] every blob's bearing and colour as float (with it k_cand_entries reads the scan's exact records)
+  uint4* prim = nullptr;             // the primary-blob table (prim_table_uint4)
+  unsigned* skip_duo = nullptr;      // != 0: k_step_pub_duo stands back / k_step_pub_big does (one of the two takes the scan, or neither)
+  unsigned* skip_big = nullptr;
+  DuoLimits duo;                     // what k_step_pub_duo has room for (tbytes 0: the instance is off)
+};
+// One launch of k_cand_entries: the publish table's layout from the lists both ways.  pub.cand.rec, cand.over, erec, bcnt, brec,
+// binfo, glist, skip_pub and skip_cand are needed whatever the scan.
+struct CandEntriesLaunch {
+  PubTables pub;
+  bool pruned = false;                // the lists have had their far look-alikes taken off (CandidatesLaunch::far)
+  unsigned char* flag_all = nullptr;  // [P] with n_flagged: a scan nobody takes flags every particle in this very launch
+  unsigned* n_flagged = nullptr;
+};
+void launch_cand_entries(hipStream_t s, const DeviceState& d, const ScanTables& scan, const CandEntriesLaunch& c);
 // The primary-blob table of the two-pass kernels (k_cand_entries writes it, once per scan): for every landmark l (and the kCandSpare
 // spare records) the records of the FIRST blob of its candidate list, in landmark order -- four planes of Lp + kCandSpare uint4
 // (bearing, r, g, b as float | exact bearing, r | exact g, b | ray direction ux, uy), then the blob's index per landmark (u32;
 // 0xFFFF: the list is empty)
 inline size_t prim_table_uint4(int Lp) { const size_t Lpp = (size_t)Lp + kCandSpare; return 4 * Lpp + (Lpp + 3) / 4; }
-void launch_step_pub(hipStream_t s, DeviceState& d, int B, const double* exact_dev, const unsigned short* order_dev,
-                     const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const CandTable& cand, const uint4* erec_dev,
-                     const unsigned* glist_dev, const unsigned* skip_dev, int ecap, int64_t p0 = 0, int64_t p1 = -1,
-                     int reserve_cus = 0);
+void launch_step_pub(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                     const ObserveExtras& ex, const PubTables& pub, const ParticleRange& range = ParticleRange());
 // every particle of [p0, p1) flagged for the fall-back kernels when *over != 0 (a candidate list overflowed)
 void launch_flag_range_if(hipStream_t s, const unsigned* over_dev, unsigned char* pflag_dev, unsigned* n_flagged_dev, int64_t p0, int64_t p1);
 // The same for maps beyond kRegsMaxL landmarks (up to kPubBigMaxL), in two passes over the map (the second from L2 / Infinity
@@ -376,20 +436,17 @@ void launch_flag_range_if(hipStream_t s, const unsigned* over_dev, unsigned char
 constexpr int kPubBigMaxL = 6144;  // six pairs per lane: beyond that the slot words of a lane no longer fit its registers
 int step_pub_big_entry_capacity(int B);
 size_t step_pub_big_lds_bytes(int B, int ecap);
-void launch_step_pub_big(hipStream_t s, DeviceState& d, int B, const double* exact_dev, const unsigned short* order_dev,
-                         const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const CandTable& cand, const uint4* erec_dev,
-                         const unsigned* glist_dev, const unsigned* skip_dev, int ecap, const uint4* prim_dev, const unsigned* stats_dev,
-                         const float4* gate4_dev = nullptr, int64_t p0 = 0, int64_t p1 = -1, int reserve_cus = 0);
+void launch_step_pub_big(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                         const ObserveExtras& ex, const PubTables& pub, const ParticleRange& range = ParticleRange());
 // The two-workgroups-per-CU instance of the two-pass kernel (pk_k_step_duo.hip): ONE landmark per lane and turn, one carried word
 // per landmark, the expected bearing worked out again in pass 2 -- at most 128 VGPRs, so that two 512-lane workgroups share a CU
 // (four waves per SIMD) and one's row latency is the other's float64 issue.  Each has half the CU's LDS: k_cand_entries decides per
 // scan whether the publish table fits (step_pub_duo_limits -> DuoLimits; *skip_duo), k_step_pub_big takes the scans that do not.
 void step_pub_duo_limits(int B, int Lp, int nl, DuoLimits* out);
 size_t step_pub_duo_lds_bytes(int B, const DuoLimits& lim);
-void launch_step_pub_duo(hipStream_t s, DeviceState& d, int B, const double* exact_dev, const unsigned short* order_dev,
-                         const FastHandoff& fh, const NoiseD& qt, const ObserveExtras& ex, const CandTable& cand, const uint4* erec_dev,
-                         const unsigned* glist_dev, const unsigned* skip_duo_dev, const unsigned* stats_dev, const DuoLimits& lim,
-                         const float4* gate4_dev, const uint4* prim_dev, int64_t p0 = 0, int64_t p1 = -1, int reserve_cus = 0);
+// (nothing is launched while pub.duo.tbytes is 0, or without pub.prim and pub.stats)
+void launch_step_pub_duo(hipStream_t s, DeviceState& d, const ScanTables& scan, const FastHandoff& fh, const NoiseD& qt,
+                         const ObserveExtras& ex, const PubTables& pub, const ParticleRange& range = ParticleRange());
 extern int g_observe_nv;
 // dynamic LDS of the general ML instance of k_observe (per-particle chains first[Lp], next[B], ids[B]) and of
 // k_assoc_brute (best[B] u64 + bid[B]): callers check them against kMaxDynLds BEFORE anything is enqueued
@@ -567,9 +624,9 @@ void launch_probe(hipStream_t s, const double* in_dev, double* out_dev);
 // maximum-likelihood association -- or takes supplied ids --, the EKF updates in scan order and the log-weight.
 // update = false: association only (ids_out_dev), no state is touched.
 size_t dense_lds_bytes(int Lp, int B);
-void launch_observe_dense(hipStream_t s, DeviceState& d, const double* blobs_dev, const double* blobdir_dev, int B,
-                          const int32_t* ids_in_dev, int32_t* ids_out_dev, const double Qt[16], bool update,
-                          const ObserveExtras& ex);
+// scan: B, blobs and dir alone.  ids_in_dev: [B] supplied ids shared by all particles, or NULL; ids_out_dev: [P][B] or NULL
+void launch_observe_dense(hipStream_t s, DeviceState& d, const ScanTables& scan, const int32_t* ids_in_dev, int32_t* ids_out_dev,
+                          const double Qt[16], bool update, const ObserveExtras& ex);
 void launch_probe_dense(hipStream_t s, const double* in_dev, double* out_dev);
 // sharded resample
 // record header in front of the map slot: x, y, h, logw, slot_lo, slot_hi (the last two int64:
