@@ -206,7 +206,8 @@ int pk_measurement_model(const pk_filter* f, int32_t* model);
  *   PK_ERR_INVALID      another num_blobs than the ranges were named for;
  *   PK_ERR_UNSUPPORTED  a filter that is not on PK_MODEL_BEARING; the dense layout (the bearing model's own refusal); growing maps
  *                       (pk_grow_enable: a new landmark is still placed from two bearings);
- * and pk_propose / pk_propose_odom refuse them with PK_ERR_UNSUPPORTED before anything else (the proposal samples from the bearings).
+ * and pk_propose / pk_propose_odom refuse them with PK_ERR_UNSUPPORTED before anything else (the proposal samples from the bearings)
+ * unless pk_proposal_ranges has switched ranges into the proposal.
  * pk_scan_ranges_state: *armed = the num_blobs of the armed ranges (0: none), *staged = that of a staged scan that was given ranges
  * (0: none); either pointer may be NULL. */
 int pk_scan_ranges(pk_filter* f, const double* ranges, const double* variances, int32_t num_blobs);
@@ -648,6 +649,23 @@ int pk_propose(pk_filter* f, double v, double w, double dt, const double* z, uin
 int pk_propose_odom(pk_filter* f, const double delta[3], const double alpha[4], const double* z, uint64_t seed, uint64_t draw,
                     const double* blobs, int32_t num_blobs, const int32_t* ids, int32_t fresh, int32_t* ids_out);
 int pk_proposal_download(pk_filter* f, double* xi, double* dlogw, int32_t* used);
+
+/* Ranges in the proposal ("Ranges in the proposal"): an opt-in mode of pk_propose / pk_propose_odom.  Off (the
+ * default) they refuse armed ranges (pk_scan_ranges) as ever.  On, with nothing armed, they do what they did, bit for bit; with ranges
+ * armed they consume them -- pk_scan_ranges' own refusals first (num_blobs, the model, the dense layout, growing maps), then the
+ * proposal's; a refused call changes nothing and the ranges are gone -- and the rule above becomes, for a blob with a finite range
+ * (rho, q_rho); a blob without one (NaN) is handled exactly as above, blob by blob:
+ *   3. association at x^ by the range kernels (the density at the measured point); a tentative id of a ranged blob is settled there too;
+ *   4. r^ = sqrt(q), nu = (wrap(beta - (atan2(dy, dx) - h^)), rho - r^), h_x = [[dy / q, -dx / q, -1], [-dx / r^, -dy / r^, 0]],
+ *      h_m = [[-dy / q, dx / q], [dx / r^, dy / r^]] (all 0 at q = 0), S2 = h_m P h_m' + diag(Q00, q_rho), A (2 x 3) with rows
+ *      s . (G' h_x); Lambda += A' S2^-1 A, eta += A' S2^-1 nu, c += nu' S2^-1 nu, l += log det S2, kappa and n as above, n_rho += 1;
+ *   5. dlogw = -(2 n + n_rho / 2) log 2 pi - ... as above: the Gaussian marginal of the stacked innovations, 1 x 1 and 2 x 2 blocks;
+ *   7. the update at the sampled pose takes the range-bearing EKF (pk_scan_ranges' update) for a ranged blob.
+ * A scan in which some blob has a range takes k_propose_range and k_observe_proposed_range and may grow the per-scan block by 32
+ * bytes a blob, as in pk_observe; an armed scan without a finite range stages, launches and computes what the unarmed call does.
+ * pk_proposal_ranges_state: *on = 1 or 0. */
+int pk_proposal_ranges(pk_filter* f, int32_t on);
+int pk_proposal_ranges_state(const pk_filter* f, int32_t* on);
 
 /* ---- sharded (multi-GPU) resampling: see DESIGN.md section 6 -------------------
  * Particles are sharded contiguously over one process per GPU; global particle index =

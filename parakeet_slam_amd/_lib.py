@@ -124,6 +124,8 @@ SIGNATURES = {
     "pk_propose": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_int32, _ip]),
     "pk_propose_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_int32, _ip]),
     "pk_proposal_download": (C.c_int, [_h, _dp, _dp, _ip]),
+    "pk_proposal_ranges": (C.c_int, [_h, C.c_int32]),
+    "pk_proposal_ranges_state": (C.c_int, [_h, C.POINTER(C.c_int32)]),
     "pk_motion_odom_range": (C.c_int, [_h, _dp, _dp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64]),
     "pk_step_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_double, C.c_int32, C.c_double]),
     "pk_shard_max_logw": (C.c_int, [_h, _dp]),
@@ -418,6 +420,17 @@ class DeviceFilter(object):
         xi, dl, used = np.empty((self.P, 3)), np.empty(self.P), np.empty(self.P, dtype=np.int32)
         check(self._lib.pk_proposal_download(self._h, dptr(xi), dptr(dl), iptr(used)))
         return xi, dl, used
+
+    def proposal_ranges(self, on=True):
+        """Ranges in the proposal (pk_proposal_ranges): on, propose / propose_odom consume the ranges scan_ranges armed -- a ranged
+        blob enters the sampling, the weight and the update as a (bearing, range) measurement -- instead of refusing them."""
+        check(self._lib.pk_proposal_ranges(self._h, 1 if on else 0))
+
+    def proposal_ranges_state(self):
+        """Whether propose / propose_odom take armed ranges: pk_proposal_ranges_state."""
+        on = C.c_int32(0)
+        check(self._lib.pk_proposal_ranges_state(self._h, C.byref(on)))
+        return bool(on.value)
 
     def download_log_weights(self):
         out = np.empty(self.P, dtype=np.float64)

@@ -45,8 +45,12 @@ def _blob_row(blob):
     return np.array([blob.bearing, blob.color.r, blob.color.g, blob.color.b], dtype=np.float64)
 
 
-def _check_range_noise(range_noise, measurement_model, proposal, new_landmarks, who="FastSLAM"):
-    """range_noise=(sigma0, sigma1) of FastSLAM: None, or the two floats of a range's standard deviation sigma0 + sigma1 rho."""
+def _check_range_noise(range_noise, measurement_model, proposal, new_landmarks, who="FastSLAM", proposal_ranges=False):
+    """range_noise=(sigma0, sigma1) of FastSLAM: None, or the two floats of a range's standard deviation sigma0 + sigma1 rho.
+    proposal_ranges=True: ranges enter the measurement-informed proposal -- it needs both range_noise and proposal='measurement'."""
+    if proposal_ranges and (range_noise is None or proposal != "measurement"):
+        raise ValueError("%s(proposal_ranges=True): ranges in the proposal need range_noise=(sigma0, sigma1) and "
+                         "proposal='measurement'" % who)
     if range_noise is None:
         return None
     try:
@@ -61,9 +65,9 @@ def _check_range_noise(range_noise, measurement_model, proposal, new_landmarks, 
     if measurement_model != "bearing":
         raise ValueError("%s(range_noise=...): per-blob ranges are an option of measurement_model='bearing'; the reference model "
                          "has no range" % who)
-    if proposal == "measurement":
+    if proposal == "measurement" and not proposal_ranges:
         raise ValueError("%s(range_noise=..., proposal='measurement'): the measurement-informed proposal samples the pose from the "
-                         "bearings alone; ranges go with proposal='motion'" % who)
+                         "bearings alone; ranges go with proposal='motion', or enter the proposal with proposal_ranges=True" % who)
     if new_landmarks:
         raise ValueError("%s(range_noise=..., new_landmarks=True): a growing map still places a new landmark from two bearings; "
                          "ranges go with a preset map" % who)
@@ -678,6 +682,12 @@ class FastSLAM(object):
     of one colour on one ray are told apart, and a landmark's depth no longer waits for parallax.  The pose estimate does not gain
     by it on the drives measured.  With range_noise=None a (B, 5) array is a ValueError, and a ``range`` attribute of message objects
     is IGNORED.  Ranges are not state: snapshots do not change.
+
+    proposal_ranges=True (default False; with proposal="measurement" and range_noise=(sigma0, sigma1)): the ranges enter the
+    measurement-informed proposal (pk_proposal_ranges; DESIGN.md section 4, "Ranges in the proposal") -- a ranged blob is associated
+    at its measured point at the predicted pose and conditions the pose draw, the weight and the update as the 2-D measurement
+    (bearing, range); a blob without a range is the bearing-only proposal's, blob by blob.  Without it range_noise and
+    proposal="measurement" stay a ValueError; with it and no range_noise, or with proposal="motion", it is one too.
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -695,7 +705,8 @@ class FastSLAM(object):
         ba.apply_defaults()
         a = ba.arguments
         _check_landmark_init(a["landmark_init"], a["min_parallax"], a["new_landmarks"])
-        _check_range_noise(a["range_noise"], a["measurement_model"], a["proposal"], a["new_landmarks"])
+        _check_range_noise(a["range_noise"], a["measurement_model"], a["proposal"], a["new_landmarks"],
+                           proposal_ranges=bool(a["proposal_ranges"]))
         devices = a.get("devices")
         if devices is not None and len(list(devices)) > 1:
             from .multi import ShardedFastSLAM
@@ -740,11 +751,13 @@ class FastSLAM(object):
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
                  odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion",
-                 landmark_init="reference", min_parallax=0.2, range_noise=None):
+                 landmark_init="reference", min_parallax=0.2, range_noise=None, proposal_ranges=False):
         self._landmark_init, self._min_parallax = _check_landmark_init(landmark_init, min_parallax, new_landmarks)
         if measurement_model not in _lib.MEASUREMENT_MODELS:
             raise ValueError("FastSLAM(measurement_model=%r): 'reference' (default) or 'bearing'" % (measurement_model,))
-        self._range_noise = _check_range_noise(range_noise, measurement_model, proposal, new_landmarks)
+        self._range_noise = _check_range_noise(range_noise, measurement_model, proposal, new_landmarks,
+                                               proposal_ranges=bool(proposal_ranges))
+        self._proposal_ranges = bool(proposal_ranges)
         if proposal not in ("motion", "measurement"):
             raise ValueError("FastSLAM(proposal=%r): 'motion' (default) or 'measurement'" % (proposal,))
         if proposal == "measurement" and measurement_model != "bearing":
@@ -784,6 +797,8 @@ class FastSLAM(object):
         self._filter = _lib.DeviceFilter(self.num_particles, L + self._spare, device=self._device)
         if self._model != "reference":
             self._filter.set_measurement_model(self._model)
+        if self._proposal_ranges:
+            self._filter.proposal_ranges(True)
         if L + self._spare:
             means = np.zeros((L + self._spare, 5))
             covs = np.tile(np.identity(5).reshape(25), (L + self._spare, 1))
@@ -1034,8 +1049,14 @@ class FastSLAM(object):
         change: a plain observe."""
         with self._lock:
             scan = ros_view.last_sensor_reading
-            blobs = _blob_matrix(_scan_with_ranges(scan.observes, None)[0])  # (a (B, 5) scan is refused: no range_noise here)
+            # (without proposal_ranges a (B, 5) scan is refused: no range_noise here)
+            observes, ranges = _scan_with_ranges(scan.observes, self._range_noise if self._proposal_ranges else None)
+            blobs = _blob_matrix(observes)
             self._filter.set_measurement_noise(self.Qt)
+            if ranges is not None and len(blobs) and not np.isnan(ranges).all():
+                # the one call below consumes them (pk_scan_ranges, pk_proposal_ranges); the variances are formed as cam_cb forms them
+                sigma = self._range_noise[0] + self._range_noise[1] * ranges
+                self._filter.scan_ranges(ranges, sigma * sigma)
             fresh = self._threshold is None
             want = self._proposal_ids
             z = None

@@ -1028,8 +1028,10 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
 
 // A proposal step's scan (pk_api_propose.hip) on the device, ahead of k_propose: supplied ids as pk_observe uploads them -- the block
 // ctl | blobs | first | next, and behind it the id row itself -- or the bearing model's association at the live (predicted) poses,
-// which leaves tentative ids in ids_dev and touches no state.  The caller has checked the blobs, the ids and the filter.
-int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out) {
+// which leaves tentative ids in ids_dev and touches no state.  The caller has checked the blobs, the ids and the filter.  rs: the
+// ranges the step took (pk_proposal_ranges), staged as pk_observe stages them -- a scan without a finite range stages the bytes
+// it always staged.
+int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out, const RangeScan* rs) {
   int rc;
   *out = ProposalScan();
   f->ct_updated = true;
@@ -1037,7 +1039,8 @@ int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* i
     if ((rc = ct_end(f))) return rc;
     f->staged.valid = false;
     KnownScan ks;
-    if ((rc = upload_known_scan(f, blobs, B, ids, true, &ks))) return rc;
+    if ((rc = upload_known_scan(f, blobs, B, ids, true, &ks, rs))) return rc;
+    if (ks.o_rng) out->rng = reinterpret_cast<const double*>(f->scan_dev + ks.o_rng);
     f->gmax_fused = false;
     out->scan = known_scan_tables(f, ks, B);
     out->known = known_chains(f, ks);
@@ -1046,10 +1049,11 @@ int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* i
     return PK_OK;
   }
   AssocLaunch al;
-  if ((rc = enqueue_association(f, blobs, B, false, false, &al, false, true))) return rc;
+  if ((rc = enqueue_association(f, blobs, B, false, false, &al, false, true, rs))) return rc;
   if (al.plan.onepass()) return fail(PK_ERR_UNSUPPORTED, "pk_propose: the scan did not take the general association");
   if ((rc = ct_end(f))) return rc;
   out->scan = al.scan;
+  out->rng = al.scan.rng;
   out->ids = f->ids_dev;
   return PK_OK;
 }

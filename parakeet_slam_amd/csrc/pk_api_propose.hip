@@ -2,7 +2,8 @@
 // proposal"): one move plus one observe in which every particle's pose is drawn from the motion model CONDITIONED on the scan
 // (FastSLAM 2.0).  Host orchestration only: the kernels are the motion kernels as they stand (twice: with zero normals for the
 // predicted pose, with k_propose's normals for the sampled one), the bearing model's association, k_propose (pk_k_propose.hip)
-// and k_observe_proposed (pk_k_observe.hip).
+// and k_observe_proposed (pk_k_observe.hip) -- for a scan with ranged blobs (pk_proposal_ranges) the range association,
+// k_propose_range and k_observe_proposed_range.
 #include "pk_filter.hpp"
 
 namespace {
@@ -53,7 +54,14 @@ int copy_poses(pk_filter* f, bool save) {
 int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const double* z, uint64_t seed, uint64_t draw,
                  const double* blobs, int32_t B, const int32_t* ids, bool fresh, int32_t* ids_out) {
   int rc;
-  if ((rc = refuse_ranges_proposal(f, who))) return rc;  // (armed ranges, pk_scan_ranges: refused and gone)
+  // armed ranges (pk_scan_ranges): refused and gone -- or, with pk_proposal_ranges on, consumed here whatever follows, with the
+  // range scans' own refusals ahead of the proposal's
+  RangeScan rs;
+  if (!f->prop.ranges) {
+    if ((rc = refuse_ranges_proposal(f, who))) return rc;
+  } else if ((rc = ranges_take(f, who, B, &rs))) {
+    return rc;
+  }
   if ((rc = refuse_proposal(f, who))) return rc;
   if (B < 0 || (B > 0 && !blobs)) return fail(PK_ERR_INVALID, "%s: bad blobs", who);
   if (!f->map_loaded) return fail(PK_ERR_STATE, "%s: no map uploaded (pk_upload_map)", who);
@@ -101,12 +109,13 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
     move(q.zero, nullptr);
   }
   ProposalScan sc;
-  rc = proposal_scan(f, blobs, B, ids, &sc);  // (the association, in its own span)
+  rc = proposal_scan(f, blobs, B, ids, &sc, &rs);  // (the association, in its own span)
   if (!rc) {
     Span t(f, PK_T_PROPOSE);
     ProposeLaunch pl;
     pl.blobs_dev = sc.scan.blobs;
     pl.blobdir_dev = sc.scan.dir;
+    pl.rng_dev = sc.rng;
     pl.B = B;
     pl.ids_dev = sc.ids;
     pl.ids_shared = ids != nullptr;
@@ -137,6 +146,7 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
     ex.model = PK_MODEL_BEARING;
     ex.gmax_key = ctl_gmax_key(f);
     ex.dlogw = q.dlogw;
+    ex.rng = sc.rng;
     if (ids)
       launch_observe(f->stream, f->d, sc.scan, sc.known, f->qt, ex);
     else
@@ -176,6 +186,18 @@ int pk_propose_odom(pk_filter* f, const double delta[3], const double alpha[4], 
   if (int rc = pk_odom_sigmas(delta, alpha, m.sigma)) return rc;  // before anything moves
   memcpy(m.delta, delta, sizeof(m.delta));
   return propose_impl(f, "pk_propose_odom", m, z, seed, draw, blobs, num_blobs, ids, fresh != 0, ids_out);
+}
+
+int pk_proposal_ranges(pk_filter* f, int32_t on) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_proposal_ranges: NULL handle");
+  f->prop.ranges = on != 0;
+  return PK_OK;
+}
+
+int pk_proposal_ranges_state(const pk_filter* f, int32_t* on) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_proposal_ranges_state: NULL handle");
+  if (on) *on = f->prop.ranges ? 1 : 0;
+  return PK_OK;
 }
 
 int pk_proposal_download(pk_filter* f, double* xi, double* dlogw, int32_t* used) {

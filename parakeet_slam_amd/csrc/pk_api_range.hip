@@ -9,8 +9,9 @@
 //   2. a filter that is not on PK_MODEL_BEARING                                         PK_ERR_UNSUPPORTED
 //   3. the dense layout: the bearing model's own refusal, in its own words              PK_ERR_UNSUPPORTED
 //   4. growing maps (pk_grow_enable)                                                    PK_ERR_UNSUPPORTED
-// pk_propose / pk_propose_odom refuse armed ranges before anything else (refuse_ranges_proposal).  Nothing has changed when one of
-// them answers, except that the ranges are gone.
+// pk_propose / pk_propose_odom refuse armed ranges before anything else (refuse_ranges_proposal) -- unless pk_proposal_ranges is on:
+// then they consume them (ranges_take), these refusals ahead of the proposal's own.  Nothing has changed when one of them answers,
+// except that the ranges are gone.
 int refuse_ranges(const pk_filter* f, const char* who, int32_t B, int32_t armed_B) {
   if (B != armed_B)
     return fail(PK_ERR_INVALID, "%s: pk_scan_ranges named the ranges of a scan of %d blobs, this one has %d", who, (int)armed_B, (int)B);
@@ -51,7 +52,7 @@ int refuse_ranges_proposal(pk_filter* f, const char* who) {
   if (!f || !f->rng.armed) return PK_OK;
   ranges_disarm(f);
   return fail(PK_ERR_UNSUPPORTED, "%s: per-blob ranges (pk_scan_ranges) are not part of the measurement-informed proposal: it samples "
-                                  "the pose from the bearings alone", who);
+                                  "the pose from the bearings alone unless pk_proposal_ranges(f, 1) switches them in", who);
 }
 
 extern "C" {

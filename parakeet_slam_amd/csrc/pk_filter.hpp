@@ -389,6 +389,7 @@ struct pk_filter {
     double* dlogw = nullptr;        // [P] its weight increments
     int32_t* used = nullptr;        // [P] the matches it used
     bool valid = false;             // the last call's results are there (pk_proposal_download)
+    bool ranges = false;            // pk_proposal_ranges: armed ranges (pk_scan_ranges) are consumed by the step, not refused
   } prop;
   int32_t* anc = nullptr;           // P
   unsigned char* slot_tmp = nullptr;  // one slot
@@ -545,13 +546,15 @@ void blob_directions(const double* blobs, int B, double* dir);
 int stage_ml_scan(pk_filter* f, const double* blobs, int B, const RangeScan* rs = nullptr);
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out, bool reset);
 // a proposal step's scan on the device (pk_api_propose.hip): where its parts lie.  known: supplied ids' chains (the ids are
-// final); scan.dir: the rays that settle tentative ids; ids: one row of B (supplied) or ids_dev's [P][B]
+// final); scan.dir: the rays that settle tentative ids; ids: one row of B (supplied) or ids_dev's [P][B]; rng: the range rows
+// ([B][2], scan order) of a scan in which some blob has a range (rs->any), else NULL
 struct ProposalScan {
   ScanTables scan;
   KnownChains known;
   int32_t* ids = nullptr;
+  const double* rng = nullptr;
 };
-int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out);
+int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out, const RangeScan* rs = nullptr);
 void proposal_observed(pk_filter* f, bool known);
 // what the bearing model (pk_set_measurement_model) has no kernels for, refused while it is on (a NULL handle passes)
 int refuse_bearing(const pk_filter* f, const char* who, const char* what);
@@ -562,7 +565,7 @@ int refuse_ranges(const pk_filter* f, const char* who, int32_t B, int32_t armed_
 int ranges_take(pk_filter* f, const char* who, int32_t B, RangeScan* out);
 int ranges_check(pk_filter* f, const char* who, int32_t B);
 void ranges_disarm(pk_filter* f);
-int refuse_ranges_proposal(pk_filter* f, const char* who);
+int refuse_ranges_proposal(pk_filter* f, const char* who);  // (only while pk_proposal_ranges is off)
 // pk_api_shard.hip
 int refuse_balanced(const pk_filter* f, const char* who);
 int refuse_path(const pk_filter* f, const char* who);

@@ -53,6 +53,7 @@ struct ObserveArgs {
 // RANGE (k_observe_range, bearing model): a blob with a finite range is settled and applied as a range-bearing measurement
 // (pk_range_math.hpp); one without takes the bearing model's path, decided blob by blob.  Each lane walks its OWN landmark's chain,
 // so the choice is per lane: a wave whose lanes hold ranged and unranged blobs at the same chain position runs both paths in turn.
+// SETTLED and RANGE together (k_observe_proposed_range): k_propose_range settled the ids; a ranged blob takes ekf_update_range.
 template <bool KNOWN, int MODEL = kModelReference, bool SETTLED = false, bool RANGE = false>
 __device__ __forceinline__ double apply_blobs(Landmark<double>& lm, int l, double sx, double sy,
                                               const ObserveArgs& a, const int32_t* first,
@@ -266,6 +267,11 @@ template <bool KNOWN, int NV>
 __global__ void __launch_bounds__(kObsThreads) k_observe_proposed(ObserveArgs a, const double* dlogw) {
   observe_body<KNOWN, NV, kModelBearing, true>(a, dlogw);
 }
+// ... behind k_propose_range: the settled ids are final, a ranged blob updates its landmark with ekf_update_range
+template <bool KNOWN, int NV>
+__global__ void __launch_bounds__(kObsThreads) k_observe_proposed_range(ObserveArgs a, const double* dlogw) {
+  observe_body<KNOWN, NV, kModelBearing, true, true>(a, dlogw);
+}
 
 
 // ------------------------------------------------------------------ K3 (known ids, one sighting per landmark)
@@ -345,12 +351,19 @@ static void observe_launch(hipStream_t s, DeviceState& d, const ScanTables& scan
   a.B = B;
   a.P = d.P;
   a.qt = device_noise(qt);
-  static bool attr_set[kMaxDevices] = {false};  // the four instances that build their chains in LDS
-  allow_dynamic_lds(attr_set, kMaxDynLds, k_observe_proposed<false, 1>, k_observe_range<false, 1>, k_observe_bearing<false, 1>,
-                    k_observe<false, 1>, k_observe<false, 2>);
+  static bool attr_set[kMaxDevices] = {false};  // the instances that build their chains in LDS
+  allow_dynamic_lds(attr_set, kMaxDynLds, k_observe_proposed_range<false, 1>, k_observe_proposed<false, 1>, k_observe_range<false, 1>,
+                    k_observe_bearing<false, 1>, k_observe<false, 1>, k_observe<false, 2>);
   // (behind a one-pass kernel few particles, if any, are flagged: 4 096 workgroups walk the flags)
   const unsigned grid = (unsigned)(ex.only_flagged && d.P > 4096 ? 4096 : d.P);
-  if (ex.dlogw) {  // behind k_propose (bearing model): the same two shapes
+  if (ex.dlogw && ex.rng) {  // behind k_propose_range: a proposal step's scan with ranged blobs
+    if (ids_dev == nullptr) {
+      hipLaunchKernelGGL((k_observe_proposed_range<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a, ex.dlogw);
+    } else {
+      const size_t lds = observe_general_lds_bytes(d.lay.Lp, B);  // <= kMaxDynLds: checked by the caller
+      hipLaunchKernelGGL((k_observe_proposed_range<false, 1>), dim3(grid), dim3(kObsThreads), lds, s, a, ex.dlogw);
+    }
+  } else if (ex.dlogw) {  // behind k_propose (bearing model): the same two shapes
     if (ids_dev == nullptr) {
       hipLaunchKernelGGL((k_observe_proposed<true, 2>), dim3(grid), dim3(kObsThreads), 0, s, a, ex.dlogw);
     } else {

@@ -238,7 +238,8 @@ struct ObserveExtras {
   const double* rng = nullptr;                  // launch_observe, bearing model: the scan's range rows ([B][2] range, variance, scan order;
                                                 //   pk_scan_ranges) -- set only when some blob has a range: k_observe_range
   const double* dlogw = nullptr;                // launch_observe, bearing model: k_observe_proposed -- the ids are FINAL (k_propose settled
-                                                //   them) and the log-weight takes dlogw[p], not the updates' own importance factors
+                                                //   them) and the log-weight takes dlogw[p], not the updates' own importance factors;
+                                                //   with rng set as well: k_observe_proposed_range
 };
 // The colour table (pk_k_colour.hip): tab[k][6][Lp], rows crr crg crb cgg cgb cbb as in a slot -- landmark l's
 // colour block after k updates from the one pk_upload_map broadcast (base[6][Lp]; the uploaded counts are 0, so a landmark's level is
@@ -284,6 +285,8 @@ void launch_observe(hipStream_t s, DeviceState& d, const ScanTables& scan, int32
 struct ProposeLaunch {
   const double* blobs_dev = nullptr;
   const double* blobdir_dev = nullptr;  // NULL: the ids are final
+  const double* rng_dev = nullptr;      // the scan's range rows ([B][2] range, variance, scan order; pk_proposal_ranges) -- set only
+                                        //   when some blob has a range: k_propose_range
   int B = 0;
   int32_t* ids_dev = nullptr;           // [P][B], or one row of B for every particle (ids_shared; not written)
   bool ids_shared = false;

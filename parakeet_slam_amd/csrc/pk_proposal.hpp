@@ -6,12 +6,17 @@
 // innovation nu with variance sigma^2 and the row a = s (.) (G' h_x): nu(xi) ~ nu - a' xi.  The sums below are all a particle needs:
 //   Lambda = I + sum a a' / sigma^2,  eta = sum a nu / sigma^2,  c = sum nu^2 / sigma^2,  ell = sum log sigma^2,
 //   kappa = sum log det(C + Qc) + d_c' (C + Qc)^-1 d_c,  n = matches,  low = blobs that weigh log 0.1
+//
+// A match of a blob that carries a range (pk_proposal_ranges; DESIGN.md section 4, "Ranges in the proposal") gives the 2-vector
+// nu = (bearing, range) with the 2 x 2 variance S2 and the 2 x 3 block A, rows s (.) (G' h_x): Lambda += A' S2^-1 A, eta += A' S2^-1 nu,
+// c += nu' S2^-1 nu, ell += log det S2, and a fifteenth sum n_rho counts them (the density's constant).
 #pragma once
 #include "pk_math.hpp"
 
 namespace pk {
 
-constexpr int kProposeSums = 14;  // the members of ProposalSums: what a workgroup reduces per particle
+constexpr int kProposeSums = 14;       // the members of ProposalSums: what k_propose reduces per particle
+constexpr int kProposeSumsRange = 15;  // ... and k_propose_range: n_rho, the matches that carried a range, beside them
 
 // G = d pose / d (s (.) xi) at xi = 0, by columns, from the predicted heading and the control alone.
 //   twist (motion_model):    h1 = h^ - w dt / 2, ds = v dt:  (cos h1, sin h1, 0), (-ds sin h1, ds cos h1, 1), (0, 0, 1)
@@ -101,11 +106,71 @@ __device__ __forceinline__ void proposal_match(ProposalSums& S, const Landmark<d
   S.n += 1.0;
 }
 
+// The same for a blob with the range rho of variance qr: the 2-D measurement (bearing, range) of ekf_update_range.
+//   h_x = [[dy / q, -dx / q, -1], [-dx / r, -dy / r, 0]],  h_m = [[-dy / q, dx / q], [dx / r, dy / r]],  r = sqrt(q); all zero at q = 0
+//   S2 = h_m Sigma_xy h_m' + diag(q00, qr), inverted in closed form
+__device__ __forceinline__ void proposal_match_range(ProposalSums& S, double& nrho, const Landmark<double>& f, double sx, double sy, double sh,
+                                                     const BlobT<double>& z, double rho, double qr, const Noise<double>& qt,
+                                                     const NoiseJacobian& G, double s0, double s1, double s2) {
+  const double dx = f.mx - sx, dy = f.my - sy;
+  const double q = dx * dx + dy * dy;
+  const double rhat = sqrt(q);
+  const double nb = wrap_angle(z.bearing - (pk_atan2(dy, dx) - sh));
+  const double nr = rho - rhat;
+  double hb0 = 0.0, hb1 = 0.0, hb2 = 0.0, hr0 = 0.0, hr1 = 0.0;  // h_x: the bearing's row, the range's (its third entry is 0)
+  if (q != 0.0) {
+    const double iq = 1.0 / q, ir = 1.0 / rhat;
+    hb0 = dy * iq;
+    hb1 = -(dx * iq);
+    hb2 = -1.0;
+    hr0 = -(dx * ir);
+    hr1 = -(dy * ir);
+  }
+  const double mb0 = -hb0, mb1 = -hb1, mr0 = -hr0, mr1 = -hr1;  // h_m
+  const double pb0 = f.pxx * mb0 + f.pxy * mb1, pb1 = f.pxy * mb0 + f.pyy * mb1;
+  const double pr0 = f.pxx * mr0 + f.pxy * mr1, pr1 = f.pxy * mr0 + f.pyy * mr1;
+  const double s00 = mb0 * pb0 + mb1 * pb1 + qt.q00;
+  const double s01 = mb0 * pr0 + mb1 * pr1;
+  const double s11 = mr0 * pr0 + mr1 * pr1 + qr;
+  const double dets = s00 * s11 - s01 * s01;
+  const double idet = 1.0 / dets;
+  const double i00 = s11 * idet, i01 = -(s01 * idet), i11 = s00 * idet;  // S2^-1
+  // A: the bearing's row ab, the range's row ar
+  const double ab0 = s0 * (G.g[0][0] * hb0 + G.g[0][1] * hb1 + G.g[0][2] * hb2);
+  const double ab1 = s1 * (G.g[1][0] * hb0 + G.g[1][1] * hb1 + G.g[1][2] * hb2);
+  const double ab2 = s2 * (G.g[2][0] * hb0 + G.g[2][1] * hb1 + G.g[2][2] * hb2);
+  const double ar0 = s0 * (G.g[0][0] * hr0 + G.g[0][1] * hr1);
+  const double ar1 = s1 * (G.g[1][0] * hr0 + G.g[1][1] * hr1);
+  const double ar2 = s2 * (G.g[2][0] * hr0 + G.g[2][1] * hr1);
+  // S2^-1 A by rows: cb, cr
+  const double cb0 = i00 * ab0 + i01 * ar0, cb1 = i00 * ab1 + i01 * ar1, cb2 = i00 * ab2 + i01 * ar2;
+  const double cr0 = i01 * ab0 + i11 * ar0, cr1 = i01 * ab1 + i11 * ar1, cr2 = i01 * ab2 + i11 * ar2;
+  S.l00 += ab0 * cb0 + ar0 * cr0;
+  S.l01 += ab0 * cb1 + ar0 * cr1;
+  S.l02 += ab0 * cb2 + ar0 * cr2;
+  S.l11 += ab1 * cb1 + ar1 * cr1;
+  S.l12 += ab1 * cb2 + ar1 * cr2;
+  S.l22 += ab2 * cb2 + ar2 * cr2;
+  S.e0 += cb0 * nb + cr0 * nr;
+  S.e1 += cb1 * nb + cr1 * nr;
+  S.e2 += cb2 * nb + cr2 * nr;
+  S.c += (i00 * nb * nb + 2.0 * i01 * nb * nr) + i11 * nr * nr;
+  S.ell += log_few_ulp(dets);
+  double detc;
+  const Sym3<double> qci =
+      sym3_inverse(Sym3<double>{f.crr + qt.rr, f.crg + qt.rg, f.crb + qt.rb, f.cgg + qt.gg, f.cgb + qt.gb, f.cbb + qt.bb}, detc);
+  S.kappa += log_few_ulp(detc) + sym3_quad(qci, z.r - f.mr, z.g - f.mg, z.b - f.mb);
+  S.n += 1.0;
+  nrho += 1.0;
+}
+
 // The particle's normals xi = m + R^-T z and its weight increment from the reduced sums: Lambda = I + sum = R R' (Cholesky, R lower),
 // m = Lambda^-1 eta.  delta = -2 n log 2 pi - (ell + log det Lambda) / 2 - (c - eta' m) / 2 - kappa / 2 + low log 0.1: the Gaussian
 // marginal of the stacked innovations (Woodbury, the determinant lemma).  No settled match: xi = z, bit for bit.
+// RANGE: every ranged match stacks one more innovation -- the constant is -(2 n + n_rho / 2) log 2 pi.
+template <bool RANGE = false>
 __device__ __forceinline__ double proposal_finish(const ProposalSums& S, double z0, double z1, double z2, double& x0, double& x1,
-                                                  double& x2) {
+                                                  double& x2, double nrho = 0.0) {
   const double low = S.low * Consts<double>::log_no_match;
   if (S.n == 0.0) {
     x0 = z0;
@@ -133,6 +198,8 @@ __device__ __forceinline__ double proposal_finish(const ProposalSums& S, double 
   x2 = m2 + t2;
   const double logdet = 2.0 * log_few_ulp(r00 * r11 * r22);
   const double etam = y0 * y0 + y1 * y1 + y2 * y2;  // eta' Lambda^-1 eta
+  if constexpr (RANGE)
+    return -(2.0 * S.n + 0.5 * nrho) * Consts<double>::log_two_pi - 0.5 * (S.ell + logdet) - 0.5 * (S.c - etam) - 0.5 * S.kappa + low;
   return -2.0 * S.n * Consts<double>::log_two_pi - 0.5 * (S.ell + logdet) - 0.5 * (S.c - etam) - 0.5 * S.kappa + low;
 }
 
