@@ -205,7 +205,7 @@ int pk_measurement_model(const pk_filter* f, int32_t* model);
  * While ranges are armed (or staged) the consuming call refuses, in this order, changes nothing, and the ranges are gone:
  *   PK_ERR_INVALID      another num_blobs than the ranges were named for;
  *   PK_ERR_UNSUPPORTED  a filter that is not on PK_MODEL_BEARING; the dense layout (the bearing model's own refusal); growing maps
- *                       (pk_grow_enable: a new landmark is still placed from two bearings);
+ *                       (pk_grow_enable: a new landmark is still placed from two bearings) unless pk_grow_ranges is on;
  * and pk_propose / pk_propose_odom refuse them with PK_ERR_UNSUPPORTED before anything else (the proposal samples from the bearings)
  * unless pk_proposal_ranges has switched ranges into the proposal.
  * pk_scan_ranges_state: *armed = the num_blobs of the armed ranges (0: none), *staged = that of a staged scan that was given ranges
@@ -322,6 +322,25 @@ int pk_grow_shape(const pk_filter* f, int32_t* preset_landmarks, int32_t* spare_
 #define PK_GROW_INIT_TRIANGULATED 1
 int pk_grow_init(pk_filter* f, int32_t mode, double min_parallax);
 int pk_grow_init_mode(const pk_filter* f, int32_t* mode, double* min_parallax);
+/* Ranged scans on a growing map ("Single-sighting initialisation"; off by default).  Off, armed ranges
+ * (pk_scan_ranges) are refused on a filter with pk_grow_enable, as ever.  On, that refusal steps aside (the others stay, in their
+ * order): pk_observe, pk_observe_fresh, pk_stage_scan + pk_observe_staged (which re-checks), pk_step, pk_step_adaptive and
+ * pk_step_odom consume the ranges.  Matched blobs are associated and updated as on a preset map (potential features update, weigh
+ * 0.1 and are promoted as ever), and the bookkeeping, per particle and unmatched blob in scan order, becomes: a blob with a finite
+ * range rho (variance q_rho), while a spare slot is free, is a potential feature in the next spare slot at once -- no search of the
+ * stored readings, nothing stored.  With (px, py, ph) the particle's pose, zb the bearing, (s, c) the sine and cosine of ph + zb and
+ * q00 = Qt[0][0] of the scan,
+ *     mean = (px + rho c, py + rho s, r, g, b)   (the blob's own colour),     a = rho^2 q00,
+ *     Pxx = q_rho c^2 + a s^2,   Pxy = (q_rho - a) c s,   Pyy = q_rho s^2 + a c^2,
+ * the colour block is the identity, the count word PK_LANDMARK_POTENTIAL, the slot id next_id (which advances).  Every other
+ * unmatched blob -- without a range, or ranged with every spare slot taken -- goes through the rule pk_grow_init selects, unchanged.
+ * A scan in which no blob has a finite range launches and computes what it would with the mode off, bit for bit.  The mode holds no
+ * per-particle state (pk_device_bytes, records, pack / adopt and the resample are what they were), may be switched between any two
+ * scans, and composes with pk_grow_retire unchanged.  pk_propose / pk_propose_odom and the split observe refuse growing maps as ever.
+ * PK_ERR_STATE without pk_grow_enable; PK_ERR_INVALID unless on is 0 or 1; nothing changed either way.
+ * pk_grow_ranges_state: *on = 1 or 0 (0 on a filter that never asked). */
+int pk_grow_ranges(pk_filter* f, int32_t on);
+int pk_grow_ranges_state(const pk_filter* f, int32_t* on);
 /* Growing maps that also shrink (the reference's hypothesis_set and potential_features only grow; off by default, and a filter
  * that never calls this does and holds what it did without it).  While a threshold is non-zero, one more kernel runs behind the
  * bookkeeping of every non-empty maximum-likelihood scan.  t counts those scans (uint32, wrapping; ages are differences modulo 2^32).

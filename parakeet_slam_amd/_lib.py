@@ -186,6 +186,8 @@ SIGNATURES = {
     "pk_grow_shape": (C.c_int, [_h, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pk_grow_init": (C.c_int, [_h, C.c_int32, C.c_double]),
     "pk_grow_init_mode": (C.c_int, [_h, C.POINTER(C.c_int32), _dp]),
+    "pk_grow_ranges": (C.c_int, [_h, C.c_int32]),
+    "pk_grow_ranges_state": (C.c_int, [_h, C.POINTER(C.c_int32)]),
     "pk_grow_retire": (C.c_int, [_h, C.c_int32, C.c_int32]),
     "pk_grow_clocks_download": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _up, _ip, _ip, _up]),
     "pk_grow_clocks_upload": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _up, _ip, _ip, _up]),
@@ -875,6 +877,18 @@ class DeviceFilter(object):
         m, a = C.c_int32(), C.c_double()
         check(self._lib.pk_grow_init_mode(self._h, C.byref(m), C.byref(a)))
         return {v: k for k, v in LANDMARK_INITS.items()}[int(m.value)], float(a.value)
+
+    def grow_ranges(self, on=True):
+        """Ranged scans on a growing map (pk_grow_ranges): on, the calls that take blobs consume the ranges scan_ranges armed, and an
+        unmatched blob with a range becomes a potential feature at once, at the measured point with its covariance; a blob without
+        one goes through grow_init's rule.  Off (the default), such a scan is refused as ever.  ``on`` is 0 or 1 (or a bool)."""
+        check(self._lib.pk_grow_ranges(self._h, int(on)))
+
+    def grow_ranges_state(self):
+        """Whether a growing map takes ranged scans: pk_grow_ranges_state."""
+        on = C.c_int32()
+        check(self._lib.pk_grow_ranges_state(self._h, C.byref(on)))
+        return bool(on.value)
 
     def grow_download(self, p0=0, p1=None, counters=True, readings=True, slot_ids=True):
         """(counters (n, 4) int32: readings stored / spare slots in use / next_id / readings dropped,

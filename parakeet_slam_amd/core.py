@@ -45,9 +45,15 @@ def _blob_row(blob):
     return np.array([blob.bearing, blob.color.r, blob.color.g, blob.color.b], dtype=np.float64)
 
 
-def _check_range_noise(range_noise, measurement_model, proposal, new_landmarks, who="FastSLAM", proposal_ranges=False):
+def _check_range_noise(range_noise, measurement_model, proposal, new_landmarks, who="FastSLAM", proposal_ranges=False,
+                       grow_ranges=False):
     """range_noise=(sigma0, sigma1) of FastSLAM: None, or the two floats of a range's standard deviation sigma0 + sigma1 rho.
-    proposal_ranges=True: ranges enter the measurement-informed proposal -- it needs both range_noise and proposal='measurement'."""
+    proposal_ranges=True: ranges enter the measurement-informed proposal -- it needs both range_noise and proposal='measurement'.
+    grow_ranges=True: ranges on a growing map -- it needs range_noise, new_landmarks=True and proposal='motion' (the spare slots and
+    the device bookkeeping are checked by _check_grow_ranges)."""
+    if grow_ranges and (range_noise is None or not new_landmarks or proposal == "measurement"):
+        raise ValueError("%s(grow_ranges=True): ranges on a growing map need range_noise=(sigma0, sigma1), new_landmarks=True and "
+                         "proposal='motion'" % who)
     if proposal_ranges and (range_noise is None or proposal != "measurement"):
         raise ValueError("%s(proposal_ranges=True): ranges in the proposal need range_noise=(sigma0, sigma1) and "
                          "proposal='measurement'" % who)
@@ -68,10 +74,18 @@ def _check_range_noise(range_noise, measurement_model, proposal, new_landmarks, 
     if proposal == "measurement" and not proposal_ranges:
         raise ValueError("%s(range_noise=..., proposal='measurement'): the measurement-informed proposal samples the pose from the "
                          "bearings alone; ranges go with proposal='motion', or enter the proposal with proposal_ranges=True" % who)
-    if new_landmarks:
+    if new_landmarks and not grow_ranges:
         raise ValueError("%s(range_noise=..., new_landmarks=True): a growing map still places a new landmark from two bearings; "
                          "ranges go with a preset map" % who)
     return s0, s1
+
+
+def _check_grow_ranges(grow_ranges, spare_landmarks, bookkeeping, who="FastSLAM"):
+    """grow_ranges=True beyond what _check_range_noise holds it to: the single-sighting rule is the device kernel's."""
+    if grow_ranges and not (int(spare_landmarks) > 0 and bookkeeping == "device"):
+        raise ValueError("%s(grow_ranges=True): a new landmark is placed from one ranged sighting by the device bookkeeping of a "
+                         "growing map (spare_landmarks > 0, bookkeeping='device'), not by bookkeeping='host'" % who)
+    return bool(grow_ranges)
 
 
 def _scan_with_ranges(observes, range_noise, who="FastSLAM"):
@@ -688,6 +702,14 @@ class FastSLAM(object):
     at its measured point at the predicted pose and conditions the pose draw, the weight and the update as the 2-D measurement
     (bearing, range); a blob without a range is the bearing-only proposal's, blob by blob.  Without it range_noise and
     proposal="measurement" stay a ValueError; with it and no range_noise, or with proposal="motion", it is one too.
+
+    grow_ranges=True (default False; with range_noise=(sigma0, sigma1), new_landmarks=True, spare_landmarks > 0, the device
+    bookkeeping and proposal="motion"): a growing map takes ranged scans (pk_grow_ranges; DESIGN.md section 9, "Single-sighting
+    initialisation").  Matched blobs are associated and updated as on a preset map; an unmatched blob with a range becomes a potential
+    feature at once, at its measured point with the covariance q_rho u u' + rho^2 Qt[0][0] n n', and stores no reading; one without a
+    range goes through ``landmark_init``'s rule.  Without it range_noise and new_landmarks=True stay a ValueError; with it, a missing
+    range_noise, a preset map, bookkeeping="host" or proposal="measurement" is one.  ``save_state`` writes the flag when it is set
+    and ``load_state`` takes it from the snapshot (one without it: off).  One GPU (the bearing model's).
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -706,7 +728,8 @@ class FastSLAM(object):
         a = ba.arguments
         _check_landmark_init(a["landmark_init"], a["min_parallax"], a["new_landmarks"])
         _check_range_noise(a["range_noise"], a["measurement_model"], a["proposal"], a["new_landmarks"],
-                           proposal_ranges=bool(a["proposal_ranges"]))
+                           proposal_ranges=bool(a["proposal_ranges"]), grow_ranges=bool(a["grow_ranges"]))
+        _check_grow_ranges(a["grow_ranges"], a["spare_landmarks"], a["bookkeeping"])
         devices = a.get("devices")
         if devices is not None and len(list(devices)) > 1:
             from .multi import ShardedFastSLAM
@@ -751,13 +774,14 @@ class FastSLAM(object):
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
                  odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion",
-                 landmark_init="reference", min_parallax=0.2, range_noise=None, proposal_ranges=False):
+                 landmark_init="reference", min_parallax=0.2, range_noise=None, proposal_ranges=False, grow_ranges=False):
         self._landmark_init, self._min_parallax = _check_landmark_init(landmark_init, min_parallax, new_landmarks)
         if measurement_model not in _lib.MEASUREMENT_MODELS:
             raise ValueError("FastSLAM(measurement_model=%r): 'reference' (default) or 'bearing'" % (measurement_model,))
         self._range_noise = _check_range_noise(range_noise, measurement_model, proposal, new_landmarks,
-                                               proposal_ranges=bool(proposal_ranges))
+                                               proposal_ranges=bool(proposal_ranges), grow_ranges=bool(grow_ranges))
         self._proposal_ranges = bool(proposal_ranges)
+        self._grow_ranges = _check_grow_ranges(grow_ranges, spare_landmarks, bookkeeping)
         if proposal not in ("motion", "measurement"):
             raise ValueError("FastSLAM(proposal=%r): 'motion' (default) or 'measurement'" % (proposal,))
         if proposal == "measurement" and measurement_model != "bearing":
@@ -828,6 +852,8 @@ class FastSLAM(object):
                 self._filter.grow_retire(*self._retire)
             if self._landmark_init != "reference":
                 self._filter.grow_init(self._landmark_init, self._min_parallax)
+            if self._grow_ranges:
+                self._filter.grow_ranges(True)
         else:
             self._nl_host = dict(
                 hyp=[[] for _ in range(P)],          # orphaned readings: (id, x, y, heading, bearing, r, g, b)  (:739-746)
@@ -1348,6 +1374,8 @@ class FastSLAM(object):
                 extra = _nl_snapshot(self._nl())
             if self._grow:
                 extra.update(landmark_init=np.array(self._landmark_init), min_parallax=np.float64(self._min_parallax))
+            if self._grow_ranges:  # (off: no field -- a snapshot without it restores as off)
+                extra["grow_ranges"] = np.bool_(True)
             if self._threshold is not None:  # the weights carry over: bit for bit, not through exp and log
                 extra["log_weights"] = self._filter.download_log_weights()
             if self._record_path:
@@ -1386,6 +1414,10 @@ class FastSLAM(object):
             if self._grow:  # (a snapshot from before the fields: the reference's rule)
                 init = _check_landmark_init(str(d["landmark_init"]) if "landmark_init" in d.files else "reference",
                                             float(d["min_parallax"]) if "min_parallax" in d.files else self._min_parallax, True, "snapshot")
+            ranged = bool(d["grow_ranges"]) if "grow_ranges" in d.files else False
+            if ranged and not (self._nl_device and self._range_noise is not None and self._proposal == "motion"):
+                raise ValueError("snapshot: taken with grow_ranges=True, which needs this filter's range_noise=(sigma0, sigma1), "
+                                 "new_landmarks=True with spare_landmarks > 0, bookkeeping='device' and proposal='motion'")
             have_path = self._record_path and "path_ancestors" in d.files
             if have_path:
                 n = d["path_ancestors"].shape[0]
@@ -1439,6 +1471,8 @@ class FastSLAM(object):
                 self._landmark_init, self._min_parallax = init
                 if self._nl_device:
                     self._filter.grow_init(*init)
+                    self._grow_ranges = ranged
+                    self._filter.grow_ranges(ranged)
             if have_nl and self._nl_device:
                 _, S, R = self._filter.grow_shape()
                 self._filter.grow_upload(0, P, *_nl_arrays_from_snapshot(d, P, self._L0, S, R))

@@ -1012,7 +1012,8 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   if (grow) {  // :92-95 for every particle, on the ids the association kernel left in HBM (every particle's slot is its own now)
     Span t(f, PK_T_OBSERVE);
     launch_new_landmarks(f->stream, f->d, f->grow, f->grow_init, f->qt.q00, f->ids_dev, al.scan.blobs, B, f->grow_bits ? f->unm_dev : nullptr,
-                         f->unm_words, f->grow_bits ? f->fh.pflag : nullptr);
+                         f->unm_words, f->grow_bits ? f->fh.pflag : nullptr,
+                         f->grow_ranges ? al.scan.rng : nullptr);  // (pk_grow_ranges; NULL too when no blob has a finite range)
     if (f->retire.on()) {  // pk_grow_retire: stale readings and unconfirmed features go, behind this scan's bookkeeping
       f->retire.t += 1u;
       launch_grow_retire(f->stream, f->d, f->grow, f->retire);

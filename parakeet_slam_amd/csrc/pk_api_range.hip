@@ -8,7 +8,7 @@
 //   1. another number of blobs than the ranges were armed for                          PK_ERR_INVALID
 //   2. a filter that is not on PK_MODEL_BEARING                                         PK_ERR_UNSUPPORTED
 //   3. the dense layout: the bearing model's own refusal, in its own words              PK_ERR_UNSUPPORTED
-//   4. growing maps (pk_grow_enable)                                                    PK_ERR_UNSUPPORTED
+//   4. growing maps (pk_grow_enable), unless pk_grow_ranges is on                       PK_ERR_UNSUPPORTED
 // pk_propose / pk_propose_odom refuse armed ranges before anything else (refuse_ranges_proposal) -- unless pk_proposal_ranges is on:
 // then they consume them (ranges_take), these refusals ahead of the proposal's own.  Nothing has changed when one of them answers,
 // except that the ranges are gone.
@@ -19,7 +19,7 @@ int refuse_ranges(const pk_filter* f, const char* who, int32_t B, int32_t armed_
     return fail(PK_ERR_UNSUPPORTED, "%s: per-blob ranges (pk_scan_ranges) are an option of the bearing model "
                                     "(pk_set_measurement_model(f, PK_MODEL_BEARING)); the reference model has no range", who);
   if (f->dense) return refuse_bearing(f, who, "the dense layout (covariances or a Qt that couple position, bearing and colour)");
-  if (f->grow_on)
+  if (f->grow_on && !f->grow_ranges)
     return fail(PK_ERR_UNSUPPORTED, "%s: per-blob ranges (pk_scan_ranges) have no kernel for growing maps (pk_grow_enable): a new "
                                     "landmark is still placed from two bearings", who);
   return PK_OK;
@@ -85,6 +85,22 @@ int pk_scan_ranges(pk_filter* f, const double* ranges, const double* variances, 
   r.any = any;
   r.B = B;
   std::swap(f->rng, r);
+  return PK_OK;
+}
+
+// pk_grow_ranges: ranged scans on a growing map -- refusal 4 above steps aside, and the bookkeeping kernel places a new feature from
+// one ranged sighting (k_new_landmarks_ranged / _tri_ranged, pk_k_grow.hip), from the next scan on (it keeps no per-particle state)
+int pk_grow_ranges(pk_filter* f, int32_t on) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_grow_ranges: NULL handle");
+  if (!f->grow_on) return fail(PK_ERR_STATE, "pk_grow_ranges: pk_grow_enable was not called on this filter");
+  if (on != 0 && on != 1) return fail(PK_ERR_INVALID, "pk_grow_ranges: on = %d is neither 0 nor 1", (int)on);
+  f->grow_ranges = on == 1;
+  return PK_OK;
+}
+
+int pk_grow_ranges_state(const pk_filter* f, int32_t* on) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_grow_ranges_state: NULL handle");
+  if (on) *on = f->grow_ranges ? 1 : 0;
   return PK_OK;
 }
 

@@ -379,7 +379,8 @@ struct pk_filter {
   GrowState grow{};                 // section 8(f4) on the device (pk_grow_enable): per-particle new-landmark bookkeeping
   GrowInit grow_init{};             // pk_grow_init: where and how surely the bookkeeping places a new feature (no per-particle state)
   bool grow_on = false;
-  RetireState retire{};             // pk_grow_retire (pk_api_retire.hip): the clocks of the retirement rule -- nothing until it is switched on
+  bool grow_ranges = false;         // pk_grow_ranges: a ranged scan is taken, and one ranged sighting places a new feature (no per-particle state)
+  RetireState retire{};            // pk_grow_retire (pk_api_retire.hip): the clocks of the retirement rule -- nothing until it is switched on
   // the measurement-informed proposal (pk_propose / pk_propose_odom; pk_api_propose.hip): nothing until the first call, then
   // 84 P bytes -- ten rows of P doubles and one of P int32
   struct Proposal {

@@ -60,13 +60,21 @@ __device__ __forceinline__ bool grow_cross_readings(double x1, double y1, double
 // kTri (pk_grow_init, PK_GROW_INIT_TRIANGULATED; DESIGN.md section 9, "Parallax-gated pairing"): a stored reading is a candidate only
 // if its ray meets the blob's at min_parallax or more (sin_min = sin(min_parallax), formed on the host), and the new feature's
 // position covariance is the triangulation's own, J diag(q00, q00) J' over the two bearings, in place of the identity.
-template <bool kTri>
+//
+// kRanged (pk_grow_ranges; DESIGN.md section 9, "Single-sighting initialisation"): rng holds the scan's range rows ([B][2] range,
+// variance, scan order; NaN range = none).  An unmatched blob with a finite range becomes a potential feature in the next spare slot
+// at once, at s + rho u with the covariance q_rho u u' + rho^2 q00 n n' -- no ring search, no ring write; without a range, or with
+// every spare slot taken, it goes through the rule above.  The range row is read at a wave-uniform address, so the test is
+// wave-uniform.  (The bit rows of the one-pass kernels stay in this shared body; under the bearing model, the only one with ranges,
+// they are not reached: its scans take the general route and leave ids.)
+template <bool kTri, bool kRanged>
 __device__ __forceinline__ void new_landmarks_body(const GrowState& g, const double* __restrict__ x, const double* __restrict__ y,
                                                    const double* __restrict__ h, const int32_t* __restrict__ ids,
                                                    const double* __restrict__ blobs, int B, unsigned char* __restrict__ map,
                                                    size_t slot_bytes, size_t count_off, int Lp, int64_t P,
                                                    const unsigned* __restrict__ unm, int unm_words,
-                                                   const unsigned char* __restrict__ pflag, double sin_min, double q00) {
+                                                   const unsigned char* __restrict__ pflag, double sin_min, double q00,
+                                                   const double* __restrict__ rng) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t p = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
   if (p >= P) return;  // wave-uniform
@@ -98,6 +106,37 @@ __device__ __forceinline__ void new_landmarks_body(const GrowState& g, const dou
       const int b = b0 + __builtin_ctzll(vote);
       vote &= vote - 1ull;
       const double zb = blobs[4 * b], zr = blobs[4 * b + 1], zg = blobs[4 * b + 2], zc = blobs[4 * b + 3];
+      if constexpr (kRanged) {
+        const double rho = rng[2 * b], qr = rng[2 * b + 1];
+        if (isfinite(rho) && used < g.S) {  // wave-uniform: the measured point, and what add_new_feature leaves around it
+          if (lane == 0) {
+            const int l = g.L0 + used;
+            const double t = ph + zb;
+            double sn, cs;
+            sincos(t, &sn, &cs);
+            const double a = (rho * rho) * q00;
+            f[(size_t)F_MX * Lp + l] = px + rho * cs;
+            f[(size_t)F_MY * Lp + l] = py + rho * sn;
+            f[(size_t)F_MR * Lp + l] = zr;  // (the blob's own colour: there is no second reading to average with)
+            f[(size_t)F_MG * Lp + l] = zg;
+            f[(size_t)F_MB * Lp + l] = zc;
+            f[(size_t)F_PXX * Lp + l] = qr * (cs * cs) + a * (sn * sn);
+            f[(size_t)F_PXY * Lp + l] = (qr - a) * (cs * sn);
+            f[(size_t)F_PYY * Lp + l] = qr * (sn * sn) + a * (cs * cs);
+            f[(size_t)F_CRR * Lp + l] = 1.0;
+            f[(size_t)F_CRG * Lp + l] = 0.0;
+            f[(size_t)F_CRB * Lp + l] = 0.0;
+            f[(size_t)F_CGG * Lp + l] = 1.0;
+            f[(size_t)F_CGB * Lp + l] = 0.0;
+            f[(size_t)F_CBB * Lp + l] = 1.0;
+            fc[l] = kPotentialBit;
+            sid[used] = next_id;
+          }
+          ++used;
+          ++next_id;
+          continue;
+        }
+      }
       int best = -1;
       double best_d = INFINITY;
       for (int r = lane; r < n; r += kWave) {  // find_nearest_reading :566-590 over the stored readings
@@ -185,7 +224,7 @@ __global__ void __launch_bounds__(256) k_new_landmarks(GrowState g, const double
                                                        size_t slot_bytes, size_t count_off, int Lp, int64_t P,
                                                        const unsigned* __restrict__ unm, int unm_words,
                                                        const unsigned char* __restrict__ pflag) {
-  new_landmarks_body<false>(g, x, y, h, ids, blobs, B, map, slot_bytes, count_off, Lp, P, unm, unm_words, pflag, 0.0, 0.0);
+  new_landmarks_body<false, false>(g, x, y, h, ids, blobs, B, map, slot_bytes, count_off, Lp, P, unm, unm_words, pflag, 0.0, 0.0, nullptr);
 }
 // PK_GROW_INIT_TRIANGULATED: the parallax gate in the search, the propagated covariance in lane 0's write
 __global__ void __launch_bounds__(256) k_new_landmarks_tri(GrowState g, const double* __restrict__ x, const double* __restrict__ y,
@@ -194,15 +233,41 @@ __global__ void __launch_bounds__(256) k_new_landmarks_tri(GrowState g, const do
                                                            size_t slot_bytes, size_t count_off, int Lp, int64_t P,
                                                            const unsigned* __restrict__ unm, int unm_words,
                                                            const unsigned char* __restrict__ pflag, double sin_min, double q00) {
-  new_landmarks_body<true>(g, x, y, h, ids, blobs, B, map, slot_bytes, count_off, Lp, P, unm, unm_words, pflag, sin_min, q00);
+  new_landmarks_body<true, false>(g, x, y, h, ids, blobs, B, map, slot_bytes, count_off, Lp, P, unm, unm_words, pflag, sin_min, q00, nullptr);
+}
+// pk_grow_ranges, for a scan in which some blob has a range: the two rules above behind the single-sighting placement
+__global__ void __launch_bounds__(256) k_new_landmarks_ranged(GrowState g, const double* __restrict__ x, const double* __restrict__ y,
+                                                              const double* __restrict__ h, const int32_t* __restrict__ ids,
+                                                              const double* __restrict__ blobs, int B, unsigned char* __restrict__ map,
+                                                              size_t slot_bytes, size_t count_off, int Lp, int64_t P,
+                                                              const unsigned* __restrict__ unm, int unm_words,
+                                                              const unsigned char* __restrict__ pflag, double q00,
+                                                              const double* __restrict__ rng) {
+  new_landmarks_body<false, true>(g, x, y, h, ids, blobs, B, map, slot_bytes, count_off, Lp, P, unm, unm_words, pflag, 0.0, q00, rng);
+}
+__global__ void __launch_bounds__(256) k_new_landmarks_tri_ranged(GrowState g, const double* __restrict__ x, const double* __restrict__ y,
+                                                                  const double* __restrict__ h, const int32_t* __restrict__ ids,
+                                                                  const double* __restrict__ blobs, int B, unsigned char* __restrict__ map,
+                                                                  size_t slot_bytes, size_t count_off, int Lp, int64_t P,
+                                                                  const unsigned* __restrict__ unm, int unm_words,
+                                                                  const unsigned char* __restrict__ pflag, double sin_min, double q00,
+                                                                  const double* __restrict__ rng) {
+  new_landmarks_body<true, true>(g, x, y, h, ids, blobs, B, map, slot_bytes, count_off, Lp, P, unm, unm_words, pflag, sin_min, q00, rng);
 }
 #pragma clang fp contract(on)
 
 void launch_new_landmarks(hipStream_t s, DeviceState& d, GrowState& g, const GrowInit& init, double q00, const int32_t* ids_dev,
-                          const double* blobs_dev, int B, const unsigned* unm_dev, int unm_words, const unsigned char* pflag_dev) {
+                          const double* blobs_dev, int B, const unsigned* unm_dev, int unm_words, const unsigned char* pflag_dev,
+                          const double* rng_dev) {
   if (d.P == 0 || B == 0) return;
   const dim3 grid((unsigned)((d.P + 3) / 4)), block(256);
-  if (init.mode == kGrowInitTriangulated)
+  if (rng_dev && init.mode == kGrowInitTriangulated)
+    hipLaunchKernelGGL(k_new_landmarks_tri_ranged, grid, block, 0, s, g, d.x[d.cur], d.y[d.cur], d.h[d.cur], ids_dev, blobs_dev, B,
+                       d.map[d.mcur], d.lay.slot_bytes, d.lay.count_off, d.lay.Lp, d.P, unm_dev, unm_words, pflag_dev, init.sin_min, q00, rng_dev);
+  else if (rng_dev)
+    hipLaunchKernelGGL(k_new_landmarks_ranged, grid, block, 0, s, g, d.x[d.cur], d.y[d.cur], d.h[d.cur], ids_dev, blobs_dev, B, d.map[d.mcur],
+                       d.lay.slot_bytes, d.lay.count_off, d.lay.Lp, d.P, unm_dev, unm_words, pflag_dev, q00, rng_dev);
+  else if (init.mode == kGrowInitTriangulated)
     hipLaunchKernelGGL(k_new_landmarks_tri, grid, block, 0, s, g, d.x[d.cur], d.y[d.cur], d.h[d.cur], ids_dev, blobs_dev, B, d.map[d.mcur],
                        d.lay.slot_bytes, d.lay.count_off, d.lay.Lp, d.P, unm_dev, unm_words, pflag_dev, init.sin_min, q00);
   else

@@ -686,9 +686,11 @@ void launch_iota(hipStream_t s, int32_t* p, int64_t n);
 // unm_dev != NULL: the unmatched blobs of particle p come from its bit row there (the one-pass kernels leave it) unless pflag_dev[p] != 0
 // (the fall-back kernels took the particle and left its ids in ids_dev's row)
 // init.mode picks the kernel's instance; q00 = Qt[0][0] of this scan (the triangulated covariance's bearing variance)
+// rng_dev != NULL (pk_grow_ranges, a scan in which some blob has a range): the scan's range rows ([B][2] range, variance, scan
+// order) -- the ranged instance of the rule init.mode picks; NULL: today's kernels
 void launch_new_landmarks(hipStream_t s, DeviceState& d, GrowState& g, const GrowInit& init, double q00, const int32_t* ids_dev,
                           const double* blobs_dev, int B, const unsigned* unm_dev = nullptr, int unm_words = 0,
-                          const unsigned char* pflag_dev = nullptr);
+                          const unsigned char* pflag_dev = nullptr, const double* rng_dev = nullptr);
 // anc >= 0: a particle of this filter; anc < 0: record -anc - 1 of buf (stride bytes apart, its bookkeeping tail_off bytes in)
 void launch_grow_gather(hipStream_t s, GrowState& g, const int32_t* anc_dev, int64_t P, const unsigned char* buf_dev = nullptr,
                         size_t stride = 0, size_t tail_off = 0);
