@@ -660,7 +660,8 @@ int pk_step_odom(pk_filter* f, const double delta[3], const double alpha[4], con
  * calls them allocates and launches what it did.  The limits of a maximum-likelihood pk_observe (65 535 blobs, the LDS chains of
  * landmarks + 2 x blobs) hold for maximum-likelihood scans here; supplied ids have neither.
  * Refused, nothing changed -- PK_ERR_UNSUPPORTED: a filter not on PK_MODEL_BEARING (the reference model's Jacobian is not one), the
- * dense layout, growing maps or retirement (pk_grow_enable, pk_grow_retire), a shard of a sharded filter or a split step in progress;
+ * dense layout, growing maps or retirement (pk_grow_enable, pk_grow_retire) unless pk_proposal_grow is on, a shard of a sharded
+ * filter or a split step in progress;
  * PK_ERR_STATE: a staged scan in flight (pk_stage_scan), no map; PK_ERR_INVALID: the arguments, as pk_motion / pk_motion_odom /
  * pk_observe refuse them. */
 int pk_propose(pk_filter* f, double v, double w, double dt, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
@@ -685,6 +686,27 @@ int pk_proposal_download(pk_filter* f, double* xi, double* dlogw, int32_t* used)
  * pk_proposal_ranges_state: *on = 1 or 0. */
 int pk_proposal_ranges(pk_filter* f, int32_t on);
 int pk_proposal_ranges_state(const pk_filter* f, int32_t* on);
+
+/* The proposal on growing maps ("The proposal on growing maps"): an opt-in mode of pk_propose / pk_propose_odom.
+ * Off (the default) they refuse a filter with pk_grow_enable or pk_grow_retire on, as ever.  On (on = 1; anything but 0 or 1 is
+ * PK_ERR_INVALID and changes nothing), a filter without either does what it did, bit for bit, and a growing filter runs steps 1-7
+ * above unchanged, with two steps behind them:
+ *   3. the association sees the untouched state, spare slots included; with ranges it is "Ranges in the proposal"'s;
+ *   4. only settled matches to CONFIRMED landmarks condition the draw: a match to a potential feature is updated at the sampled
+ *      pose and weighs log 0.1, as does a blob nobody matched;
+ *   8. behind the update, pk_observe's new-landmark bookkeeping at the SAMPLED pose on the settled ids (0 = unmatched), by the rule
+ *      pk_grow_init selected; with pk_grow_ranges on it takes the scan's ranges -- a ranged unmatched blob becomes a potential
+ *      feature at once, at the sampled pose + rho u;
+ *   9. then pk_grow_retire's pass, its clock advanced, as behind pk_observe.
+ * An empty scan (num_blobs = 0): xi = z, no bookkeeping, and the retirement clock stands still.  The resample, the path, the
+ * adaptive gate and the summaries follow unchanged.  The new launches are timed in PK_T_OBSERVE.
+ * Refused on a growing filter with the mode on, nothing changed and armed ranges gone, in this order: the ranges' own refusals
+ * (armed ranges need pk_proposal_ranges and pk_grow_ranges: without the former the proposal's refusal of ranges answers, without
+ * the latter pk_scan_ranges' refusal 4), the proposal's, then supplied ids with num_blobs > 0 -- PK_ERR_STATE, in pk_observe's
+ * words: the bookkeeping follows the maximum-likelihood association.
+ * The mode holds no device memory (pk_device_bytes is what it was).  pk_proposal_grow_state: *on = 1 or 0. */
+int pk_proposal_grow(pk_filter* f, int32_t on);
+int pk_proposal_grow_state(const pk_filter* f, int32_t* on);
 
 /* ---- sharded (multi-GPU) resampling: see DESIGN.md section 6 -------------------
  * Particles are sharded contiguously over one process per GPU; global particle index =

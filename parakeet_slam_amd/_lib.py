@@ -126,6 +126,8 @@ SIGNATURES = {
     "pk_proposal_download": (C.c_int, [_h, _dp, _dp, _ip]),
     "pk_proposal_ranges": (C.c_int, [_h, C.c_int32]),
     "pk_proposal_ranges_state": (C.c_int, [_h, C.POINTER(C.c_int32)]),
+    "pk_proposal_grow": (C.c_int, [_h, C.c_int32]),
+    "pk_proposal_grow_state": (C.c_int, [_h, C.POINTER(C.c_int32)]),
     "pk_motion_odom_range": (C.c_int, [_h, _dp, _dp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64]),
     "pk_step_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_double, C.c_int32, C.c_double]),
     "pk_shard_max_logw": (C.c_int, [_h, _dp]),
@@ -432,6 +434,17 @@ class DeviceFilter(object):
         """Whether propose / propose_odom take armed ranges: pk_proposal_ranges_state."""
         on = C.c_int32(0)
         check(self._lib.pk_proposal_ranges_state(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def proposal_grow(self, on=True):
+        """The proposal on growing maps (pk_proposal_grow): on, propose / propose_odom run on a filter with grow_enable / grow_retire
+        -- the new-landmark bookkeeping and retirement follow the step at the sampled poses -- instead of refusing it."""
+        check(self._lib.pk_proposal_grow(self._h, int(on)))
+
+    def proposal_grow_state(self):
+        """Whether propose / propose_odom run on a growing filter: pk_proposal_grow_state."""
+        on = C.c_int32(0)
+        check(self._lib.pk_proposal_grow_state(self._h, C.byref(on)))
         return bool(on.value)
 
     def download_log_weights(self):

@@ -45,13 +45,37 @@ def _blob_row(blob):
     return np.array([blob.bearing, blob.color.r, blob.color.g, blob.color.b], dtype=np.float64)
 
 
+def _check_proposal_grow(proposal_grow, proposal, new_landmarks, spare_landmarks, bookkeeping, devices, range_noise, proposal_ranges,
+                         grow_ranges, who="FastSLAM"):
+    """proposal_grow=True: the measurement-informed proposal on a growing map (pk_proposal_grow) -- it needs proposal='measurement',
+    new_landmarks=True with spare slots, the device bookkeeping and one GPU; a range_noise then goes through the proposal AND the
+    bookkeeping (proposal_ranges=True and grow_ranges=True together)."""
+    if not proposal_grow:
+        return False
+    if proposal != "measurement":
+        raise ValueError("%s(proposal_grow=True): the proposal on growing maps is a mode of proposal='measurement'" % who)
+    if not new_landmarks or not int(spare_landmarks) > 0:
+        raise ValueError("%s(proposal_grow=True): the proposal on growing maps needs a map that grows: new_landmarks=True and "
+                         "spare_landmarks > 0" % who)
+    if bookkeeping != "device":
+        raise ValueError("%s(proposal_grow=True): the new-landmark bookkeeping follows the proposal step on the device "
+                         "(bookkeeping='device'), not bookkeeping='host'" % who)
+    if devices is not None and len(list(devices)) > 1:
+        raise ValueError("%s(devices=[...], proposal_grow=True): the measurement-informed proposal runs on one GPU" % who)
+    if range_noise is not None and not (proposal_ranges and grow_ranges):
+        raise ValueError("%s(range_noise=..., proposal_grow=True): the ranges of a growing map under the proposal enter both the "
+                         "proposal and the bookkeeping: proposal_ranges=True and grow_ranges=True together" % who)
+    return True
+
+
 def _check_range_noise(range_noise, measurement_model, proposal, new_landmarks, who="FastSLAM", proposal_ranges=False,
-                       grow_ranges=False):
+                       grow_ranges=False, proposal_grow=False):
     """range_noise=(sigma0, sigma1) of FastSLAM: None, or the two floats of a range's standard deviation sigma0 + sigma1 rho.
     proposal_ranges=True: ranges enter the measurement-informed proposal -- it needs both range_noise and proposal='measurement'.
     grow_ranges=True: ranges on a growing map -- it needs range_noise, new_landmarks=True and proposal='motion' (the spare slots and
-    the device bookkeeping are checked by _check_grow_ranges)."""
-    if grow_ranges and (range_noise is None or not new_landmarks or proposal == "measurement"):
+    the device bookkeeping are checked by _check_grow_ranges); proposal='measurement' takes it with proposal_grow=True
+    (_check_proposal_grow has held that to its own conditions)."""
+    if grow_ranges and (range_noise is None or not new_landmarks or (proposal == "measurement" and not proposal_grow)):
         raise ValueError("%s(grow_ranges=True): ranges on a growing map need range_noise=(sigma0, sigma1), new_landmarks=True and "
                          "proposal='motion'" % who)
     if proposal_ranges and (range_noise is None or proposal != "measurement"):
@@ -680,7 +704,8 @@ class FastSLAM(object):
     CONDITIONED on its scan (FastSLAM 2.0; pk_propose, pk_propose_odom; DESIGN.md section 4, "The measurement-informed proposal") --
     one call in place of the move and the observe, with the same dt bookkeeping and draw counter.  In odometry mode
     ``odom_motion_update`` only stores the message, and ``cam_cb`` moves by the change since the pose it last moved up to.  One GPU,
-    preset maps only (no new_landmarks).  ``record_ids=True`` keeps every step's settled ids in ``last_ids`` (one download per step).
+    preset maps only (no new_landmarks) unless proposal_grow=True.  ``record_ids=True`` keeps every step's settled ids in
+    ``last_ids`` (one download per step).
 
     measurement_model="bearing" (default "reference": the reference's model, quirks included): the textbook robot-frame bearing
     model -- wrapped bearing differences in the gate and the innovation, the blob's ray turned by the heading, H = (-dy / q, dx / q),
@@ -710,6 +735,15 @@ class FastSLAM(object):
     range goes through ``landmark_init``'s rule.  Without it range_noise and new_landmarks=True stay a ValueError; with it, a missing
     range_noise, a preset map, bookkeeping="host" or proposal="measurement" is one.  ``save_state`` writes the flag when it is set
     and ``load_state`` takes it from the snapshot (one without it: off).  One GPU (the bearing model's).
+
+    proposal_grow=True (default False; with proposal="measurement", new_landmarks=True, spare_landmarks > 0 and the device
+    bookkeeping): the measurement-informed proposal on a growing map (pk_proposal_grow; DESIGN.md section 4, "The proposal on growing
+    maps").  Every pose is drawn conditioned on the scan's matches to CONFIRMED landmarks; a match to a potential feature is updated
+    and weighs log 0.1; the unmatched blobs then go through ``landmark_init``'s rule at the SAMPLED pose, and the retirement pass
+    follows.  range_noise then needs proposal_ranges=True and grow_ranges=True together: a ranged unmatched blob becomes a potential
+    feature at once.  Without the keyword proposal="measurement" with new_landmarks=True stays a ValueError; with it,
+    proposal="motion", a preset map, no spare slot, bookkeeping="host" or several devices is one.  In odometry mode a scan with no
+    new odometry is the plain growing observe.  Snapshots do not carry the flag (they do not carry ``proposal`` either).  One GPU.
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -727,8 +761,11 @@ class FastSLAM(object):
         ba.apply_defaults()
         a = ba.arguments
         _check_landmark_init(a["landmark_init"], a["min_parallax"], a["new_landmarks"])
+        _check_proposal_grow(bool(a["proposal_grow"]), a["proposal"], a["new_landmarks"], a["spare_landmarks"], a["bookkeeping"],
+                             a.get("devices"), a["range_noise"], bool(a["proposal_ranges"]), bool(a["grow_ranges"]))
         _check_range_noise(a["range_noise"], a["measurement_model"], a["proposal"], a["new_landmarks"],
-                           proposal_ranges=bool(a["proposal_ranges"]), grow_ranges=bool(a["grow_ranges"]))
+                           proposal_ranges=bool(a["proposal_ranges"]), grow_ranges=bool(a["grow_ranges"]),
+                           proposal_grow=bool(a["proposal_grow"]))
         _check_grow_ranges(a["grow_ranges"], a["spare_landmarks"], a["bookkeeping"])
         devices = a.get("devices")
         if devices is not None and len(list(devices)) > 1:
@@ -774,12 +811,16 @@ class FastSLAM(object):
                  bookkeeping="device", reading_capacity=64, record_ids=None, record_path=0, resample_threshold=None,
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
                  odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion",
-                 landmark_init="reference", min_parallax=0.2, range_noise=None, proposal_ranges=False, grow_ranges=False):
+                 landmark_init="reference", min_parallax=0.2, range_noise=None, proposal_ranges=False, grow_ranges=False,
+                 proposal_grow=False):
         self._landmark_init, self._min_parallax = _check_landmark_init(landmark_init, min_parallax, new_landmarks)
         if measurement_model not in _lib.MEASUREMENT_MODELS:
             raise ValueError("FastSLAM(measurement_model=%r): 'reference' (default) or 'bearing'" % (measurement_model,))
+        self._proposal_grow = _check_proposal_grow(bool(proposal_grow), proposal, new_landmarks, spare_landmarks, bookkeeping, devices,
+                                                   range_noise, bool(proposal_ranges), bool(grow_ranges))
         self._range_noise = _check_range_noise(range_noise, measurement_model, proposal, new_landmarks,
-                                               proposal_ranges=bool(proposal_ranges), grow_ranges=bool(grow_ranges))
+                                               proposal_ranges=bool(proposal_ranges), grow_ranges=bool(grow_ranges),
+                                               proposal_grow=self._proposal_grow)
         self._proposal_ranges = bool(proposal_ranges)
         self._grow_ranges = _check_grow_ranges(grow_ranges, spare_landmarks, bookkeeping)
         if proposal not in ("motion", "measurement"):
@@ -787,7 +828,7 @@ class FastSLAM(object):
         if proposal == "measurement" and measurement_model != "bearing":
             raise ValueError("FastSLAM(proposal='measurement'): the measurement-informed proposal needs measurement_model='bearing' "
                              "-- the reference model's Jacobian is not one")
-        if proposal == "measurement" and new_landmarks:
+        if proposal == "measurement" and new_landmarks and not self._proposal_grow:
             raise ValueError("FastSLAM(proposal='measurement', new_landmarks=True): growing maps are found by the plain step "
                              "(proposal='motion')")
         self._model = measurement_model
@@ -823,6 +864,8 @@ class FastSLAM(object):
             self._filter.set_measurement_model(self._model)
         if self._proposal_ranges:
             self._filter.proposal_ranges(True)
+        if self._proposal_grow:
+            self._filter.proposal_grow(True)
         if L + self._spare:
             means = np.zeros((L + self._spare, 5))
             covs = np.tile(np.identity(5).reshape(25), (L + self._spare, 1))
@@ -1415,7 +1458,7 @@ class FastSLAM(object):
                 init = _check_landmark_init(str(d["landmark_init"]) if "landmark_init" in d.files else "reference",
                                             float(d["min_parallax"]) if "min_parallax" in d.files else self._min_parallax, True, "snapshot")
             ranged = bool(d["grow_ranges"]) if "grow_ranges" in d.files else False
-            if ranged and not (self._nl_device and self._range_noise is not None and self._proposal == "motion"):
+            if ranged and not (self._nl_device and self._range_noise is not None and (self._proposal == "motion" or self._proposal_grow)):
                 raise ValueError("snapshot: taken with grow_ranges=True, which needs this filter's range_noise=(sigma0, sigma1), "
                                  "new_landmarks=True with spare_landmarks > 0, bookkeeping='device' and proposal='motion'")
             have_path = self._record_path and "path_ancestors" in d.files

@@ -898,6 +898,26 @@ static KnownChains known_chains(const pk_filter* f, const KnownScan& ks) {
   return c;
 }
 
+// Behind the observe launches of a growing filter's non-empty scan (pk_observe, pk_step; pk_propose / pk_propose_odom with
+// pk_proposal_grow): :92-95 for every particle at its live pose, on the ids the association left in HBM -- or, where the last
+// observe's one-pass kernel left them (grow_bits), on its bit rows -- (every particle's slot is its own now), then retirement's pass
+// with its clock advanced, then the launch check.  The one place: the plain path and the proposal's cannot drift apart.
+int grow_bookkeeping(pk_filter* f, const char* who, const ScanTables& scan, int32_t B) {
+  {
+    Span t(f, PK_T_OBSERVE);
+    launch_new_landmarks(f->stream, f->d, f->grow, f->grow_init, f->qt.q00, f->ids_dev, scan.blobs, B, f->grow_bits ? f->unm_dev : nullptr,
+                         f->unm_words, f->grow_bits ? f->fh.pflag : nullptr,
+                         f->grow_ranges ? scan.rng : nullptr);  // (pk_grow_ranges; NULL too when no blob has a finite range)
+    if (f->retire.on()) {  // pk_grow_retire: stale readings and unconfirmed features go, behind this scan's bookkeeping
+      f->retire.t += 1u;
+      launch_grow_retire(f->stream, f->d, f->grow, f->retire);
+    }
+  }
+  const std::string what = std::string(who) + " (new landmarks)";
+  PK_LAUNCH_CHECK(what.c_str());
+  return PK_OK;
+}
+
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out,
                         bool reset) {
   if (!f) return fail(PK_ERR_INVALID, "pk_observe: NULL handle");
@@ -1009,17 +1029,7 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   }
   PK_LAUNCH_CHECK("pk_observe");
   observe_done(f);
-  if (grow) {  // :92-95 for every particle, on the ids the association kernel left in HBM (every particle's slot is its own now)
-    Span t(f, PK_T_OBSERVE);
-    launch_new_landmarks(f->stream, f->d, f->grow, f->grow_init, f->qt.q00, f->ids_dev, al.scan.blobs, B, f->grow_bits ? f->unm_dev : nullptr,
-                         f->unm_words, f->grow_bits ? f->fh.pflag : nullptr,
-                         f->grow_ranges ? al.scan.rng : nullptr);  // (pk_grow_ranges; NULL too when no blob has a finite range)
-    if (f->retire.on()) {  // pk_grow_retire: stale readings and unconfirmed features go, behind this scan's bookkeeping
-      f->retire.t += 1u;
-      launch_grow_retire(f->stream, f->d, f->grow, f->retire);
-    }
-    PK_LAUNCH_CHECK("pk_observe (new landmarks)");
-  }
+  if (grow && (rc = grow_bookkeeping(f, "pk_observe", al.scan, B))) return rc;
   if (ids_out && B > 0) {
     PK_HIP(hipMemcpyAsync(ids_out, f->ids_dev, (size_t)f->d.P * B * 4, hipMemcpyDeviceToHost, f->stream));
     PK_HIP(hipStreamSynchronize(f->stream));
@@ -1031,8 +1041,8 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
 // ctl | blobs | first | next, and behind it the id row itself -- or the bearing model's association at the live (predicted) poses,
 // which leaves tentative ids in ids_dev and touches no state.  The caller has checked the blobs, the ids and the filter.  rs: the
 // ranges the step took (pk_proposal_ranges), staged as pk_observe stages them -- a scan without a finite range stages the bytes
-// it always staged.
-int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out, const RangeScan* rs) {
+// it always staged.  grow: the new-landmark bookkeeping follows the step (pk_proposal_grow), as plan_scan is told.
+int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out, const RangeScan* rs, bool grow) {
   int rc;
   *out = ProposalScan();
   f->ct_updated = true;
@@ -1050,8 +1060,9 @@ int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* i
     return PK_OK;
   }
   AssocLaunch al;
-  if ((rc = enqueue_association(f, blobs, B, false, false, &al, false, true, rs))) return rc;
+  if ((rc = enqueue_association(f, blobs, B, false, false, &al, grow, true, rs))) return rc;
   if (al.plan.onepass()) return fail(PK_ERR_UNSUPPORTED, "pk_propose: the scan did not take the general association");
+  f->grow_bits = false;  // (the bookkeeping behind this scan reads the ids, never an earlier observe's bit rows)
   if ((rc = ct_end(f))) return rc;
   out->scan = al.scan;
   out->rng = al.scan.rng;

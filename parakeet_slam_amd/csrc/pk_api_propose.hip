@@ -3,7 +3,8 @@
 // (FastSLAM 2.0).  Host orchestration only: the kernels are the motion kernels as they stand (twice: with zero normals for the
 // predicted pose, with k_propose's normals for the sampled one), the bearing model's association, k_propose (pk_k_propose.hip)
 // and k_observe_proposed (pk_k_observe.hip) -- for a scan with ranged blobs (pk_proposal_ranges) the range association,
-// k_propose_range and k_observe_proposed_range.
+// k_propose_range and k_observe_proposed_range.  On a growing filter (pk_proposal_grow) pk_observe's own tail follows:
+// k_new_landmarks* at the sampled poses on the ids k_propose settled, then k_grow_retire.
 #include "pk_filter.hpp"
 
 namespace {
@@ -16,9 +17,10 @@ int refuse_proposal(const pk_filter* f, const char* who) {
   if (f->dense || f->qt_dense)
     return fail(PK_ERR_UNSUPPORTED, "%s: the measurement-informed proposal has no kernel for the dense layout (covariances or a Qt that "
                                     "couple position, bearing and colour)", who);
-  if (f->grow_on || f->retire.on())
+  if ((f->grow_on || f->retire.on()) && !f->prop.grow)
     return fail(PK_ERR_UNSUPPORTED, "%s: the measurement-informed proposal has no kernel for growing maps (pk_grow_enable, "
-                                    "pk_grow_retire): new landmarks are found by the plain step", who);
+                                    "pk_grow_retire): new landmarks are found by the plain step, or behind the proposal's own once "
+                                    "pk_proposal_grow(f, 1) switches that in", who);
   if (f->split.active || f->ct_sharded || f->d.global_offset != 0 || f->d.logical[0] || f->d.alt)
     return fail(PK_ERR_UNSUPPORTED, "%s: the measurement-informed proposal runs on one whole filter: this one is a shard of a sharded "
                                     "filter or inside a split step", who);
@@ -63,6 +65,10 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
     return rc;
   }
   if ((rc = refuse_proposal(f, who))) return rc;
+  // pk_proposal_grow: the new-landmark bookkeeping follows the step -- at the sampled poses, on the ids k_propose settles
+  const bool grow = f->grow_on && B > 0;
+  if (grow && ids)
+    return fail(PK_ERR_STATE, "%s: the new-landmark bookkeeping (pk_grow_enable) follows the maximum-likelihood association: no ids", who);
   if (B < 0 || (B > 0 && !blobs)) return fail(PK_ERR_INVALID, "%s: bad blobs", who);
   if (!f->map_loaded) return fail(PK_ERR_STATE, "%s: no map uploaded (pk_upload_map)", who);
   const int L = f->d.lay.L;
@@ -109,7 +115,7 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
     move(q.zero, nullptr);
   }
   ProposalScan sc;
-  rc = proposal_scan(f, blobs, B, ids, &sc, &rs);  // (the association, in its own span)
+  rc = proposal_scan(f, blobs, B, ids, &sc, &rs, grow);  // (the association, in its own span)
   if (!rc) {
     Span t(f, PK_T_PROPOSE);
     ProposeLaunch pl;
@@ -155,6 +161,8 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
   PK_LAUNCH_CHECK(who);
   proposal_observed(f, ids != nullptr);
   q.valid = true;
+  // a growing filter (pk_proposal_grow): pk_observe's own tail, at the sampled poses on the settled ids (0 = unmatched; no bit rows)
+  if (grow && (rc = grow_bookkeeping(f, who, sc.scan, B))) return rc;
   if (ids_out && B > 0) {
     if (ids) {
       for (int64_t p = 0; p < f->d.P; ++p) memcpy(ids_out + (size_t)p * B, ids, (size_t)B * 4);
@@ -197,6 +205,21 @@ int pk_proposal_ranges(pk_filter* f, int32_t on) {
 int pk_proposal_ranges_state(const pk_filter* f, int32_t* on) {
   if (!f) return fail(PK_ERR_INVALID, "pk_proposal_ranges_state: NULL handle");
   if (on) *on = f->prop.ranges ? 1 : 0;
+  return PK_OK;
+}
+
+// pk_proposal_grow: the step on a growing filter -- refuse_proposal's growing-map clause steps aside, and pk_observe's bookkeeping
+// and retirement run behind the step (grow_bookkeeping, pk_api_observe.hip).  No device state: kernels the library has, reordered.
+int pk_proposal_grow(pk_filter* f, int32_t on) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_proposal_grow: NULL handle");
+  if (on != 0 && on != 1) return fail(PK_ERR_INVALID, "pk_proposal_grow: on = %d is neither 0 nor 1", (int)on);
+  f->prop.grow = on == 1;
+  return PK_OK;
+}
+
+int pk_proposal_grow_state(const pk_filter* f, int32_t* on) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_proposal_grow_state: NULL handle");
+  if (on) *on = f->prop.grow ? 1 : 0;
   return PK_OK;
 }
 

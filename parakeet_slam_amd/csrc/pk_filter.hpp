@@ -7,7 +7,8 @@
 //                       settled rows, the best particle
 //   pk_api_adaptive.hip adaptive resampling: the gated resample and step, the weight sums, the weighted pose summary
 //   pk_api_mapmatch.hip the discovered landmarks: the matched moments and the finished estimate
-//   pk_api_propose.hip  the measurement-informed proposal: pk_propose, pk_propose_odom, pk_proposal_download
+//   pk_api_propose.hip  the measurement-informed proposal: pk_propose, pk_propose_odom, pk_proposal_download, its modes
+//                       (pk_proposal_ranges, pk_proposal_grow)
 //   pk_api_range.hip    range-bearing scans: pk_scan_ranges, what consumes the armed ranges, their refusals
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
 #pragma once
@@ -391,6 +392,7 @@ struct pk_filter {
     int32_t* used = nullptr;        // [P] the matches it used
     bool valid = false;             // the last call's results are there (pk_proposal_download)
     bool ranges = false;            // pk_proposal_ranges: armed ranges (pk_scan_ranges) are consumed by the step, not refused
+    bool grow = false;              // pk_proposal_grow: the step runs on a growing filter, the bookkeeping and retirement behind it (no device state)
   } prop;
   int32_t* anc = nullptr;           // P
   unsigned char* slot_tmp = nullptr;  // one slot
@@ -555,8 +557,12 @@ struct ProposalScan {
   int32_t* ids = nullptr;
   const double* rng = nullptr;
 };
-int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out, const RangeScan* rs = nullptr);
+int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, ProposalScan* out, const RangeScan* rs = nullptr,
+                  bool grow = false);
 void proposal_observed(pk_filter* f, bool known);
+// the tail of a growing filter's non-empty scan, behind its observe launches: new landmarks at the live poses on the ids in ids_dev
+// (or the last one-pass kernel's bit rows), retirement's pass with its clock advanced, the launch check ("<who> (new landmarks)")
+int grow_bookkeeping(pk_filter* f, const char* who, const ScanTables& scan, int32_t B);
 // what the bearing model (pk_set_measurement_model) has no kernels for, refused while it is on (a NULL handle passes)
 int refuse_bearing(const pk_filter* f, const char* who, const char* what);
 // pk_api_range.hip: the armed ranges of the next scan (pk_scan_ranges).  ranges_take: what every call that takes blobs starts
