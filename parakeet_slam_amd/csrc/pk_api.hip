@@ -839,7 +839,7 @@ int motion_impl(pk_filter* f, const char* who, const double* z, const MotionLaun
   if (!z && sg.valid && !sg.uploaded && f->opt.upload_kernel) {
     void* dev_view = nullptr;
     if (hipHostGetDevicePointer(&dev_view, sg.st, 0) == hipSuccess && dev_view) {
-      launch(nullptr, f->scan_dev, dev_view, staged_upload_bytes(sg));
+      launch(nullptr, f->scan_dev, dev_view, sg.lay.upload_bytes);
       f->pose_part_ok = true;
       sg.uploaded = true;
       f->gmax_fused = false;  // the block's control words (running weight maximum) were just overwritten
@@ -879,16 +879,15 @@ int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed,
         {
           Span t(f, PK_T_MOTION);
           if (m.odom)
-            launch_motion_odom(f->stream, f->d, m.delta, m.sigma, nullptr, seed, draw, f->scan_dev, dev_view, staged_upload_bytes(sg), f->pose_part);
+            launch_motion_odom(f->stream, f->d, m.delta, m.sigma, nullptr, seed, draw, f->scan_dev, dev_view, sg.lay.upload_bytes, f->pose_part);
           else
-            launch_motion(f->stream, f->d, m.v, m.w, m.dt, nullptr, seed, draw, 0, f->scan_dev, dev_view, staged_upload_bytes(sg), f->pose_part);
+            launch_motion(f->stream, f->d, m.v, m.w, m.dt, nullptr, seed, draw, 0, f->scan_dev, dev_view, sg.lay.upload_bytes, f->pose_part);
           f->pose_part_ok = true;
         }
         sg.uploaded = true;
         f->gmax_fused = false;
         if ((rc = note_upload(f, sg.slot))) return rc;
-        const double* staged_blobs = reinterpret_cast<const double*>(sg.st + kCtlBytes);
-        if ((rc = observe_impl(f, staged_blobs, B, nullptr, nullptr, reset))) return rc;  // :73 (reset fused) + :82-124
+        if ((rc = observe_impl(f, staged_blobs(sg), B, nullptr, nullptr, reset))) return rc;  // :73 (reset fused) + :82-124
         return resample();
       }
       (void)hipGetLastError();

@@ -1,6 +1,7 @@
-// The observe pipeline behind the C ABI (pk_filter.hpp): the staging ring and the per-scan block, the blob grid, which kernels a
-// scan gets (plan_scan; DESIGN.md section 4, "Routing"), the association, the one-pass stages, observe_impl and the pk_observe*
-// entry points with their read-outs; and the colour table's host side (ct_*).  Host orchestration only.
+// The observe pipeline behind the C ABI (pk_filter.hpp): which kernels a scan gets (plan_scan; DESIGN.md section 4, "Routing"), the
+// association, the dense observe, the one-pass stages, the new-landmark bookkeeping's launch, observe_impl, the proposal's scan and
+// the pk_observe* entry points with their read-outs; and the colour table's host side (ct_*).  How the scan got onto the device is
+// pk_api_scan.hip's.  Host orchestration only.
 #include "pk_filter.hpp"
 
 // a pinned block of 64 bytes whose first word starts at 0 (retry_seen, ct_seen)
@@ -17,82 +18,6 @@ int refuse_bearing(const pk_filter* f, const char* who, const char* what) {
   if (f && f->model == PK_MODEL_BEARING)
     return fail(PK_ERR_UNSUPPORTED, "%s: the bearing measurement model (pk_set_measurement_model) has no kernel for %s; "
                                     "pk_set_measurement_model(f, PK_MODEL_REFERENCE) takes it", who, what);
-  return PK_OK;
-}
-
-static int ensure_scan_capacity(pk_filter* f, size_t bytes) {
-  if (bytes <= f->scan_cap) return PK_OK;
-  int rc;
-  if ((rc = dev_reserve(f, &f->scan_dev, &f->scan_cap, bytes, bytes + bytes / 4 + 4096))) return rc;
-  f->gmax_fused = false;  // the running-max keys lived in the block that was just freed
-  return PK_OK;
-}
-
-static int ensure_ids_capacity(pk_filter* f, int B) {
-  const int64_t need = f->d.P * (int64_t)B;
-  return dev_reserve(f, &f->ids_dev, &f->ids_cap, need, need);
-}
-
-// One scan block host -> device in stream order.  The staging ring is pinned and device-mapped, so
-// a small kernel reads it directly (k_upload); sizes are padded to 16 bytes on both sides.  Falls
-// back to the copy engine when the mapping is not available.
-static int upload_scan(pk_filter* f, const unsigned char* st, size_t bytes) {
-  void* dev_view = nullptr;
-  if (f->opt.upload_kernel && hipHostGetDevicePointer(&dev_view, const_cast<unsigned char*>(st), 0) == hipSuccess && dev_view) {
-    launch_upload(f->stream, f->scan_dev, dev_view, bytes);
-    return PK_OK;
-  }
-  (void)hipGetLastError();
-  PK_HIP(hipMemcpyAsync(f->scan_dev, st, bytes, hipMemcpyHostToDevice, f->stream));
-  return PK_OK;
-}
-
-// An upload that reads staging slot `slot` has just been enqueued on the stream.
-int note_upload(pk_filter* f, int slot) {
-  f->slot_seq[slot] = ++f->upload_seq;
-  if ((slot & 3) == 3) {  // an event record costs the stream a few microseconds: one per four uploads
-    PK_HIP(hipEventRecord(f->stage_done[slot], f->stream));
-    f->event_seq[slot] = f->upload_seq;
-  }
-  return PK_OK;
-}
-
-// Next pinned staging block of at least `bytes`; waits for the upload that last read it.
-static int take_stage(pk_filter* f, size_t bytes, unsigned char** out, int* slot) {
-  if (bytes > f->stage_cap) {
-    PK_HIP(hipStreamSynchronize(f->stream));
-    int rc;
-    f->stage_cap = 0;
-    size_t cap = bytes + bytes / 4 + 4096;
-    for (int i = 0; i < pk_filter::kRing; ++i) {
-      dev_free(f, &f->stage[i]);
-      if ((rc = host_alloc(f, &f->stage[i], cap, hipHostMallocMapped))) return rc;
-      if (!f->stage_done[i]) PK_HIP(hipEventCreateWithFlags(&f->stage_done[i], hipEventDisableTiming));
-      f->slot_seq[i] = 0;  // the stream is idle: nothing reads the old blocks any more
-    }
-    f->stage_cap = cap;
-  }
-  int i = f->stage_next;
-  f->stage_next = (i + 1) % pk_filter::kRing;
-  // Slot i may still be read by upload number slot_seq[i]; any event recorded at or after that upload
-  // covers it.  Normally that is the record behind slot (i | 3) of the previous trip round the ring;
-  // when that slot's scan was discarded before its upload (pk_stage_scan followed by a supplied-ids
-  // observe, an error between take_stage and the upload) no such record exists and one is made now.
-  const uint64_t need = f->slot_seq[i];
-  if (need != 0) {
-    int ev = -1;
-    for (int j = 0; j < pk_filter::kRing; ++j)
-      if (f->event_seq[j] >= need && (ev < 0 || f->event_seq[j] < f->event_seq[ev])) ev = j;
-    if (ev < 0) {
-      PK_HIP(hipEventRecord(f->stage_done[i], f->stream));
-      f->event_seq[i] = f->upload_seq;
-      ev = i;
-    }
-    PK_HIP(hipEventSynchronize(f->stage_done[ev]));
-    f->slot_seq[i] = 0;
-  }
-  *out = f->stage[i];
-  *slot = i;
   return PK_OK;
 }
 
@@ -191,135 +116,6 @@ static int ct_engage(pk_filter* f) {
   return PK_OK;
 }
 
-// unit((cos b, sin b, 0.0)) of closest_point (prkt_core_v2.py:510, utils.py:68-76): the ray
-// direction of each blob, scaled by 1/length exactly like utils.scale(vector, 1.0/length).
-void blob_directions(const double* blobs, int B, double* dir) {
-  for (int b = 0; b < B; ++b) {
-    double c = std::cos(blobs[4 * b]), s = std::sin(blobs[4 * b]);
-    double len = std::sqrt(c * c + s * s + 0.0 * 0.0);
-    dir[2 * b] = c * (1.0 / len);
-    dir[2 * b + 1] = s * (1.0 / len);
-  }
-}
-
-// Bucket the blobs of one scan into a 3-D colour grid (cell edge kGridCell > sqrt(300), the
-// colour gate radius of prkt_core_v2.py:441) and lay out what k_assoc_grid reads:
-//   tables: start u16[ncell+1] (padded to 16 bytes) | rec32 float4[B] | idx9 u16[n9] | order u16[B]
-//   exact:  double[B][6] = bearing, r, g, b, ux, uy      (rec32, exact, order in cell order)
-// With dup, idx9 lists for every (r, g) column and b cell the blobs (cell-order index) within
-// one cell in r and g, and `start` = offsets into idx9; otherwise n9 = 0 and `start` = cell
-// offsets into rec32.  Returns n9 through *n9_out (0 when the duplicated list is not built).
-static void build_blob_grid(const double* blobs, const double* dir, int B, bool want_dup, BlobGrid& g,
-                     unsigned char* tables, double* exact, int* n9_out) {
-  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, M = 0.0, Mb = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    lo[k] = hi[k] = B ? blobs[1 + k] : 0.0;
-    for (int b = 0; b < B; ++b) {
-      double v = blobs[4 * b + 1 + k];
-      lo[k] = std::fmin(lo[k], v);
-      hi[k] = std::fmax(hi[k], v);
-      M = std::fmax(M, std::fabs(v));
-    }
-  }
-  for (int b = 0; b < B; ++b) Mb = std::fmax(Mb, std::fabs(blobs[4 * b]));
-  g.inv_h = 1.0 / kGridCell;
-  g.ncell = 1;
-  for (int k = 0; k < 3; ++k) {
-    g.lo[k] = lo[k];
-    double span = std::floor((hi[k] - lo[k]) * g.inv_h) + 1.0;
-    g.G[k] = span > (double)kGridMax ? kGridMax : (int)span;
-    g.ncell *= g.G[k];
-  }
-  // fp32 pre-filter bounds.  Colour: with d the exact channel difference of a pair inside the
-  // gate and d' its fp32 evaluation from fp32-rounded colours, |d' - d| <= eta = 2^-24 (2M + 35);
-  // then sum d'^2 <= 300 + 60 eta + 3 eta^2 (+ fp32 summation error).  Bearing: a pair inside
-  // the gate has |expected| <= Mb + 0.5, so |d' - d| <= 2^-24 (2 Mb + 1.5).  Both doubled.
-  const double eta = 2.0 * std::ldexp(2.0 * M + 35.0, -24);
-  const double thr = (300.0 + 60.0 * eta + 3.0 * eta * eta + 1e-3) * (1.0 + 1e-6);
-  g.thr32 = thr < 3.0e38 ? (float)thr : INFINITY;
-  const double thrb = (0.5 + 2.0 * std::ldexp(2.0 * Mb + 1.5, -24) + 1e-6) * (1.0 + 1e-6);
-  g.thrb32 = thrb < 3.0e38 ? (float)thrb : INFINITY;
-  // The bearing model's screen: d' = fl(fl(bearing) - fl(e)) with e the expected bearing wrapped into [-pi, pi] in float64, then
-  // w' = fma(-k, fl(2 pi), d'), k = rint(d' fl(1 / 2 pi)).  |d' - d| <= 2^-24 2 (Mb + pi + 1); for a pair inside the gate k is the
-  // exact wrap's integer, |k| <= (Mb + pi) / 2 pi + 1, |fl(2 pi) - 2 pi| < 2^-22, and the fma rounds a value below 1 once:
-  // |w' - w| <= 2^-24 (2 (Mb + pi + 1) + 4 |k| + 1) <= 2^-24 (2.64 (Mb + pi) + 7).  Doubled, like the others.
-  const double thrbw = (0.5 + 2.0 * std::ldexp(2.64 * (Mb + 3.1415926535897932) + 7.0, -24) + 1e-6) * (1.0 + 1e-6);
-  g.thrb32w = thrbw < 3.0e38 ? (float)thrbw : INFINITY;
-  auto cell_of = [&](int b) {
-    int c[3];
-    for (int k = 0; k < 3; ++k) {
-      double q = std::floor((blobs[4 * b + 1 + k] - g.lo[k]) * g.inv_h);
-      c[k] = q < 0.0 ? 0 : (q > (double)(g.G[k] - 1) ? g.G[k] - 1 : (int)q);
-    }
-    return (c[0] * g.G[1] + c[1]) * g.G[2] + c[2];
-  };
-  std::vector<int> cell((size_t)std::max(B, 1)), cs((size_t)g.ncell + 1, 0), fill;
-  for (int b = 0; b < B; ++b) {
-    cell[b] = cell_of(b);
-    ++cs[cell[b] + 1];
-  }
-  for (int c = 0; c < g.ncell; ++c) cs[c + 1] += cs[c];
-  fill = cs;
-  const size_t cs_bytes = ((size_t)(g.ncell + 1) * 2 + 15) & ~(size_t)15;
-  memset(tables, 0, cs_bytes);
-  uint16_t* start = reinterpret_cast<uint16_t*>(tables);
-  float* rec32 = reinterpret_cast<float*>(tables + cs_bytes);
-  uint16_t* idx9 = reinterpret_cast<uint16_t*>(tables + cs_bytes + (size_t)B * 16);
-  // duplicated column lists: size known before laying out `order`
-  int n9 = 0;
-  std::vector<int> col_start;
-  if (want_dup) {
-    col_start.assign((size_t)g.ncell + 1, 0);
-    long total = 0;
-    for (int r = 0; r < g.G[0]; ++r)
-      for (int gg = 0; gg < g.G[1]; ++gg)
-        for (int k = 0; k < g.G[2]; ++k) {
-          col_start[(r * g.G[1] + gg) * g.G[2] + k] = (int)total;
-          for (int r2 = std::max(r - 1, 0); r2 <= std::min(r + 1, g.G[0] - 1); ++r2)
-            for (int g2 = std::max(gg - 1, 0); g2 <= std::min(gg + 1, g.G[1] - 1); ++g2) {
-              const int c = (r2 * g.G[1] + g2) * g.G[2] + k;
-              total += cs[c + 1] - cs[c];
-            }
-        }
-    col_start[g.ncell] = (int)total;
-    if (total + 3 <= 65535) n9 = (int)((total + 3 + 7) & ~7L);  // the walk reads up to three entries past a range
-  }
-  uint16_t* order = reinterpret_cast<uint16_t*>(tables + cs_bytes + (size_t)B * 16 + (size_t)n9 * 2);
-  for (int b = 0; b < B; ++b) {  // ascending b inside a cell
-    const int pos = fill[cell[b]]++;
-    order[pos] = (uint16_t)b;
-    rec32[4 * pos] = (float)blobs[4 * b + 1];
-    rec32[4 * pos + 1] = (float)blobs[4 * b + 2];
-    rec32[4 * pos + 2] = (float)blobs[4 * b + 3];
-    rec32[4 * pos + 3] = (float)blobs[4 * b];
-    double* e = exact + 6 * (size_t)pos;
-    e[0] = blobs[4 * b];
-    e[1] = blobs[4 * b + 1];
-    e[2] = blobs[4 * b + 2];
-    e[3] = blobs[4 * b + 3];
-    e[4] = dir[2 * b];
-    e[5] = dir[2 * b + 1];
-  }
-  if (n9 > 0) {
-    int w = 0;
-    for (int r = 0; r < g.G[0]; ++r)
-      for (int gg = 0; gg < g.G[1]; ++gg)
-        for (int k = 0; k < g.G[2]; ++k) {
-          start[(r * g.G[1] + gg) * g.G[2] + k] = (uint16_t)w;
-          for (int r2 = std::max(r - 1, 0); r2 <= std::min(r + 1, g.G[0] - 1); ++r2)
-            for (int g2 = std::max(gg - 1, 0); g2 <= std::min(gg + 1, g.G[1] - 1); ++g2) {
-              const int c = (r2 * g.G[1] + g2) * g.G[2] + k;
-              for (int t = cs[c]; t < cs[c + 1]; ++t) idx9[w++] = (uint16_t)t;
-            }
-        }
-    start[g.ncell] = (uint16_t)w;
-    for (; w < n9; ++w) idx9[w] = 0;
-  } else {
-    for (int c = 0; c <= g.ncell; ++c) start[c] = (uint16_t)cs[c];
-  }
-  *n9_out = n9;
-}
-
 // rows: particles the lists have room for -- all of them (the hand-off routes), or the capped number of second-chance rows
 // (ADVICE round 2 / VERDICT round 3: the second chance used to allocate lists for ALL P particles with the route, 6.4 GB at
 // 100 000 x 2 000, for the few percent a scan flags at worst)
@@ -342,74 +138,6 @@ static int ensure_handoff(pk_filter* f, int B, int slots, bool lists = true, boo
   if ((rc = dev_reserve(f, &f->fh.lmpass, &f->fh_cap_l, need_l, need_l))) return rc;
   if ((rc = dev_reserve(f, &f->fh.bcount, &f->fh_cap_b, need_b, need_b))) return rc;
   return dev_lazy(f, &f->fh.pflag, (size_t)f->d.P);
-}
-
-// Host half of the ML scan upload: blobs, ray directions, exact records and the association tables
-// are laid out in a pinned staging slot (no device work; may synchronise only to grow buffers).
-// block: ctl | blobs (4B) | dir (2B) | exact (6B) doubles | tables, and behind them -- only for a scan in which some blob has a
-// range (rs->any; pk_scan_ranges) -- the range rows (2B doubles in scan order, 2B in cell order): a scan without stages the bytes
-// it always staged.
-int stage_ml_scan(pk_filter* f, const double* blobs, int B, const RangeScan* rs) {
-  int rc;
-  if (B > 65535) return fail(PK_ERR_UNSUPPORTED, "maximum-likelihood association handles at most 65535 blobs per scan (got %d)", B);
-  // the general EKF kernel (every ML route's last resort) builds per-particle chains in LDS
-  if (observe_general_lds_bytes(f->d.lay.Lp, B) > kMaxDynLds)
-    return fail(PK_ERR_UNSUPPORTED,
-                "maximum-likelihood association: %d landmarks + 2 x %d blobs need %zu bytes of LDS chains per particle, the "
-                "workgroup has %zu", f->d.lay.Lp, B, observe_general_lds_bytes(f->d.lay.Lp, B), (size_t)kMaxDynLds);
-  if ((rc = ensure_ids_capacity(f, B))) return rc;
-  pk_filter::Staged& sg = f->staged;
-  sg.valid = false;
-  sg.uploaded = false;
-  sg.with_ranges = rs && rs->armed;
-  sg.ranged = rs && rs->any;
-  const size_t rng_bytes = sg.ranged ? (size_t)B * 4 * sizeof(double) : 0;
-  const int ncell_max = kGridMax * kGridMax * kGridMax;
-  const size_t tab_max = (blob_grid_table_bytes(ncell_max, B, 9 * B + 16) + 15) & ~(size_t)15;
-  const size_t o_blobs = kCtlBytes;
-  const size_t o_dir = o_blobs + (size_t)B * 4 * sizeof(double);
-  const size_t o_exact = o_dir + (size_t)B * 2 * sizeof(double);
-  const size_t o_tab = o_exact + (size_t)B * 6 * sizeof(double);
-  unsigned char* st = nullptr;
-  int slot = 0;
-  if ((rc = take_stage(f, o_tab + tab_max + 16 + rng_bytes, &st, &slot))) return rc;
-  if ((rc = ensure_scan_capacity(f, o_tab + tab_max + 16 + rng_bytes))) return rc;
-  memset(st, 0, kCtlBytes);
-  memmove(st + o_blobs, blobs, (size_t)B * 4 * sizeof(double));
-  double* dir = reinterpret_cast<double*>(st + o_dir);
-  blob_directions(blobs, B, dir);
-  // the grid kernel keeps landmark indices as u16 and its tables in LDS
-  sg.use_grid = f->opt.assoc_kernel == 0 && f->d.lay.L <= 65535;
-  sg.tab_bytes = 0;
-  sg.n9 = 0;
-  sg.g = BlobGrid{};
-  if (sg.use_grid) {
-    // duplicated column lists when they fit in LDS (about 48 B per blob), else the 9-range walk
-    bool dup = f->opt.assoc_dup && assoc_grid_lds_bytes(ncell_max, B, 9 * B + 16) <= kMaxDynLds;
-    build_blob_grid(blobs, dir, B, dup, sg.g, st + o_tab, reinterpret_cast<double*>(st + o_exact), &sg.n9);
-    sg.tab_bytes = (blob_grid_table_bytes(sg.g.ncell, B, sg.n9) + 15) & ~(size_t)15;
-    if (assoc_grid_lds_bytes(sg.g.ncell, B, sg.n9) > kMaxDynLds) sg.use_grid = false;  // scan too large for LDS tables
-  }
-  sg.B = B;
-  sg.st = st;
-  sg.slot = slot;
-  if (sg.ranged) {
-    double* rows = reinterpret_cast<double*>(st + staged_range_offset(sg));
-    memcpy(rows, rs->rv.data(), (size_t)B * 2 * sizeof(double));
-    double* cell = rows + 2 * (size_t)B;
-    if (sg.use_grid) {  // beside the exact records: row t is blob order[t]'s
-      const size_t cs_b = ((size_t)(sg.g.ncell + 1) * 2 + 15) & ~(size_t)15;
-      const uint16_t* order = reinterpret_cast<const uint16_t*>(st + o_tab + cs_b + (size_t)B * 16 + (size_t)sg.n9 * 2);
-      for (int t = 0; t < B; ++t) {
-        cell[2 * (size_t)t] = rs->rv[2 * (size_t)order[t]];
-        cell[2 * (size_t)t + 1] = rs->rv[2 * (size_t)order[t] + 1];
-      }
-    } else {
-      memcpy(cell, rows, (size_t)B * 2 * sizeof(double));
-    }
-  }
-  sg.valid = true;
-  return PK_OK;
 }
 
 // Maps of at most 512 landmarks: the publish / subscribe instance (k_step_pub<1, 256> on candidate lists) or k_step_fused?  The former's
@@ -502,16 +230,12 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
                         bool whole = false, const RangeScan* rs = nullptr) {
   int rc;
   pk_filter::Staged& sg = f->staged;
-  const size_t o_blobs = kCtlBytes;
-  const size_t o_dir = o_blobs + (size_t)B * 4 * sizeof(double);
-  const size_t o_exact = o_dir + (size_t)B * 2 * sizeof(double);
-  const size_t o_tab = o_exact + (size_t)B * 6 * sizeof(double);
-  if (!(sg.valid && sg.B == B && blobs == reinterpret_cast<const double*>(sg.st + o_blobs)))
+  if (!is_staged_scan(f, blobs, B))
     if ((rc = stage_ml_scan(f, blobs, B, rs))) return rc;
   sg.valid = false;  // consumed
+  const MlScanLayout& lay = sg.lay;
   if (!sg.uploaded) {
-    if ((rc = upload_scan(f, sg.st, staged_upload_bytes(sg)))) return rc;
-    if ((rc = note_upload(f, sg.slot))) return rc;
+    if ((rc = upload_scan(f, sg.st, lay.upload_bytes, sg.slot))) return rc;
   }
   sg.uploaded = false;
   f->gmax_fused = false;
@@ -522,17 +246,16 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
   scan.B = B;
   scan.grid = sg.g;
   scan.n9 = sg.n9;
-  scan.blobs = reinterpret_cast<const double*>(f->scan_dev + o_blobs);
-  scan.dir = reinterpret_cast<const double*>(f->scan_dev + o_dir);
-  if (sg.ranged) {
-    scan.rng = reinterpret_cast<const double*>(f->scan_dev + staged_range_offset(sg));
-    scan.rng_cell = scan.rng + 2 * (size_t)B;
+  scan.blobs = reinterpret_cast<const double*>(f->scan_dev + lay.blobs);
+  scan.dir = reinterpret_cast<const double*>(f->scan_dev + lay.dir);
+  if (lay.rng) {
+    scan.rng = reinterpret_cast<const double*>(f->scan_dev + lay.rng);
+    scan.rng_cell = reinterpret_cast<const double*>(f->scan_dev + lay.rng_cell);
   }
   if (sg.use_grid) {
-    const size_t cs_b = ((size_t)(sg.g.ncell + 1) * 2 + 15) & ~(size_t)15;
-    scan.tables = f->scan_dev + o_tab;
-    scan.exact = reinterpret_cast<const double*>(f->scan_dev + o_exact);
-    scan.order = reinterpret_cast<const unsigned short*>(f->scan_dev + o_tab + cs_b + (size_t)B * 16 + (size_t)sg.n9 * 2);
+    scan.tables = f->scan_dev + lay.tables;
+    scan.exact = reinterpret_cast<const double*>(f->scan_dev + lay.exact);
+    scan.order = reinterpret_cast<const unsigned short*>(f->scan_dev + lay.order);
   }
   if (out) {
     *out = al;
@@ -591,24 +314,18 @@ static int dense_observe(pk_filter* f, const double* blobs, int32_t B, const int
   if (dense_lds_bytes(lay.Lp, B) > kMaxDynLds)
     return fail(PK_ERR_UNSUPPORTED, "dense observe: %d landmarks and %d blobs need %zu bytes of LDS per particle, the workgroup has %zu",
                 lay.Lp, B, dense_lds_bytes(lay.Lp, B), (size_t)kMaxDynLds);
-  // block: ctl | blobs (4B doubles) | dir (2B doubles) | ids (B int32)
-  const size_t o_blobs = kCtlBytes;
-  const size_t o_dir = o_blobs + (size_t)B * 4 * sizeof(double);
-  const size_t o_ids = o_dir + (size_t)B * 2 * sizeof(double);
-  const size_t total = (o_ids + (size_t)B * sizeof(int32_t) + 15) & ~(size_t)15;
+  const DenseScanLayout blk = dense_scan_layout(B);
   unsigned char* st = nullptr;
   int slot = 0;
-  if ((rc = take_stage(f, total, &st, &slot))) return rc;
-  if ((rc = ensure_scan_capacity(f, total))) return rc;
+  if ((rc = take_stage(f, blk.upload_bytes, &st, &slot))) return rc;
   if (ids_out && !ids && (rc = ensure_ids_capacity(f, B))) return rc;
   memset(st, 0, kCtlBytes);
   if (B > 0) {
-    memmove(st + o_blobs, blobs, (size_t)B * 4 * sizeof(double));
-    blob_directions(reinterpret_cast<const double*>(st + o_blobs), B, reinterpret_cast<double*>(st + o_dir));
-    if (ids) memcpy(st + o_ids, ids, (size_t)B * sizeof(int32_t));
+    memmove(st + blk.blobs, blobs, (size_t)B * 4 * sizeof(double));
+    blob_directions(reinterpret_cast<const double*>(st + blk.blobs), B, reinterpret_cast<double*>(st + blk.dir));
+    if (ids) memcpy(st + blk.ids, ids, (size_t)B * sizeof(int32_t));
   }
-  if ((rc = upload_scan(f, st, total))) return rc;
-  if ((rc = note_upload(f, slot))) return rc;
+  if ((rc = upload_scan(f, st, blk.upload_bytes, slot))) return rc;
   ObserveExtras ex;
   ex.reset = reset;
   ex.gmax_key = ctl_gmax_key(f);
@@ -616,9 +333,9 @@ static int dense_observe(pk_filter* f, const double* blobs, int32_t B, const int
     Span t(f, update ? PK_T_OBSERVE : PK_T_ASSOC);
     ScanTables scan;
     scan.B = B;
-    scan.blobs = reinterpret_cast<const double*>(f->scan_dev + o_blobs);
-    scan.dir = reinterpret_cast<const double*>(f->scan_dev + o_dir);
-    const int32_t* ids_in = ids ? reinterpret_cast<const int32_t*>(f->scan_dev + o_ids) : nullptr;
+    scan.blobs = reinterpret_cast<const double*>(f->scan_dev + blk.blobs);
+    scan.dir = reinterpret_cast<const double*>(f->scan_dev + blk.dir);
+    const int32_t* ids_in = ids ? reinterpret_cast<const int32_t*>(f->scan_dev + blk.ids) : nullptr;
     int32_t* ids_to = (ids_out && !ids) ? f->ids_dev : nullptr;
     launch_observe_dense(f->stream, f->d, scan, ids_in, ids_to, f->qt16, update, ex);
   }
@@ -629,15 +346,7 @@ static int dense_observe(pk_filter* f, const double* blobs, int32_t B, const int
   } else {
     f->gmax_fused = false;  // the control words were overwritten by this upload
   }
-  if (ids_out && B > 0) {
-    if (ids) {
-      for (int64_t p = 0; p < f->d.P; ++p) memcpy(ids_out + (size_t)p * B, ids, (size_t)B * 4);
-    } else {
-      PK_HIP(hipMemcpyAsync(ids_out, f->ids_dev, (size_t)f->d.P * B * 4, hipMemcpyDeviceToHost, f->stream));
-      PK_HIP(hipStreamSynchronize(f->stream));
-    }
-  }
-  return PK_OK;
+  return return_ids(f, ids_out, B, ids);
 }
 
 // ---- the one-pass kinds (ScanPlan::onepass) in three pieces, so that the sharded filter can run the middle one on a part of the
@@ -828,76 +537,6 @@ static int onepass_finish(pk_filter* f, const AssocLaunch& al, const ObserveExtr
   return PK_OK;
 }
 
-// A scan with supplied ids on the device, in one block: ctl | blobs (4B doubles) | first (Lp int32) | next (B int32), and with
-// `with_ids` the id row itself behind them (B int32; k_propose reads it).  first / next: the landmark -> blob chains shared by all
-// particles, in scan order (prkt_core_v2.py:88).  The one place that lays this block out, for pk_observe and pk_propose alike.
-struct KnownScan {
-  size_t o_blobs = 0, o_first = 0, o_next = 0, o_ids = 0;
-  size_t o_rng = 0;               // the range rows ([B][2] range, variance) of a scan in which some blob has one, behind everything else; 0: none
-  int n_unmatched = 0;            // blobs with id 0
-  bool single_sightings = true;   // no landmark is matched by more than one blob
-};
-static int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, bool with_ids, KnownScan* out,
-                             const RangeScan* rs = nullptr) {
-  int rc;
-  const MapLayout& lay = f->d.lay;
-  KnownScan k;
-  k.o_blobs = kCtlBytes;
-  k.o_first = k.o_blobs + (size_t)B * 4 * sizeof(double);
-  k.o_next = k.o_first + (size_t)lay.Lp * sizeof(int32_t);
-  k.o_ids = k.o_next + (size_t)B * sizeof(int32_t);
-  size_t total = k.o_ids + (with_ids ? (size_t)B * sizeof(int32_t) : 0);
-  if (rs && rs->any) {
-    k.o_rng = (total + 15) & ~(size_t)15;
-    total = k.o_rng + (size_t)B * 2 * sizeof(double);
-  }
-  unsigned char* st = nullptr;
-  int slot = 0;
-  if ((rc = take_stage(f, total, &st, &slot))) return rc;
-  if ((rc = ensure_scan_capacity(f, total))) return rc;
-  memset(st, 0, kCtlBytes);
-  if (B > 0) memcpy(st + k.o_blobs, blobs, (size_t)B * 4 * sizeof(double));
-  if (with_ids && B > 0) memcpy(st + k.o_ids, ids, (size_t)B * sizeof(int32_t));
-  if (k.o_rng) memcpy(st + k.o_rng, rs->rv.data(), (size_t)B * 2 * sizeof(double));
-  int32_t* first = reinterpret_cast<int32_t*>(st + k.o_first);
-  int32_t* next = reinterpret_cast<int32_t*>(st + k.o_next);
-  std::vector<int32_t> last((size_t)lay.Lp, -1);
-  for (int l = 0; l < lay.Lp; ++l) first[l] = -1;
-  for (int b = 0; b < B; ++b) {
-    next[b] = -1;
-    int id = ids[b];
-    if (id == 0) {
-      ++k.n_unmatched;
-      continue;
-    }
-    if (first[id - 1] < 0) {
-      first[id - 1] = b;
-    } else {
-      next[last[id - 1]] = b;
-      k.single_sightings = false;
-    }
-    last[id - 1] = b;
-  }
-  if ((rc = upload_scan(f, st, total))) return rc;
-  if ((rc = note_upload(f, slot))) return rc;
-  *out = k;
-  return PK_OK;
-}
-// ... and the device views of that block: a scan with supplied ids has B and the blobs alone
-static ScanTables known_scan_tables(const pk_filter* f, const KnownScan& ks, int B) {
-  ScanTables scan;
-  scan.B = B;
-  scan.blobs = reinterpret_cast<const double*>(f->scan_dev + ks.o_blobs);
-  return scan;
-}
-static KnownChains known_chains(const pk_filter* f, const KnownScan& ks) {
-  KnownChains c;
-  c.first = reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_first);
-  c.next = reinterpret_cast<const int32_t*>(f->scan_dev + ks.o_next);
-  c.n_unmatched = ks.n_unmatched;
-  return c;
-}
-
 // Behind the observe launches of a growing filter's non-empty scan (pk_observe, pk_step; pk_propose / pk_propose_odom with
 // pk_proposal_grow): :92-95 for every particle at its live pose, on the ids the association left in HBM -- or, where the last
 // observe's one-pass kernel left them (grow_bits), on its bit rows -- (every particle's slot is its own now), then retirement's pass
@@ -925,29 +564,19 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   // the ranges of this scan (pk_scan_ranges): armed ones are consumed here, whatever follows; a staged scan brought its own, and
   // is held to the same refusals once more (the filter may have changed since pk_stage_scan) -- refused, it is discarded
   RangeScan rs;
-  const bool from_staged = f->staged.valid && B > 0 && blobs == reinterpret_cast<const double*>(f->staged.st + kCtlBytes);
-  if (!from_staged) {
+  if (!is_staged_scan(f, blobs, B)) {
     if ((rc = ranges_take(f, "pk_observe", B, &rs))) return rc;
   } else if (f->staged.with_ranges && (rc = refuse_ranges(f, "pk_observe", B, f->staged.B))) {
     f->staged.valid = false;
     return rc;
   }
-  if (B < 0 || (B > 0 && !blobs)) return fail(PK_ERR_INVALID, "pk_observe: bad blobs");
-  if (!f->map_loaded) return fail(PK_ERR_STATE, "pk_observe: no map uploaded (pk_upload_map)");
+  if ((rc = check_scan_shape(f, "pk_observe", blobs, B))) return rc;
   if (f->split.active) return fail(PK_ERR_STATE, "pk_observe: a split observe is in progress (pk_observe_staged_range with last = 1 ends it)");
   if ((rc = use_device(f))) return rc;
-  const MapLayout& lay = f->d.lay;
-  const int L = lay.L;
-  for (int i = 0; i < 4 * B; ++i)
-    if (!std::isfinite(blobs[i])) return fail(PK_ERR_INVALID, "pk_observe: blob %d is not finite", i / 4);
-  static const int32_t no_ids = 0;
-  if (!ids && B == 0) ids = &no_ids;  // an empty scan needs no association: every landmark keeps its state
-  if (ids)
-    for (int b = 0; b < B; ++b)
-      if (ids[b] < 0 || ids[b] > L) return fail(PK_ERR_INVALID, "pk_observe: ids[%d] = %d outside 0..%d", b, ids[b], L);
+  if ((rc = check_scan_values(f, "pk_observe", blobs, B, &ids))) return rc;
   // section 8(f4) on the device: the unmatched blobs of every particle go through the new-landmark bookkeeping behind the observe
   const bool grow = f->grow_on && B > 0;
-  if (grow && ids) return fail(PK_ERR_STATE, "pk_observe: the new-landmark bookkeeping (pk_grow_enable) follows the maximum-likelihood association: no ids");
+  if (grow && ids) return refuse_grow_ids("pk_observe");
   if (grow && f->dense)
     return fail(PK_ERR_STATE, "pk_observe: the new-landmark bookkeeping (pk_grow_enable) writes the compact landmark layout; this filter "
                               "is on the dense one (a covariance or Qt that couples position and colour)");
@@ -961,7 +590,7 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
     f->staged.valid = false;  // a staged ML scan does not survive another observe
     KnownScan ks;
     if ((rc = upload_known_scan(f, blobs, B, ids, false, &ks, &rs))) return rc;
-    if (ks.o_rng) ex.rng = reinterpret_cast<const double*>(f->scan_dev + ks.o_rng);
+    if (ks.lay.rng) ex.rng = reinterpret_cast<const double*>(f->scan_dev + ks.lay.rng);
     ex.single_sightings = ks.single_sightings;
     ex.gmax_key = ctl_gmax_key(f);
     {
@@ -971,9 +600,7 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
     PK_LAUNCH_CHECK("pk_observe");
     observe_done(f);
     f->route = PK_ROUTE_KNOWN_IDS;
-    if (ids_out)
-      for (int64_t p = 0; p < f->d.P; ++p) memcpy(ids_out + (size_t)p * B, ids, (size_t)B * 4);
-    return PK_OK;
+    return return_ids(f, ids_out, B, ids);
   }
   // maximum-likelihood association on the device
   AssocLaunch al;
@@ -1030,11 +657,7 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   PK_LAUNCH_CHECK("pk_observe");
   observe_done(f);
   if (grow && (rc = grow_bookkeeping(f, "pk_observe", al.scan, B))) return rc;
-  if (ids_out && B > 0) {
-    PK_HIP(hipMemcpyAsync(ids_out, f->ids_dev, (size_t)f->d.P * B * 4, hipMemcpyDeviceToHost, f->stream));
-    PK_HIP(hipStreamSynchronize(f->stream));
-  }
-  return PK_OK;
+  return return_ids(f, ids_out, B, nullptr);
 }
 
 // A proposal step's scan (pk_api_propose.hip) on the device, ahead of k_propose: supplied ids as pk_observe uploads them -- the block
@@ -1051,12 +674,12 @@ int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* i
     f->staged.valid = false;
     KnownScan ks;
     if ((rc = upload_known_scan(f, blobs, B, ids, true, &ks, rs))) return rc;
-    if (ks.o_rng) out->rng = reinterpret_cast<const double*>(f->scan_dev + ks.o_rng);
+    if (ks.lay.rng) out->rng = reinterpret_cast<const double*>(f->scan_dev + ks.lay.rng);
     f->gmax_fused = false;
     out->scan = known_scan_tables(f, ks, B);
     out->known = known_chains(f, ks);
     out->known.n_unmatched = 0;  // (k_observe_proposed takes the weight from k_propose, unmatched blobs and all)
-    out->ids = reinterpret_cast<int32_t*>(f->scan_dev + ks.o_ids);
+    out->ids = reinterpret_cast<int32_t*>(f->scan_dev + ks.lay.ids);
     return PK_OK;
   }
   AssocLaunch al;
@@ -1085,24 +708,6 @@ int pk_observe_fresh(pk_filter* f, const double* blobs, int32_t B, const int32_t
   return observe_impl(f, blobs, B, ids, ids_out, true);
 }
 
-int pk_stage_scan(pk_filter* f, const double* blobs, int32_t B) {
-  if (!f) return fail(PK_ERR_INVALID, "pk_stage_scan: NULL handle");
-  RangeScan rs;
-  if (int rr = ranges_take(f, "pk_stage_scan", B, &rs)) return rr;
-  if (B < 1 || !blobs) return fail(PK_ERR_INVALID, "pk_stage_scan: needs at least one blob");
-  if (!f->map_loaded) return fail(PK_ERR_STATE, "pk_stage_scan: no map uploaded (pk_upload_map)");
-  for (int i = 0; i < 4 * B; ++i)
-    if (!std::isfinite(blobs[i])) return fail(PK_ERR_INVALID, "pk_stage_scan: blob %d is not finite", i / 4);
-  int rc;
-  if ((rc = use_device(f))) return rc;
-  if (f->dense) {  // no tables to build: the blobs wait on the host
-    f->dense_staged.assign(blobs, blobs + 4 * (size_t)B);
-    return PK_OK;
-  }
-  f->dense_staged.clear();
-  return stage_ml_scan(f, blobs, B, &rs);
-}
-
 int pk_observe_staged(pk_filter* f, int32_t fresh) {
   if (!f) return fail(PK_ERR_INVALID, "pk_observe_staged: NULL handle");
   if (f->dense && !f->dense_staged.empty()) {
@@ -1111,8 +716,7 @@ int pk_observe_staged(pk_filter* f, int32_t fresh) {
     return observe_impl(f, b.data(), (int32_t)(b.size() / 4), nullptr, nullptr, fresh != 0);
   }
   if (!f->staged.valid) return fail(PK_ERR_STATE, "pk_observe_staged: no staged scan (pk_stage_scan)");
-  const double* blobs = reinterpret_cast<const double*>(f->staged.st + kCtlBytes);
-  return observe_impl(f, blobs, f->staged.B, nullptr, nullptr, fresh != 0);
+  return observe_impl(f, staged_blobs(f->staged), f->staged.B, nullptr, nullptr, fresh != 0);
 }
 
 int pk_staged_takes_regs(pk_filter* f) {
@@ -1136,10 +740,9 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
     if (sp.active) return fail(PK_ERR_STATE, "pk_observe_staged_range: the previous split observe was not finished (last = 1)");
     if (!pk_staged_takes_regs(f))
       return fail(PK_ERR_STATE, "pk_observe_staged_range: needs a staged scan that takes the register route (pk_staged_takes_regs)");
-    const double* blobs = reinterpret_cast<const double*>(f->staged.st + kCtlBytes);
     sp.reset = fresh != 0;
     sp.al = AssocLaunch();
-    if ((rc = enqueue_association(f, blobs, f->staged.B, false, true, &sp.al))) return rc;
+    if ((rc = enqueue_association(f, staged_blobs(f->staged), f->staged.B, false, true, &sp.al))) return rc;
     if (!sp.al.plan.ranged()) return fail(PK_ERR_STATE, "pk_observe_staged_range: the scan did not take the register route");
     if ((rc = onepass_prepare(f, sp.al, &sp.pub, p1 > p0 ? p0 : 0))) return rc;
     sp.active = true;
@@ -1170,14 +773,12 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
 int pk_associate(pk_filter* f, const double* blobs, int32_t B, int32_t* ids_out) {
   if (!f || !ids_out) return fail(PK_ERR_INVALID, "pk_associate: NULL argument");
   RangeScan rs;
-  if (int rr = ranges_take(f, "pk_associate", B, &rs)) return rr;
-  if (B < 0 || (B > 0 && !blobs)) return fail(PK_ERR_INVALID, "pk_associate: bad blobs");
-  if (!f->map_loaded) return fail(PK_ERR_STATE, "pk_associate: no map uploaded (pk_upload_map)");
-  if (B == 0) return PK_OK;
   int rc;
+  if ((rc = ranges_take(f, "pk_associate", B, &rs))) return rc;
+  if ((rc = check_scan_shape(f, "pk_associate", blobs, B))) return rc;
+  if (B == 0) return PK_OK;
   if ((rc = use_device(f))) return rc;
-  for (int i = 0; i < 4 * B; ++i)
-    if (!std::isfinite(blobs[i])) return fail(PK_ERR_INVALID, "pk_associate: blob %d is not finite", i / 4);
+  if ((rc = check_scan_values(f, "pk_associate", blobs, B))) return rc;
   if (f->dense) return dense_observe(f, blobs, B, nullptr, ids_out, false, false);
   if ((rc = ensure_colour_rows(f))) return rc;  // (the colour table's mode goes on: nothing is updated)
   {
@@ -1188,9 +789,7 @@ int pk_associate(pk_filter* f, const double* blobs, int32_t B, int32_t* ids_out)
   }
   if (rc) return rc;
   PK_LAUNCH_CHECK("pk_associate");
-  PK_HIP(hipMemcpyAsync(ids_out, f->ids_dev, (size_t)f->d.P * B * 4, hipMemcpyDeviceToHost, f->stream));
-  PK_HIP(hipStreamSynchronize(f->stream));
-  return PK_OK;
+  return return_ids(f, ids_out, B, nullptr);
 }
 
 int pk_set_measurement_model(pk_filter* f, int32_t model) {

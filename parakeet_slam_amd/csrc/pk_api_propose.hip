@@ -67,18 +67,9 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
   if ((rc = refuse_proposal(f, who))) return rc;
   // pk_proposal_grow: the new-landmark bookkeeping follows the step -- at the sampled poses, on the ids k_propose settles
   const bool grow = f->grow_on && B > 0;
-  if (grow && ids)
-    return fail(PK_ERR_STATE, "%s: the new-landmark bookkeeping (pk_grow_enable) follows the maximum-likelihood association: no ids", who);
-  if (B < 0 || (B > 0 && !blobs)) return fail(PK_ERR_INVALID, "%s: bad blobs", who);
-  if (!f->map_loaded) return fail(PK_ERR_STATE, "%s: no map uploaded (pk_upload_map)", who);
-  const int L = f->d.lay.L;
-  for (int i = 0; i < 4 * B; ++i)
-    if (!std::isfinite(blobs[i])) return fail(PK_ERR_INVALID, "%s: blob %d is not finite", who, i / 4);
-  static const int32_t no_ids = 0;
-  if (!ids && B == 0) ids = &no_ids;  // an empty scan needs no association
-  if (ids)
-    for (int b = 0; b < B; ++b)
-      if (ids[b] < 0 || ids[b] > L) return fail(PK_ERR_INVALID, "%s: ids[%d] = %d outside 0..%d", who, b, ids[b], L);
+  if (grow && ids) return refuse_grow_ids(who);
+  if ((rc = check_scan_shape(f, who, blobs, B))) return rc;
+  if ((rc = check_scan_values(f, who, blobs, B, &ids))) return rc;
   if (!ids && B > 65535) return fail(PK_ERR_UNSUPPORTED, "%s: at most 65535 blobs per scan (got %d)", who, B);
   if (!ids && observe_general_lds_bytes(f->d.lay.Lp, B) > kMaxDynLds)  // (supplied ids: shared chains, no LDS tables)
     return fail(PK_ERR_UNSUPPORTED, "%s: %d landmarks + 2 x %d blobs need %zu bytes of LDS chains per particle, the workgroup has %zu", who,
@@ -163,15 +154,7 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
   q.valid = true;
   // a growing filter (pk_proposal_grow): pk_observe's own tail, at the sampled poses on the settled ids (0 = unmatched; no bit rows)
   if (grow && (rc = grow_bookkeeping(f, who, sc.scan, B))) return rc;
-  if (ids_out && B > 0) {
-    if (ids) {
-      for (int64_t p = 0; p < f->d.P; ++p) memcpy(ids_out + (size_t)p * B, ids, (size_t)B * 4);
-    } else {
-      PK_HIP(hipMemcpyAsync(ids_out, f->ids_dev, (size_t)f->d.P * B * 4, hipMemcpyDeviceToHost, f->stream));
-      PK_HIP(hipStreamSynchronize(f->stream));
-    }
-  }
-  return PK_OK;
+  return return_ids(f, ids_out, B, ids);
 }
 
 }  // namespace

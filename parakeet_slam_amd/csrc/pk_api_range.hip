@@ -1,6 +1,6 @@
 // Range-bearing scans behind the C ABI (pk_filter.hpp): pk_scan_ranges arms the ranges of the next scan, the calls that take blobs
 // consume them (ranges_take), and what such a scan has no kernel for is said here, once (refuse_ranges).  Host orchestration only:
-// the ranges travel in the scan's own staging block (pk_api_observe.hip), the kernels are the range instances of pk_k_observe.hip
+// the ranges travel in the scan's own staging block (pk_api_scan.hip, pk_scan_block.hpp), the kernels are the range instances of pk_k_observe.hip
 // and pk_k_assoc.hip, and pk_probe_range lives beside its kernels in pk_k_mathprobe.hip.
 #include "pk_filter.hpp"
 

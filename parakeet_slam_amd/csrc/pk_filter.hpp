@@ -1,7 +1,8 @@
 // The filter behind the C ABI (include/parakeet_slam.h): struct pk_filter and what every part of the host layer needs to work on
 // it.  Private to the pk_api*.hip files, which divide the ABI between them:
 //   pk_api.hip          lifecycle, transfers, motion, resample, the step, new-landmark bookkeeping, options, timing, the probe
-//   pk_api_observe.hip  the observe pipeline: staging, routing, association, the one-pass stages, the colour table's host side
+//   pk_api_observe.hip  the observe pipeline: routing, association, the one-pass stages, the colour table's host side
+//   pk_api_scan.hip     how a scan gets onto the device: the staging ring, the per-scan blocks, the scan-taking calls' argument checks
 //   pk_api_shard.hip    the multi-GPU protocol: host-side, device-resident and balanced
 //   pk_api_path.hip     the path estimate: the ring of resampled generations, its transfers, trace and summaries, the trunk of
 //                       settled rows, the best particle
@@ -27,6 +28,7 @@
 #include "pk_devmem.hpp"
 #include "pk_kernels.hpp"
 #include "pk_pub_layout.hpp"
+#include "pk_scan_block.hpp"
 
 using namespace pk;
 
@@ -218,7 +220,7 @@ struct pk_filter {
   DevMem<HipRaw> mem;   // owns every device and pinned block below and in d, fh, grow, bal (dev_alloc / dev_reserve / host_alloc)
   // workspaces
   double* z_dev = nullptr;        // P x 3
-  unsigned char* scan_dev = nullptr;  // per-scan block: ctl | blobs | chains or association tables
+  unsigned char* scan_dev = nullptr;  // per-scan block (pk_scan_block.hpp)
   size_t scan_cap = 0;
   bool gmax_fused = false;  // ctl holds the max of the current log-weights (set by observe)
   int32_t* ids_dev = nullptr;     // P x B
@@ -252,10 +254,10 @@ struct pk_filter {
     BlobGrid g{};
     int n9 = 0;
     bool use_grid = false;
-    size_t tab_bytes = 0;
+    MlScanLayout lay{};  // where everything lies in st (pk_scan_block.hpp); lay.upload_bytes: what the device needs of it
     bool uploaded = false;  // pk_step sent the block to the device together with the motion kernel
     bool with_ranges = false;  // the scan was staged with ranges named for it (pk_scan_ranges) ...
-    bool ranged = false;       // ... of which at least one is finite: 32 B bytes of range rows lie behind the block (staged_upload_bytes)
+    bool ranged = false;       // ... of which at least one is finite: 32 B bytes of range rows lie behind the block (lay.rng)
   } staged;
   // pk_scan_ranges: the ranges of the next scan, on the host until a call that takes blobs consumes them (pk_api_range.hip)
   struct Ranges {
@@ -472,13 +474,7 @@ inline void poses_change(pk_filter* f) {
   if (f) f->pose_part_ok = false;
 }
 
-// One device block per scan, filled by ONE host->device copy:
-//   [ctl: kGmaxKeys running-max keys (u64), flagged-particle count (u32)] [blobs 4B f64] then either
-//   known ids:  [first Lp i32] [next B i32]
-//   ML:         [dir 2B f64] [exact 6B f64] [association tables]
-// The copy also zeroes ctl, which is how every observe starts with a fresh max / count.
-constexpr size_t kCtlBytes = 8 * kGmaxKeys + 64;  // running-max keys, then the flagged-particle count, the route control words and the publish table's figures
-
+// the control words at the head of the per-scan block (kCtlBytes, pk_scan_block.hpp)
 inline unsigned long long* ctl_gmax_key(pk_filter* f) { return reinterpret_cast<unsigned long long*>(f->scan_dev); }
 inline unsigned* ctl_n_flagged(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys); }
 inline unsigned* ctl_cand_over(pk_filter* f) { return reinterpret_cast<unsigned*>(f->scan_dev + 8 * kGmaxKeys + 4); }
@@ -521,15 +517,10 @@ struct StepMotion {
 // else they carry over and pk_resample_adaptive ends it with the threshold *gate
 int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed, uint64_t draw, const double* blobs,
               int32_t B, const int32_t* ids, double u, int32_t weight_domain, const double* gate);
-// bytes of a staged ML scan block that the device needs: ctl | blobs + directions | exact records | [tables] | [range rows]
-// (staged_range_offset: where the range rows of a ranged scan lie -- [B][2] in scan order, then [B][2] in cell order)
-inline size_t staged_range_offset(const pk_filter::Staged& sg) {
-  const size_t o_exact = kCtlBytes + (size_t)sg.B * 6 * sizeof(double);
-  const size_t o_tab = o_exact + (size_t)sg.B * 6 * sizeof(double);
-  return sg.use_grid ? o_tab + sg.tab_bytes : o_exact;
-}
-inline size_t staged_upload_bytes(const pk_filter::Staged& sg) {
-  return staged_range_offset(sg) + (sg.ranged ? (size_t)sg.B * 4 * sizeof(double) : 0);
+// the staged scan's own copy of its blobs, and "these blobs are the staged scan": neither staged nor (pk_step) uploaded again
+inline const double* staged_blobs(const pk_filter::Staged& sg) { return reinterpret_cast<const double*>(sg.st + sg.lay.blobs); }
+inline bool is_staged_scan(const pk_filter* f, const double* blobs, int32_t B) {
+  return f->staged.valid && B > 0 && f->staged.B == B && blobs == staged_blobs(f->staged);
 }
 // the body pk_motion and pk_motion_odom share behind their argument checks: the copy of a supplied z, the PK_T_MOTION span, the
 // staged scan that rides the launch, pose_part_ok.  launch(z_dev, up_dst_dev, up_src_host_mapped, up_bytes) is the kernel's.
@@ -540,13 +531,34 @@ int bad_threshold(const char* who, double threshold);  // a gate's threshold: fi
 // pk_api_odom.hip
 // pk_motion_odom behind its argument checks (what step_impl runs for an odometry step that cannot ride the fused launch)
 int motion_odom_checked(pk_filter* f, const double delta[3], const double sigma[3], const double* z, uint64_t seed, uint64_t draw);
-// pk_api_observe.hip
+// pk_api_scan.hip
+// the staging ring: the next pinned block (and room for it on the device), ids_dev's capacity, one block host -> device, "slot `slot` rides an upload"
+int take_stage(pk_filter* f, size_t bytes, unsigned char** out, int* slot);
+int ensure_ids_capacity(pk_filter* f, int B);
+int upload_scan(pk_filter* f, const unsigned char* st, size_t bytes, int slot);
 int note_upload(pk_filter* f, int slot);
+int stage_ml_scan(pk_filter* f, const double* blobs, int B, const RangeScan* rs = nullptr);
+// a scan with supplied ids (first / next: the landmark -> blob chains all particles share, prkt_core_v2.py:88; with_ids: the id row too, for k_propose)
+struct KnownScan {
+  KnownScanLayout lay{};
+  int n_unmatched = 0;            // blobs with id 0
+  bool single_sightings = true;   // no landmark is matched by more than one blob
+};
+int upload_known_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, bool with_ids, KnownScan* out, const RangeScan* rs = nullptr);
+ScanTables known_scan_tables(const pk_filter* f, const KnownScan& ks, int B);
+KnownChains known_chains(const pk_filter* f, const KnownScan& ks);
+// What the scan-taking calls check of their arguments, sliced so that each call keeps its own order of refusals around them: B < 0
+// or no blobs, then no map | a blob that is not finite, then (a call with ids) the empty id row for an empty scan without ids -- no
+// association: every landmark keeps its state -- and an id outside 0..L | supplied ids on a growing filter
+int check_scan_shape(const pk_filter* f, const char* who, const double* blobs, int32_t B);
+int check_scan_values(const pk_filter* f, const char* who, const double* blobs, int32_t B, const int32_t** ids = nullptr);
+int refuse_grow_ids(const char* who);
+// the ids back to the caller, [P][B] (ids_out == NULL, an empty scan: nothing): the supplied row P times, or ids_dev behind a synchronisation
+int return_ids(pk_filter* f, int32_t* ids_out, int32_t B, const int32_t* supplied);
+// pk_api_observe.hip
 int colour_rows_for_download(pk_filter* f, int64_t p0, int64_t p1);
 int ct_end(pk_filter* f);
 int ct_maps_untouched(pk_filter* f, bool* untouched);
-void blob_directions(const double* blobs, int B, double* dir);
-int stage_ml_scan(pk_filter* f, const double* blobs, int B, const RangeScan* rs = nullptr);
 int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* ids, int32_t* ids_out, bool reset);
 // a proposal step's scan on the device (pk_api_propose.hip): where its parts lie.  known: supplied ids' chains (the ids are
 // final); scan.dir: the rays that settle tentative ids; ids: one row of B (supplied) or ids_dev's [P][B]; rng: the range rows

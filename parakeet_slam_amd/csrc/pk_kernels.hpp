@@ -118,11 +118,8 @@ void launch_reset_weights(hipStream_t s, DeviceState& d);
 // (a) reference kernel: every (landmark, blob) pair is gate-tested (launch_assoc_brute, below the scan's tables)
 // (b) production kernel: blobs bucketed on the host into a 3-D colour grid whose cell edge
 // exceeds the colour gate radius sqrt(300), so a landmark only meets the blobs of its 27
-// neighbouring cells.  Tables (device): start u16[ncell+1] (16-byte padded) | rec32
-// float4[B] = (r, g, b, bearing) in cell order | idx9 u16[n9] | order u16[B]; exact records
-// double[B][6] = (bearing, r, g, b, ux, uy) in cell order.  With n9 > 0, idx9 lists for every
-// (r, g) column the blobs within one cell in r and g, ordered by b cell, and `start` indexes
-// it: a landmark's whole 27-cell neighbourhood is then one contiguous range.
+// neighbouring cells (the tables and the exact records: pk_scan_block.hpp).  With n9 > 0, idx9 lists for every (r, g) column the
+// blobs within one cell in r and g, ordered by b cell: a landmark's whole 27-cell neighbourhood is then one contiguous range.
 struct BlobGrid {
   double lo[3];
   double inv_h;

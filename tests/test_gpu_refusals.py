@@ -13,7 +13,15 @@ is recorded with
 
     python tests/test_gpu_refusals.py --record [--lib path/to/libparakeet_slam.so]
 
-from a build of the commit whose answers are to be preserved, never from the code under test."""
+from a build of the commit whose answers are to be preserved, never from the code under test.
+
+tests/golden/scan_refusals.json holds, in the same way, what the calls that take a scan -- pk_observe, pk_observe_fresh, pk_associate,
+pk_stage_scan, pk_step, pk_propose and pk_propose_odom (the last two on bearing-model filters) -- answer to bad arguments
+(record_scan): B < 0, blobs missing, no map, a NaN in blob 1 (the message names the blob, not the double), ids of -1 and L + 1 with
+L accepted, supplied ids on a growing filter, B = 0, 65 536 blobs without ids, pk_associate without ids_out, and the pairs that show
+each call's order of checks (no map + NaN, NaN + bad id, armed ranges of another length + NaN, the reference model + bad blobs for
+pk_propose).  It was recorded by the same command from a build of the commit BEFORE these checks and the per-scan block's layout
+were stated once (pk_api_scan.hip, pk_scan_block.hpp), on the GPU, never from the code under test; --record writes both fixtures."""
 import ctypes as C
 import json
 import os
@@ -31,6 +39,7 @@ pytestmark = pytest.mark.gpu
 P, L = 16, 8
 LINEAR, LOG = 0, 1
 FIXTURE = os.path.join(ROOT, "tests", "golden", "refusals.json")
+SCAN_FIXTURE = os.path.join(ROOT, "tests", "golden", "scan_refusals.json")
 SCRATCH_BYTES = 1 << 20
 
 # option -> inclusive range (P: the number of particles), in the order pk_set_option is asked; None: any value is taken
@@ -247,6 +256,93 @@ def record(lib):
     return out
 
 
+def record_scan(lib):
+    """The scan-taking calls' argument refusals, every case in order: name -> "ok" | [status, message]."""
+    abi = lib.load()
+    out = {}
+    dp, ip = lib.dptr, lib.iptr
+    good = np.array([[0.3, 20.0, 50.0, 90.0], [-0.2, 200.0, 50.0, 90.0]])
+    nan1 = good.copy()
+    nan1[1, 2] = np.nan  # blob 1, double 6
+    many = np.tile(good, (32768, 1))  # 65 536 blobs
+    ids_out = np.zeros(P * 2, dtype=np.int32)
+    delta, alpha = np.array([0.01, 0.05, 0.0]), np.array([0.01, 0.01, 0.01, 0.01])
+
+    def ids(a, b):
+        return np.array([a, b], dtype=np.int32)
+
+    # call -> (takes ids, fn(handle, blobs, B, ids))
+    calls = {
+        "observe": (True, lambda h, b, B, i: abi.pk_observe(h, dp(b), B, ip(i), None)),
+        "observe_fresh": (True, lambda h, b, B, i: abi.pk_observe_fresh(h, dp(b), B, ip(i), None)),
+        "associate": (False, lambda h, b, B, i: abi.pk_associate(h, dp(b), B, ip(ids_out))),
+        "stage_scan": (False, lambda h, b, B, i: abi.pk_stage_scan(h, dp(b), B)),
+        "step": (True, lambda h, b, B, i: abi.pk_step(h, 0.1, 0.02, 0.1, None, 5, 0, dp(b), B, ip(i), 0.37, LINEAR)),
+        "propose": (True, lambda h, b, B, i: abi.pk_propose(h, 0.1, 0.02, 0.1, None, 5, 0, dp(b), B, ip(i), 0, None)),
+        "propose_odom": (True, lambda h, b, B, i: abi.pk_propose_odom(h, dp(delta), dp(alpha), None, 5, 0, dp(b), B, ip(i), 0, None)),
+    }
+
+    def new_filter(name, with_map=True):
+        f = lib.DeviceFilter(P, L)
+        if with_map:
+            means = np.column_stack([np.linspace(-4.0, 4.0, L), np.linspace(3.0, 5.0, L), np.linspace(10.0, 220.0, L), np.full(L, 50.0), np.full(L, 90.0)])
+            f.upload_map(means, np.tile(0.25 * np.identity(5), (L, 1, 1)).reshape(L, 25))
+        poses = np.zeros((P, 4))
+        poses[:, 3] = 1.0
+        f.upload_poses(poses)
+        if name.startswith("propose"):
+            f.set_measurement_model("bearing")
+        return f
+
+    for name, (takes_ids, fn) in calls.items():
+        def call(case, h, b, B, i=None):
+            assert name + "-" + case not in out, case
+            st = fn(h, b, B, i)
+            out[name + "-" + case] = "ok" if st == lib.PK_OK else [int(st), abi.pk_last_error().decode()]
+
+        f = new_filter(name, with_map=False)
+        call("no-map", f._h, good, 2)
+        call("no-map-and-nan", f._h, nan1, 2)
+        call("no-map-and-negative-B", f._h, good, -1)
+        f.close()
+        f = new_filter(name)
+        h = f._h
+        call("negative-B", h, good, -1)
+        call("null-blobs", h, None, 2)
+        call("nan-in-blob-1", h, nan1, 2)
+        f.scan_ranges(np.array([2.0, np.nan, 3.0]), np.array([0.01, 0.0, 0.02]))  # named for a scan of three blobs
+        call("ranges-of-3-blobs-and-nan", h, nan1, 2)
+        if takes_ids:
+            call("ids=-1", h, good, 2, ids(1, -1))
+            call("ids=L+1", h, good, 2, ids(L + 1, 1))
+            call("nan-and-ids=L+1", h, nan1, 2, ids(L + 1, 1))
+            call("null-blobs-and-ids=L+1", h, None, 2, ids(L + 1, 1))
+            call("ids=L", h, good, 2, ids(L, 1))
+        call("B=0", h, None, 0)
+        if name == "associate":
+            assert "associate-null-ids_out" not in out
+            st = abi.pk_associate(h, dp(good), 2, None)
+            out["associate-null-ids_out"] = "ok" if st == lib.PK_OK else [int(st), abi.pk_last_error().decode()]
+        if name in ("observe", "propose"):
+            call("65536-blobs", h, many, 65536)
+        if name == "propose":
+            f.set_measurement_model("reference")
+            call("reference-model-and-negative-B", h, good, -1)
+            call("reference-model-and-null-blobs", h, None, 2)
+        f.close()
+        if takes_ids:  # a growing filter: supplied ids are refused (the proposal: once pk_proposal_grow lets it run there at all)
+            f = new_filter(name)
+            f.grow_enable(L - 4, 64, 30.0)
+            call("grow-and-ids", f._h, good, 2, ids(1, 0))
+            if name.startswith("propose"):
+                f.proposal_grow(True)
+                call("proposal_grow-and-ids", f._h, good, 2, ids(1, 0))
+                call("proposal_grow-and-ids-and-nan", f._h, nan1, 2, ids(1, 0))
+            call("grow-and-ids-and-B=0", f._h, None, 0, ids(1, 0))
+            f.close()
+    return out
+
+
 @pytest.fixture(scope="module")
 def golden():
     with open(FIXTURE) as fh:
@@ -282,19 +378,58 @@ def test_every_call_is_answered_as_it_was(golden, answers):
     assert {k: v for k, v in answers.items() if golden.get(k) != v} == {}
 
 
+@pytest.fixture(scope="module")
+def scan_golden():
+    with open(SCAN_FIXTURE) as fh:
+        return json.load(fh)
+
+
+@pytest.fixture(scope="module")
+def scan_answers(lib):
+    return record_scan(lib)
+
+
+def test_the_scan_cases_are_the_fixtures(scan_golden, scan_answers):
+    assert sorted(scan_golden) == sorted(scan_answers)
+    assert not [k for k, v in scan_golden.items() if v != "ok" and (v[0] in (-2, -5) or "failed:" in v[1])]  # (no runtime error)
+
+
+def test_the_scan_fixture_shows_what_it_is_for(scan_golden):
+    g = scan_golden
+    for call in ("observe", "observe_fresh", "associate", "stage_scan", "step", "propose", "propose_odom"):
+        assert g[call + "-nan-in-blob-1"][1].endswith("blob 1 is not finite"), call
+        assert "no map uploaded" in g[call + "-no-map"][1] and g[call + "-no-map-and-nan"] == g[call + "-no-map"], call
+        assert "pk_scan_ranges named the ranges of a scan of 3 blobs" in g[call + "-ranges-of-3-blobs-and-nan"][1] or call.startswith("propose"), call
+        assert g[call + "-B=0"] == ("ok" if call != "stage_scan" else g["stage_scan-negative-B"]), call
+    for call in ("observe", "observe_fresh", "step", "propose", "propose_odom"):
+        assert g[call + "-ids=L"] == "ok" and g[call + "-ids=-1"][1].endswith("ids[1] = -1 outside 0..%d" % L), call
+        assert g[call + "-ids=L+1"][1].endswith("ids[0] = %d outside 0..%d" % (L + 1, L)), call
+        assert g[call + "-nan-and-ids=L+1"] == g[call + "-nan-in-blob-1"], call  # the values before the ids
+    assert g["propose-proposal_grow-and-ids-and-nan"] == g["propose-proposal_grow-and-ids"]  # the proposal: no ids before bad values
+    assert g["propose-reference-model-and-negative-B"] == g["propose-reference-model-and-null-blobs"]  # the proposal's own refusals first
+    assert g["observe-65536-blobs"] != "ok" and g["propose-65536-blobs"] != "ok" and g["associate-null-ids_out"] != "ok"
+
+
+def test_every_scan_call_is_answered_as_it_was(scan_golden, scan_answers):
+    assert {k: v for k, v in scan_answers.items() if scan_golden.get(k) != v} == {}
+
+
 if __name__ == "__main__":
     from parakeet_slam_amd import _lib
 
     if "--lib" in sys.argv:
         _lib.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
-    got = record(_lib)
-    if "--record" in sys.argv:
-        with open(FIXTURE, "w") as fh:
-            fh.write("{\n" + ",\n".join("%s: %s" % (json.dumps(k), json.dumps(got[k])) for k in sorted(got)) + "\n}\n")
-        print("recorded %d cases from %s" % (len(got), _lib.LIB_PATH))
-    else:
-        with open(FIXTURE) as fh:
-            want = json.load(fh)
-        bad = [k for k in sorted(set(want) | set(got)) if got.get(k) != want.get(k)]
-        print("%d cases, %d differ from the fixture: %s" % (len(got), len(bad), bad))
-        sys.exit(1 if bad else 0)
+    differ = 0
+    for path, rec in ((FIXTURE, record), (SCAN_FIXTURE, record_scan)):
+        got = rec(_lib)
+        if "--record" in sys.argv:
+            with open(path, "w") as fh:
+                fh.write("{\n" + ",\n".join("%s: %s" % (json.dumps(k), json.dumps(got[k])) for k in sorted(got)) + "\n}\n")
+            print("recorded %d cases from %s in %s" % (len(got), _lib.LIB_PATH, os.path.basename(path)))
+        else:
+            with open(path) as fh:
+                want = json.load(fh)
+            bad = [k for k in sorted(set(want) | set(got)) if got.get(k) != want.get(k)]
+            print("%s: %d cases, %d differ from the fixture: %s" % (os.path.basename(path), len(got), len(bad), bad))
+            differ += len(bad)
+    sys.exit(1 if differ else 0)
