@@ -708,6 +708,33 @@ int pk_proposal_ranges_state(const pk_filter* f, int32_t* on);
 int pk_proposal_grow(pk_filter* f, int32_t on);
 int pk_proposal_grow_state(const pk_filter* f, int32_t* on);
 
+/* Unique association ("Unique association"; the reference's unwritten "Version 2: match each scan to a unique
+ * feature", prkt_core_v2.py:317-351): an opt-in mode in which at most one blob of a scan keeps each landmark of a particle.
+ * The rule, per particle: with p(b, l) the association's own match probability (for a blob with a finite range, the measured
+ * point's) on the untouched landmark state at the live pose, the pairs with p > 0 are walked by p descending, then blob ascending
+ * (scan order), then landmark ascending (preset first, then spare slots), and a pair is taken iff neither its blob nor its landmark
+ * has been; ids[b] is the taken landmark's id, or 0.  A particle whose maximum-likelihood ids claim no landmark twice keeps them,
+ * element for element.  A blob that ends 0 is an unmatched blob in every respect (log 0.1; on a growing filter the new-landmark
+ * bookkeeping takes it), and a landmark is updated at most once per scan.
+ * Off (the default): every call launches and computes what it did, bit for bit, and pk_device_bytes is what it was.
+ * On (on = 1; anything but 0 or 1 is PK_ERR_INVALID, PK_ERR_STATE inside a split observe; nothing changed either way; 64 bytes
+ * of counters from the first time): the maximum-likelihood scans of pk_observe, pk_observe_fresh, pk_observe_staged, pk_step,
+ * pk_step_adaptive, pk_step_odom and pk_associate take the general route under both measurement models (PK_ROUTE_ML_GENERAL; either
+ * association kernel, finalising), k_assoc_unique settles the ids in place in the PK_T_ASSOC span, and k_observe*, the
+ * bookkeeping and retirement follow on the settled ids, which ids_out returns.  Supplied ids are applied as ever.
+ * Refused while it is on, PK_ERR_UNSUPPORTED, nothing changed, armed ranges gone: a maximum-likelihood scan on the dense layout;
+ * pk_observe_staged_range; pk_propose / pk_propose_odom (k_propose settles its own tentative ids); a scan whose tables
+ * (12 bytes per padded landmark + 14 per blob) exceed the workgroup's LDS.  pk_step, pk_step_adaptive and pk_step_odom are refused
+ * ahead of their motion: no particle has moved.
+ * pk_assoc_unique_stats: of the last scan whose association went through the pass -- particles with a conflict, blobs whose id
+ * changed, of those the ones matched to another landmark (the rest ended 0), the most passes any particle took (1: no conflict
+ * anywhere) --, zeros when the last observe was not in the mode; synchronises.  The pass is bounded at num_blobs + 1 passes per
+ * particle; a particle that reached the bound (a device error: no input does) stops with the ids it has, and the next
+ * synchronising call of pk_synchronize, pk_assoc_unique_stats, pk_associate or an observe with ids_out fails with PK_ERR_HIP. */
+int pk_assoc_unique(pk_filter* f, int32_t on);
+int pk_assoc_unique_state(const pk_filter* f, int32_t* on);
+int pk_assoc_unique_stats(pk_filter* f, int64_t out[4]);
+
 /* ---- sharded (multi-GPU) resampling: see DESIGN.md section 6 -------------------
  * Particles are sharded contiguously over one process per GPU; global particle index =
  * global_offset + local index.  The collectives themselves are the caller's

@@ -128,6 +128,9 @@ SIGNATURES = {
     "pk_proposal_ranges_state": (C.c_int, [_h, C.POINTER(C.c_int32)]),
     "pk_proposal_grow": (C.c_int, [_h, C.c_int32]),
     "pk_proposal_grow_state": (C.c_int, [_h, C.POINTER(C.c_int32)]),
+    "pk_assoc_unique": (C.c_int, [_h, C.c_int32]),
+    "pk_assoc_unique_state": (C.c_int, [_h, C.POINTER(C.c_int32)]),
+    "pk_assoc_unique_stats": (C.c_int, [_h, _lp]),
     "pk_motion_odom_range": (C.c_int, [_h, _dp, _dp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64]),
     "pk_step_odom": (C.c_int, [_h, _dp, _dp, _dp, C.c_uint64, C.c_uint64, _dp, C.c_int32, _ip, C.c_double, C.c_int32, C.c_double]),
     "pk_shard_max_logw": (C.c_int, [_h, _dp]),
@@ -446,6 +449,24 @@ class DeviceFilter(object):
         on = C.c_int32(0)
         check(self._lib.pk_proposal_grow_state(self._h, C.byref(on)))
         return bool(on.value)
+
+    def assoc_unique(self, on=True):
+        """Unique association (pk_assoc_unique): on, every maximum-likelihood scan's ids are settled so that at most one blob keeps
+        each landmark of a particle -- the greedy matching by (probability descending, blob ascending, landmark ascending)."""
+        check(self._lib.pk_assoc_unique(self._h, int(on)))
+
+    def assoc_unique_state(self):
+        """Whether unique association is on: pk_assoc_unique_state."""
+        on = C.c_int32(0)
+        check(self._lib.pk_assoc_unique_state(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def assoc_unique_stats(self):
+        """Of the last scan settled in the mode (pk_assoc_unique_stats; synchronises): particles with a conflict, blobs whose id
+        changed, of those the ones matched to another landmark, the most passes any particle took.  int64[4]."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.pk_assoc_unique_stats(self._h, out.ctypes.data_as(_lp)))
+        return out
 
     def download_log_weights(self):
         out = np.empty(self.P, dtype=np.float64)

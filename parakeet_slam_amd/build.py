@@ -19,7 +19,7 @@ import sys
 # k_step_fused: 121 against 99; k_assoc_grid<768, ...>: 168 + 44-52 B of scratch against 137-141 / none, and its 512-lane
 # instances 207 against 121).  k_propose: 207 against 168 (two waves a SIMD against three).
 _NO_LICM = ["-mllvm", "-disable-machine-licm"]
-EXTRA_FLAGS = {"pk_k_observe_ml.hip": _NO_LICM, "pk_k_step_pub.hip": _NO_LICM, "pk_k_cand_entries.hip": _NO_LICM, "pk_k_assoc.hip": _NO_LICM,
+EXTRA_FLAGS = {"pk_k_observe_ml.hip": _NO_LICM, "pk_k_step_pub.hip": _NO_LICM, "pk_k_cand_entries.hip": _NO_LICM, "pk_k_assoc.hip": _NO_LICM, "pk_k_assoc_unique.hip": _NO_LICM,
                "pk_k_propose.hip": _NO_LICM}  # k_propose: 168 VGPRs against 207
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -27,7 +27,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libparakeet_slam.so")
 OBJDIR = os.path.join(HERE, "csrc", "_obj")
 
-HIP_SOURCES = ["pk_k_motion.hip", "pk_k_motion_odom.hip", "pk_k_propose.hip", "pk_k_assoc.hip", "pk_k_observe.hip", "pk_k_observe_ml.hip", "pk_k_step_pub.hip", "pk_k_cand_entries.hip", "pk_k_dense.hip", "pk_k_resample.hip", "pk_k_grow.hip", "pk_k_grow_retire.hip", "pk_k_colour.hip", "pk_k_mapsum.hip", "pk_k_mapmatch.hip", "pk_k_path.hip", "pk_k_path_weighted.hip", "pk_k_path_settle.hip", "pk_k_adaptive.hip", "pk_k_mathprobe.hip", "pk_api.hip", "pk_api_observe.hip", "pk_api_scan.hip", "pk_api_shard.hip", "pk_api_path.hip", "pk_api_adaptive.hip", "pk_api_mapmatch.hip", "pk_api_retire.hip", "pk_api_odom.hip", "pk_api_propose.hip", "pk_api_range.hip"]
+HIP_SOURCES = ["pk_k_motion.hip", "pk_k_motion_odom.hip", "pk_k_propose.hip", "pk_k_assoc.hip", "pk_k_assoc_unique.hip", "pk_k_observe.hip", "pk_k_observe_ml.hip", "pk_k_step_pub.hip", "pk_k_cand_entries.hip", "pk_k_dense.hip", "pk_k_resample.hip", "pk_k_grow.hip", "pk_k_grow_retire.hip", "pk_k_colour.hip", "pk_k_mapsum.hip", "pk_k_mapmatch.hip", "pk_k_path.hip", "pk_k_path_weighted.hip", "pk_k_path_settle.hip", "pk_k_adaptive.hip", "pk_k_mathprobe.hip", "pk_api.hip", "pk_api_observe.hip", "pk_api_scan.hip", "pk_api_shard.hip", "pk_api_path.hip", "pk_api_adaptive.hip", "pk_api_mapmatch.hip", "pk_api_retire.hip", "pk_api_odom.hip", "pk_api_propose.hip", "pk_api_range.hip", "pk_api_unique.hip"]
 CXX_SOURCES = ["pk_rng.cpp"]  # host-only, no FMA contraction: must match NumPy/CPython bit for bit
 HEADERS = [
     "pk_math.hpp", "pk_layout.hpp", "pk_kernels.hpp", "pk_philox.hpp", "pk_device.hpp", "pk_pub_math.hpp", "pk_pub_layout.hpp", "pk_colour.hpp", "pk_devmem.hpp", "pk_filter.hpp", "pk_scan_block.hpp", "pk_k_step_duo.inl", "pk_path_rows.hpp", "pk_motion_common.hpp", "pk_proposal.hpp", "pk_range_math.hpp", "pk_launch.hpp",

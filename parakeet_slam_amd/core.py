@@ -45,6 +45,21 @@ def _blob_row(blob):
     return np.array([blob.bearing, blob.color.r, blob.color.g, blob.color.b], dtype=np.float64)
 
 
+def _check_association(association, proposal, devices, who="FastSLAM"):
+    """association: 'ml' (every blob takes its own most likely landmark) or 'unique' (pk_assoc_unique: at most one blob of a scan
+    keeps each landmark of a particle) -- the latter on one GPU, under the plain step."""
+    if association not in ("ml", "unique"):
+        raise ValueError("%s(association=%r): 'ml' (default) or 'unique'" % (who, association))
+    if association == "unique" and proposal == "measurement":
+        raise ValueError("%s(association='unique', proposal='measurement'): the measurement-informed proposal settles its own "
+                         "tentative ids inside its kernel and has no unique pass yet; the plain step (proposal='motion') takes it"
+                         % who)
+    if association == "unique" and devices is not None and len(list(devices)) > 1:
+        raise ValueError("%s(devices=[...], association='unique'): unique association runs on one GPU -- the kernel works per "
+                         "particle and would serve every shard, but the shards' filters are not told of the mode" % who)
+    return association
+
+
 def _check_proposal_grow(proposal_grow, proposal, new_landmarks, spare_landmarks, bookkeeping, devices, range_noise, proposal_ranges,
                          grow_ranges, who="FastSLAM"):
     """proposal_grow=True: the measurement-informed proposal on a growing map (pk_proposal_grow) -- it needs proposal='measurement',
@@ -744,6 +759,14 @@ class FastSLAM(object):
     feature at once.  Without the keyword proposal="measurement" with new_landmarks=True stays a ValueError; with it,
     proposal="motion", a preset map, no spare slot, bookkeeping="host" or several devices is one.  In odometry mode a scan with no
     new odometry is the plain growing observe.  Snapshots do not carry the flag (they do not carry ``proposal`` either).  One GPU.
+
+    association="unique" (default "ml"): unique data association (pk_assoc_unique; DESIGN.md section 4, "Unique association" -- the
+    reference's unwritten "Version 2", prkt_core_v2.py:317-351).  Every scan's maximum-likelihood ids are settled per particle so that
+    no landmark keeps more than one blob: the pairs are taken greedily by match probability, then scan order, then landmark index,
+    and a blob that loses everywhere is unmatched -- on a growing map it becomes a reading or a feature.  ``last_ids`` /
+    ``record_ids`` carry the settled ids; ``association_stats()`` returns the last scan's counters.  Both measurement models,
+    range_noise and growing maps take it; proposal="measurement", several devices or an unknown name is a ValueError.
+    Configuration, not state: snapshots do not carry it.
     """
 
     EMPTY_COLOUR = 2.0 ** 100  # colour of a spare slot that holds nothing yet: fails every colour gate (:441), exact in float32
@@ -761,6 +784,7 @@ class FastSLAM(object):
         ba.apply_defaults()
         a = ba.arguments
         _check_landmark_init(a["landmark_init"], a["min_parallax"], a["new_landmarks"])
+        _check_association(a["association"], a["proposal"], a.get("devices"))
         _check_proposal_grow(bool(a["proposal_grow"]), a["proposal"], a["new_landmarks"], a["spare_landmarks"], a["bookkeeping"],
                              a.get("devices"), a["range_noise"], bool(a["proposal_ranges"]), bool(a["grow_ranges"]))
         _check_range_noise(a["range_noise"], a["measurement_model"], a["proposal"], a["new_landmarks"],
@@ -812,8 +836,9 @@ class FastSLAM(object):
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
                  odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion",
                  landmark_init="reference", min_parallax=0.2, range_noise=None, proposal_ranges=False, grow_ranges=False,
-                 proposal_grow=False):
+                 proposal_grow=False, association="ml"):
         self._landmark_init, self._min_parallax = _check_landmark_init(landmark_init, min_parallax, new_landmarks)
+        self._association = _check_association(association, proposal, devices)
         if measurement_model not in _lib.MEASUREMENT_MODELS:
             raise ValueError("FastSLAM(measurement_model=%r): 'reference' (default) or 'bearing'" % (measurement_model,))
         self._proposal_grow = _check_proposal_grow(bool(proposal_grow), proposal, new_landmarks, spare_landmarks, bookkeeping, devices,
@@ -866,6 +891,8 @@ class FastSLAM(object):
             self._filter.proposal_ranges(True)
         if self._proposal_grow:
             self._filter.proposal_grow(True)
+        if self._association == "unique":
+            self._filter.assoc_unique(True)
         if L + self._spare:
             means = np.zeros((L + self._spare, 5))
             covs = np.tile(np.identity(5).reshape(25), (L + self._spare, 1))
@@ -976,6 +1003,14 @@ class FastSLAM(object):
         cnt, rd, sid = _nl_pack(hyp, next_id, used, slot_id, self._L0, S, R)
         self._filter.grow_upload(0, P, cnt, rd, sid)
         self._nl_cache = None
+
+    def association_stats(self):
+        """Unique association's figures of the last scan (association="unique"; pk_assoc_unique_stats): particles whose
+        maximum-likelihood ids claimed some landmark twice, blobs whose id changed, of those the ones matched to another landmark,
+        the most passes any particle took.  All zero with association="ml"."""
+        with self._lock:
+            c = self._filter.assoc_unique_stats()
+        return dict(conflicts=int(c[0]), changed=int(c[1]), rematched=int(c[2]), rounds=int(c[3]))
 
     def readings_dropped(self):
         """Orphaned readings that found the particle's ring full (bookkeeping="device"; the reference's dict grows without

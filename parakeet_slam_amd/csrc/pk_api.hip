@@ -322,7 +322,7 @@ int pk_synchronize(pk_filter* f) {
   int rc;
   if ((rc = use_device(f))) return rc;
   PK_HIP(hipStreamSynchronize(f->stream));
-  return PK_OK;
+  return unique_error(f, "pk_synchronize");
 }
 
 int64_t pk_num_particles(const pk_filter* f) { return f ? f->d.P : -1; }
@@ -863,6 +863,10 @@ int step_impl(pk_filter* f, const StepMotion& m, const double* z, uint64_t seed,
   };
   int rc;
   if ((rc = ranges_check(f, "pk_step", B))) return rc;  // (armed ranges this step cannot take: refused before anything moves)
+  if (f && !ids && B > 0 && (rc = unique_check(f, "pk_step", B))) {  // (unique association's refusals too: the armed ranges go)
+    ranges_disarm(f);
+    return rc;
+  }
   // Throughput mode with ML association: the host half of the scan upload first, then ONE launch
   // for the motion update and the upload of the scan block, then the observe kernels.
   if (f && !f->dense && !f->grow_on && !z && !ids && B > 0 && blobs && f->map_loaded && f->opt.upload_kernel && m.finite()) {

@@ -157,6 +157,8 @@ static ScanPlan plan_scan(const pk_filter* f, int B, bool use_grid, int ncell, i
   p.kind = ScanKind::General;
   // the bearing model (pk_set_measurement_model) has the general kernels alone: no hand-off, no one-pass kernel, no stand-by launch
   if (f->model == PK_MODEL_BEARING) return p;
+  // unique association (pk_assoc_unique): the settling pass stands between the general association and k_observe, for both models
+  if (f->uq.on) return p;
   const int L = f->d.lay.L, Lp = f->d.lay.Lp;
   const bool sweep = L > kFastMaxL || f->opt.fast_observe >= 2;
   auto sweep_fits = [&] { return observe_sweep_plan(f->d, B).grid > 0; };
@@ -271,13 +273,16 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
                 "%zu bytes of per-blob state fit the workgroup's %zu bytes of LDS", B, assoc_brute_lds_bytes(B), (size_t)kMaxDynLds);
   if ((rc = ct_end(f))) return rc;  // (the general association reads the slots' colour rows)
   Span t(f, PK_T_ASSOC);
+  // unique association: final ids from either kernel, then k_assoc_unique on them, in this span
+  const bool unique = f->uq.on;
+  if (unique) finalize = true;
   if (plan.kind == ScanKind::Brute) {
     launch_assoc_brute(f->stream, f->d, scan, f->ids_dev, f->model, f->qt.q00);
-    return PK_OK;
+    return unique ? unique_settle(f, scan) : PK_OK;
   }
   if (f->model == PK_MODEL_BEARING) {
     launch_assoc_grid_bearing(f->stream, f->d, scan, f->ids_dev, finalize, f->qt.q00);
-    return PK_OK;
+    return unique ? unique_settle(f, scan) : PK_OK;
   }
   FastHandoff fh{};
   CandTable cand;
@@ -300,7 +305,7 @@ static int enqueue_association(pk_filter* f, const double* blobs, int B, bool fi
     }
   }
   launch_assoc_grid(f->stream, f->d, scan, f->ids_dev, finalize, fh, cand);
-  return PK_OK;
+  return unique ? unique_settle(f, scan) : PK_OK;
 }
 
 // The dense path (maps with xy-rgb coupling or a coupled Qt): one general kernel does association (or takes the ids),
@@ -580,6 +585,13 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   if (grow && f->dense)
     return fail(PK_ERR_STATE, "pk_observe: the new-landmark bookkeeping (pk_grow_enable) writes the compact landmark layout; this filter "
                               "is on the dense one (a covariance or Qt that couples position and colour)");
+  // unique association (pk_assoc_unique) is the maximum-likelihood scans' alone: supplied ids are applied as ever
+  f->uq.last = false;
+  if (!ids && B > 0 && (rc = unique_check(f, "pk_observe", B))) {
+    f->staged.valid = false;
+    f->dense_staged.clear();
+    return rc;
+  }
   f->ct_updated = true;
   if (f->dense) return dense_observe(f, blobs, B, ids, ids_out, reset, true);
   ObserveExtras ex;
@@ -657,7 +669,8 @@ int observe_impl(pk_filter* f, const double* blobs, int32_t B, const int32_t* id
   PK_LAUNCH_CHECK("pk_observe");
   observe_done(f);
   if (grow && (rc = grow_bookkeeping(f, "pk_observe", al.scan, B))) return rc;
-  return return_ids(f, ids_out, B, nullptr);
+  if ((rc = return_ids(f, ids_out, B, nullptr))) return rc;
+  return ids_out && B > 0 ? unique_error(f, "pk_observe") : PK_OK;  // (behind return_ids' synchronisation)
 }
 
 // A proposal step's scan (pk_api_propose.hip) on the device, ahead of k_propose: supplied ids as pk_observe uploads them -- the block
@@ -669,6 +682,7 @@ int proposal_scan(pk_filter* f, const double* blobs, int32_t B, const int32_t* i
   int rc;
   *out = ProposalScan();
   f->ct_updated = true;
+  f->uq.last = false;  // (the proposal is refused while unique association is on: this scan is not in the mode)
   if (ids) {
     if ((rc = ct_end(f))) return rc;
     f->staged.valid = false;
@@ -729,6 +743,7 @@ int pk_observe_staged_range(pk_filter* f, int32_t fresh, int64_t p0, int64_t p1,
   if (!f) return fail(PK_ERR_INVALID, "pk_observe_staged_range: NULL handle");
   if (int rc = refuse_path(f, "pk_observe_staged_range")) return rc;
   if (int rc = refuse_bearing(f, "pk_observe_staged_range", "the ranged and split observes of the sharded step")) return rc;
+  if (int rc = unique_refuse(f, "pk_observe_staged_range", "the ranged and split observes of the sharded step")) return rc;
   if (p0 < 0 || p1 < p0 || p1 > f->d.P) return fail(PK_ERR_INVALID, "pk_observe_staged_range: bad particle range [%lld, %lld)", (long long)p0, (long long)p1);
   if (f->grow_on) return fail(PK_ERR_STATE, "pk_observe_staged_range: the new-landmark bookkeeping (pk_grow_enable) runs behind whole observes (pk_observe / pk_observe_staged)");
   int rc;
@@ -779,6 +794,8 @@ int pk_associate(pk_filter* f, const double* blobs, int32_t B, int32_t* ids_out)
   if (B == 0) return PK_OK;
   if ((rc = use_device(f))) return rc;
   if ((rc = check_scan_values(f, "pk_associate", blobs, B))) return rc;
+  f->uq.last = false;
+  if ((rc = unique_check(f, "pk_associate", B))) return rc;
   if (f->dense) return dense_observe(f, blobs, B, nullptr, ids_out, false, false);
   if ((rc = ensure_colour_rows(f))) return rc;  // (the colour table's mode goes on: nothing is updated)
   {
@@ -789,7 +806,8 @@ int pk_associate(pk_filter* f, const double* blobs, int32_t B, int32_t* ids_out)
   }
   if (rc) return rc;
   PK_LAUNCH_CHECK("pk_associate");
-  return return_ids(f, ids_out, B, nullptr);
+  if ((rc = return_ids(f, ids_out, B, nullptr))) return rc;
+  return unique_error(f, "pk_associate");
 }
 
 int pk_set_measurement_model(pk_filter* f, int32_t model) {

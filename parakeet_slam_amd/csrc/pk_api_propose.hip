@@ -65,6 +65,7 @@ int propose_impl(pk_filter* f, const char* who, const StepMotion& m, const doubl
     return rc;
   }
   if ((rc = refuse_proposal(f, who))) return rc;
+  if ((rc = unique_refuse(f, who, "the measurement-informed proposal, which settles its own tentative ids inside k_propose"))) return rc;
   // pk_proposal_grow: the new-landmark bookkeeping follows the step -- at the sampled poses, on the ids k_propose settles
   const bool grow = f->grow_on && B > 0;
   if (grow && ids) return refuse_grow_ids(who);

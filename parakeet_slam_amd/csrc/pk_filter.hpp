@@ -11,6 +11,7 @@
 //   pk_api_propose.hip  the measurement-informed proposal: pk_propose, pk_propose_odom, pk_proposal_download, its modes
 //                       (pk_proposal_ranges, pk_proposal_grow)
 //   pk_api_range.hip    range-bearing scans: pk_scan_ranges, what consumes the armed ranges, their refusals
+//   pk_api_unique.hip   unique association: pk_assoc_unique, its counters, the pass behind the association, its refusals
 // No kernel is defined or launched here: everything goes through the launch_* functions of pk_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -396,6 +397,13 @@ struct pk_filter {
     bool ranges = false;            // pk_proposal_ranges: armed ranges (pk_scan_ranges) are consumed by the step, not refused
     bool grow = false;              // pk_proposal_grow: the step runs on a growing filter, the bookkeeping and retirement behind it (no device state)
   } prop;
+  // unique association (pk_assoc_unique; pk_api_unique.hip): configuration, and 64 bytes of counters from the first time it is switched on
+  struct Unique {
+    bool on = false;
+    bool last = false;                    // the last scan's association went through k_assoc_unique: its counters are that scan's
+    unsigned long long* stats = nullptr;  // [kAssocUniqueWords] on the device; word 4 (the bound was reached) stays up until it is reported
+    unsigned long long* seen = nullptr;   // the same words in pinned host memory, copied behind every pass
+  } uq;
   int32_t* anc = nullptr;           // P
   unsigned char* slot_tmp = nullptr;  // one slot
   // timing
@@ -585,6 +593,16 @@ int ranges_take(pk_filter* f, const char* who, int32_t B, RangeScan* out);
 int ranges_check(pk_filter* f, const char* who, int32_t B);
 void ranges_disarm(pk_filter* f);
 int refuse_ranges_proposal(pk_filter* f, const char* who);  // (only while pk_proposal_ranges is off)
+// pk_api_unique.hip: unique association (pk_assoc_unique).  unique_refuse: what the mode has no kernels for, refused while it is on;
+// unique_fits: the pass's LDS tables against the workgroup's, before anything is enqueued; unique_settle: the pass itself on ids_dev,
+// behind an association that FINALISED its ids, inside the caller's PK_T_ASSOC span; unique_error: behind a synchronisation, a
+// particle that reached the bound of B + 1 passes since the last report fails the call (once)
+int unique_refuse(const pk_filter* f, const char* who, const char* what);
+int unique_fits(const pk_filter* f, const char* who, int32_t B);
+// both for a maximum-likelihood scan of B > 0 blobs while the mode is on (PK_OK while it is off): the dense layout, then the tables
+int unique_check(const pk_filter* f, const char* who, int32_t B);
+int unique_settle(pk_filter* f, const ScanTables& scan);
+int unique_error(pk_filter* f, const char* who);
 // pk_api_shard.hip
 int refuse_balanced(const pk_filter* f, const char* who);
 int refuse_path(const pk_filter* f, const char* who);

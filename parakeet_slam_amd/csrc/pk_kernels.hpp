@@ -1,4 +1,4 @@
-// Host-visible launchers of the gfx950 kernels (defined in the twenty pk_k_*.hip files; pk_k_step_duo.inl is part of pk_k_step_pub.hip).
+// Host-visible launchers of the gfx950 kernels (defined in the twenty-one pk_k_*.hip files; pk_k_step_duo.inl is part of pk_k_step_pub.hip).
 #pragma once
 #include <cmath>
 #include <hip/hip_runtime.h>
@@ -452,6 +452,21 @@ extern int g_observe_nv;
 // k_assoc_brute (best[B] u64 + bid[B]): callers check them against kMaxDynLds BEFORE anything is enqueued
 inline size_t observe_general_lds_bytes(int Lp, int B) { return sizeof(int32_t) * ((size_t)Lp + 2 * (size_t)B); }
 inline size_t assoc_brute_lds_bytes(int B) { return (size_t)B * 12; }
+// K2'': unique association (pk_k_assoc_unique.hip; DESIGN.md section 4, "Unique association"): behind either association kernel,
+// on FINAL maximum-likelihood ids, every particle's ids are settled in place so that no landmark keeps more than one blob of the scan
+// -- the greedy matching by (p descending, blob ascending, landmark ascending).  A particle whose ids claim no landmark twice is not
+// written.  scan: B, blobs, dir and (a scan with ranged blobs) rng, all in scan order.
+constexpr int kAssocUniqueWords = 8;  // stats_dev: particles with a conflict, blobs whose id changed, of those re-matched, the most
+                                      // passes any particle took, != 0: a particle reached the bound of B + 1 passes; three spare
+struct AssocUniqueLaunch {
+  int32_t* ids_dev = nullptr;               // [P][B], in and out
+  unsigned long long* stats_dev = nullptr;  // [kAssocUniqueWords], added to (the caller zeroes them per scan)
+  int model = 0;                            // pk_math.hpp: kModelReference / kModelBearing
+  double q00 = 0.0;                         // Qt[0][0], for the blobs with a range
+};
+// dynamic LDS: best u64[Lp] | cur_p u64[B] | win i32[Lp] | cur_id i32[B] | the losers' queue u16[B] -- callers check it against kMaxDynLds
+inline size_t assoc_unique_lds_bytes(int Lp, int B) { return (12 * (size_t)Lp + 14 * (size_t)B + 15) & ~(size_t)15; }
+void launch_assoc_unique(hipStream_t s, DeviceState& d, const ScanTables& scan, const AssocUniqueLaunch& q);
 // K4: weights -> block totals / local scans
 void launch_block_max(hipStream_t s, DeviceState& d, double* partial_dev, double* gmax_dev);
 void launch_keys_max(hipStream_t s, const unsigned long long* keys_dev, double* gmax_dev);

@@ -237,7 +237,7 @@ class ShardedFastSLAM(object):
                  backend="nccl", publish_debug=None, _shard_factory=None, new_landmarks=False, spare_landmarks=0,
                  pair_threshold=30.0, reading_capacity=64, record_path=0, resample_threshold=None, settle_path=None,
                  motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS, odom_min_trans=_odom.DEFAULT_MIN_TRANS,
-                 landmark_init="reference", min_parallax=0.2):
+                 landmark_init="reference", min_parallax=0.2, association="ml"):
         from . import _lib  # constants only; loads nothing
         from .core import _check_landmark_init
 
@@ -246,6 +246,10 @@ class ShardedFastSLAM(object):
         self._motion, self._odom_alphas, self._odom_min_trans = _odom.check_keywords(motion, odom_alphas, odom_min_trans)
         self._odom_prev = None  # the last odometry pose (x, y, heading); None: the next message is the first
 
+        from .core import _check_association
+
+        # (before any process starts) an unknown name with its own message, then 'unique' on several GPUs with the facade's
+        _check_association(association, "motion", list(devices) if len(list(devices)) > 1 else [0, 1], "ShardedFastSLAM")
         if settle_path:  # (before any process starts)
             raise ValueError("ShardedFastSLAM: settle_path is for one GPU, as record_path is -- the path is recorded and settled on "
                              "one device only")
