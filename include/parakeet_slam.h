@@ -369,6 +369,39 @@ int pk_grow_clocks_download(pk_filter* f, int64_t p0, int64_t p1, int32_t* count
                             int32_t* slot_idle, uint32_t* scan_now);
 int pk_grow_clocks_upload(pk_filter* f, int64_t p0, int64_t p1, const int32_t* counters, const uint32_t* reading_scan,
                           const int32_t* slot_seen, const int32_t* slot_idle, const uint32_t* scan_now);
+/* A field of view for retirement ("A field of view for retirement"; off by default, and with it off every call
+ * launches and computes what it did, bit for bit).  As in Probabilistic Robotics, Table 13.1, a feature's evidence falls only when
+ * the feature lies inside the sensor's perceptual range and was not observed; a feature out of view is left alone, and a feature
+ * whose evidence runs out is discarded whether it was ever confirmed or not.  With a view (half_fov, range_min, range_max) and a
+ * bound C = confirmed_max_misses, steps 2, 3 and 5 of pk_grow_retire's pass, its compaction and the state of a vacated slot are
+ * unchanged, and steps 1 and 4 become
+ *   1'. a spare slot the last pass knew: count word changed -> seen = word, idle = 0, as ever; word unchanged and the slot IN VIEW
+ *       -> idle += 1 (saturating); word unchanged and not in view -> idle stays as it is;
+ *   4'. a slot goes if M > 0, its seen word carries PK_LANDMARK_POTENTIAL and idle >= M, or if C > 0, its seen word does not carry
+ *       the flag (a promoted feature) and idle >= C.  Preset landmarks are never touched; the survivors move down in order.
+ * In view: with (px, py, ph) the particle's live pose at the pass -- in pk_step* the pose the scan was applied at, before the
+ * resample; in pk_propose* (pk_proposal_grow) the sampled pose -- and (mx, my) the slot's position mean (evaluated only for a slot
+ * this scan did not change), in float64 without contraction, in this order:
+ *     (sn, ch) = sincos(ph);  dx = mx - px, dy = my - py;  q = dx dx + dy dy;  a = dx ch + dy sn;  c = dy ch - dx sn;
+ *     in view  iff  q > 0  and  q >= range_min^2  and  q <= range_max^2  and  |atan2(c, a)| <= half_fov
+ * (the squares formed once on the host; range_max = +inf is allowed; a NaN anywhere fails every comparison: not in view; no wrap,
+ * no occlusion; the mean only -- a caller who wants a margin for the landmark's uncertainty passes a narrower field).
+ * half_fov == 0 switches the view off and sets C to 0 (the other arguments are ignored).  PK_ERR_STATE without pk_grow_enable or
+ * while retirement is off; PK_ERR_INVALID for half_fov NaN or outside [0, pi], range_min NaN, negative or infinite, range_max NaN or
+ * <= range_min, C < 0 or C > 2^30; nothing changes in either case.  pk_grow_retire(f, 0, 0) frees the clocks and clears the view with
+ * them; any other pk_grow_retire call leaves it alone (to retire confirmed features only: M = 2^30).  The view may be changed
+ * between any two scans and holds from the next pass on.  It holds no per-particle memory: the clocks, the resample, the clock
+ * transfers and what retirement refuses are what they were, and the clocks' "features retired" counts both kinds.  Its
+ * PK_GROW_VIEW_STATS_BYTES of counters are counted in pk_device_bytes from the first call that switches a view on and are released
+ * with the clocks.
+ * pk_grow_view_state: *on, view = (half_fov, range_min, range_max) (zeros while off), *confirmed_max_misses; any pointer may be NULL.
+ * pk_grow_view_stats (synchronises; PK_ERR_STATE without a view): out[0] = of the last pass, the slots it knew that did not change,
+ * out[1] = of those, the ones in view (the ones that aged), out[2] / out[3] = potential / confirmed features retired since the view
+ * was last switched on, all summed over the particles. */
+#define PK_GROW_VIEW_STATS_BYTES 32
+int pk_grow_view(pk_filter* f, double half_fov, double range_min, double range_max, int32_t confirmed_max_misses);
+int pk_grow_view_state(const pk_filter* f, int32_t* on, double view[3], int32_t* confirmed_max_misses);
+int pk_grow_view_stats(pk_filter* f, int64_t out[4]);
 
 /* FastSLAM.low_variance_resample (prkt_core_v2.py:210-252) with step = u * sum/P, u in
  * [0,1) standing for random.random() (:226).  ancestors_out: NULL or P int64. */

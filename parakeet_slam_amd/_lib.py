@@ -22,6 +22,7 @@ PK_WEIGHTS_LINEAR, PK_WEIGHTS_LOG = 0, 1
 PK_PATH_UNIFORM = 2  # pk_path_settle's third weighting: every current particle counts once
 PK_MAP_UNIFORM, PK_MAP_WEIGHTED = mapsum.UNIFORM, mapsum.WEIGHTED
 PK_LANDMARK_POTENTIAL = 0x40000000  # flag in a landmark's count word: potential feature (prkt_core_v2.py:109-118)
+PK_GROW_VIEW_STATS_BYTES = 32  # pk_grow_view's counters on the device (include/parakeet_slam.h)
 PK_T_NAMES = ("motion", "assoc", "observe", "weights", "resample", "summary", "materialise", "propose")
 PK_T_COUNT = len(PK_T_NAMES)
 PK_PROBE_LEN = 79
@@ -196,6 +197,9 @@ SIGNATURES = {
     "pk_grow_retire": (C.c_int, [_h, C.c_int32, C.c_int32]),
     "pk_grow_clocks_download": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _up, _ip, _ip, _up]),
     "pk_grow_clocks_upload": (C.c_int, [_h, C.c_int64, C.c_int64, _ip, _up, _ip, _ip, _up]),
+    "pk_grow_view": (C.c_int, [_h, C.c_double, C.c_double, C.c_double, C.c_int32]),
+    "pk_grow_view_state": (C.c_int, [_h, C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int32)]),
+    "pk_grow_view_stats": (C.c_int, [_h, _lp]),
     "pk_observe_published": (C.c_int, [_h, C.POINTER(C.c_int32)]),
     "pk_observe_flags": (C.c_int, [_h, _bp]),
     "pk_observe_pub_stats": (C.c_int, [_h, _lp]),
@@ -971,6 +975,25 @@ class DeviceFilter(object):
         now = None if scan_now is None else C.byref(C.c_uint32(int(scan_now) & 0xFFFFFFFF))
         check(self._lib.pk_grow_clocks_upload(self._h, int(p0), int(p1), iptr(c), None if sc is None else sc.ctypes.data_as(_up), iptr(se),
                                               iptr(si), now))
+
+    def grow_view(self, half_fov, range_min=0.0, range_max=float("inf"), confirmed_max_misses=0):
+        """The sensor's field for the retirement pass (pk_grow_view): an unmatched spare slot ages only while its position mean lies
+        within ``half_fov`` of the particle's heading and between the two ranges, and a promoted feature goes after
+        ``confirmed_max_misses`` such misses (0: never).  ``half_fov=0``: off."""
+        check(self._lib.pk_grow_view(self._h, float(half_fov), float(range_min), float(range_max), int(confirmed_max_misses)))
+
+    def grow_view_state(self):
+        """(on, (half_fov, range_min, range_max), confirmed_max_misses) -- pk_grow_view_state."""
+        on, c, v = C.c_int32(), C.c_int32(), np.zeros(3, dtype=np.float64)
+        check(self._lib.pk_grow_view_state(self._h, C.byref(on), dptr(v), C.byref(c)))
+        return bool(on.value), (float(v[0]), float(v[1]), float(v[2])), int(c.value)
+
+    def grow_view_stats(self):
+        """int64[4] (pk_grow_view_stats; synchronises): of the last pass, the known slots that did not change and the ones of those
+        in view; potential and confirmed features retired since the view was switched on -- summed over the particles."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.pk_grow_view_stats(self._h, out.ctypes.data_as(_lp)))
+        return out
 
     def observe_retry_rows(self):
         """(second-chance rows the last scan wanted, rows the next scan will find) -- pk_observe_retry_rows."""

@@ -127,6 +127,36 @@ def _check_grow_ranges(grow_ranges, spare_landmarks, bookkeeping, who="FastSLAM"
     return bool(grow_ranges)
 
 
+def _check_view(view, confirmed_max_misses, reading_max_age, potential_max_idle, new_landmarks, spare_landmarks, bookkeeping, devices,
+                who="FastSLAM"):
+    """view=(half_fov, r_min, r_max) / confirmed_max_misses=C -> ((half_fov, r_min, r_max) or None, C): the sensor's field for the
+    retirement pass (pk_grow_view), which needs that pass -- a threshold, device bookkeeping, one GPU."""
+    C = int(confirmed_max_misses)
+    if view is None:
+        if C:
+            raise ValueError("%s(confirmed_max_misses=%d): a promoted feature's misses are counted inside a field of view -- give "
+                             "view=(half_fov, r_min, r_max) with it" % (who, C))
+        return None, 0
+    try:
+        half_fov, r_min, r_max = (float(v) for v in view)
+    except (TypeError, ValueError):
+        raise ValueError("%s(view=%r): (half_fov, r_min, r_max) -- radians in (0, pi], 0 <= r_min < r_max (r_max may be inf)" % (who, view))
+    if not (0.0 < half_fov <= math.pi and 0.0 <= r_min < float("inf") and r_max > r_min):
+        raise ValueError("%s(view=%r): (half_fov, r_min, r_max) -- radians in (0, pi], 0 <= r_min < r_max (r_max may be inf)" % (who, view))
+    if not 0 <= C <= 2 ** 30:
+        raise ValueError("%s(confirmed_max_misses=%d): a number of scans in 0..2^30 (0: a promoted feature is never retired)" % (who, C))
+    if devices is not None and len(list(devices)) > 1:
+        raise ValueError("%s(devices=[...], view=...): readings and features are retired on one GPU only -- a particle's record "
+                         "carries no clocks from one rank to another" % who)
+    if not (new_landmarks and int(spare_landmarks) > 0 and bookkeeping == "device"):
+        raise ValueError("%s(view=...): features are retired by the device bookkeeping of a growing map (new_landmarks=True, "
+                         "spare_landmarks > 0, bookkeeping='device'), not by bookkeeping='host'" % who)
+    if not (int(reading_max_age) or int(potential_max_idle)):
+        raise ValueError("%s(view=...): the field of view belongs to the retirement pass -- give reading_max_age=... or "
+                         "potential_max_idle=... (potential_max_idle=2**30 retires confirmed features only)" % who)
+    return (half_fov, r_min, r_max), C
+
+
 def _scan_with_ranges(observes, range_noise, who="FastSLAM"):
     """(observes for _blob_matrix, ranges or None): a (B, 5) array (bearing, r, g, b, range) is split -- and refused without
     range_noise --; with range_noise, message objects are asked for an optional ``range`` attribute (absent, None or NaN: none)."""
@@ -679,6 +709,12 @@ class FastSLAM(object):
     ``reading_max_age=A`` / ``potential_max_idle=M`` (device bookkeeping, one GPU; 0: never, the default): behind every scan's
     bookkeeping each particle drops the readings at the head of its ring that are A scans old or older and retires the potential
     features that went unmatched for M scans, whose spare slots are free again (pk_grow_retire); ``retired()`` counts both.
+    ``view=(half_fov, r_min, r_max)`` with ``confirmed_max_misses=C`` (needs one of the two thresholds above; default: none): the
+    sensor's field for that pass (pk_grow_view; DESIGN.md section 9, "A field of view for retirement").  An unmatched feature ages
+    only in the scans in which its position mean lies within half_fov radians of the particle's heading and between r_min and
+    r_max of its position (r_max may be inf) -- a feature the camera points away from is left alone -- and a promoted feature is
+    retired after C such misses in a row (0: never).  ``view_stats()`` reads the pass's counters.  The view is configuration, like
+    the thresholds: no snapshot holds it.
     ``landmark_init="triangulated"`` (default "reference": the rule above) with ``min_parallax`` (radians in [0, pi / 2], default
     0.2): a stored reading is paired only if its ray meets the blob's at min_parallax or more -- a blob with no such reading is
     stored, so that a later scan pairs with it across a wider baseline -- and the new feature starts with the triangulation's own
@@ -791,6 +827,8 @@ class FastSLAM(object):
                            proposal_ranges=bool(a["proposal_ranges"]), grow_ranges=bool(a["grow_ranges"]),
                            proposal_grow=bool(a["proposal_grow"]))
         _check_grow_ranges(a["grow_ranges"], a["spare_landmarks"], a["bookkeeping"])
+        _check_view(a["view"], a["confirmed_max_misses"], a["reading_max_age"], a["potential_max_idle"], a["new_landmarks"],
+                    a["spare_landmarks"], a["bookkeeping"], a.get("devices"))
         devices = a.get("devices")
         if devices is not None and len(list(devices)) > 1:
             from .multi import ShardedFastSLAM
@@ -836,7 +874,7 @@ class FastSLAM(object):
                  reading_max_age=0, potential_max_idle=0, settle_path=None, motion="twist", odom_alphas=_odom.DEFAULT_ALPHAS,
                  odom_min_trans=_odom.DEFAULT_MIN_TRANS, measurement_model="reference", proposal="motion",
                  landmark_init="reference", min_parallax=0.2, range_noise=None, proposal_ranges=False, grow_ranges=False,
-                 proposal_grow=False, association="ml"):
+                 proposal_grow=False, association="ml", view=None, confirmed_max_misses=0):
         self._landmark_init, self._min_parallax = _check_landmark_init(landmark_init, min_parallax, new_landmarks)
         self._association = _check_association(association, proposal, devices)
         if measurement_model not in _lib.MEASUREMENT_MODELS:
@@ -871,6 +909,8 @@ class FastSLAM(object):
             raise ValueError("FastSLAM(reading_max_age=... / potential_max_idle=...): readings and features are retired by the device "
                              "bookkeeping of a growing map (new_landmarks=True, spare_landmarks > 0, bookkeeping='device'), not by "
                              "bookkeeping='host'")
+        self._view, self._confirmed_max_misses = _check_view(view, confirmed_max_misses, reading_max_age, potential_max_idle,
+                                                              new_landmarks, spare_landmarks, bookkeeping, devices)
         self._threshold = None if resample_threshold is None else adaptive.threshold_value(resample_threshold)
         self._lock = threading.RLock()
         self.last_control = Twist()
@@ -920,6 +960,8 @@ class FastSLAM(object):
                 raise ValueError("%s -- FastSLAM(..., bookkeeping='host') keeps the new-landmark bookkeeping on the host, on any layout" % e)
             if any(self._retire):
                 self._filter.grow_retire(*self._retire)
+            if self._view is not None:
+                self._filter.grow_view(self._view[0], self._view[1], self._view[2], self._confirmed_max_misses)
             if self._landmark_init != "reference":
                 self._filter.grow_init(self._landmark_init, self._min_parallax)
             if self._grow_ranges:
@@ -1026,6 +1068,14 @@ class FastSLAM(object):
         with self._lock:
             c = self._filter.grow_clocks_download()[0]
         return int(c[:, 2].sum()), int(c[:, 3].sum())
+
+    def view_stats(self):
+        """With ``view=``: (unchanged spare slots the last retirement pass knew, those of them in view -- the ones that aged --,
+        potential features retired, confirmed features retired), summed over the particles (pk_grow_view_stats)."""
+        if self._view is None:
+            raise ValueError("FastSLAM.view_stats(): this filter was made without view=(half_fov, r_min, r_max)")
+        with self._lock:
+            return tuple(int(v) for v in self._filter.grow_view_stats())
 
     def _poses(self):
         if self._pose_cache is None:

@@ -554,7 +554,9 @@ int grow_bookkeeping(pk_filter* f, const char* who, const ScanTables& scan, int3
                          f->grow_ranges ? scan.rng : nullptr);  // (pk_grow_ranges; NULL too when no blob has a finite range)
     if (f->retire.on()) {  // pk_grow_retire: stale readings and unconfirmed features go, behind this scan's bookkeeping
       f->retire.t += 1u;
-      launch_grow_retire(f->stream, f->d, f->grow, f->retire);
+      if (f->view.on)  // pk_grow_view: the first two counters are this pass's
+        PK_HIP(hipMemsetAsync(f->view.stats, 0, 2 * sizeof(unsigned long long), f->stream));
+      launch_grow_retire(f->stream, f->d, f->grow, f->retire, f->view);
     }
   }
   const std::string what = std::string(who) + " (new landmarks)";

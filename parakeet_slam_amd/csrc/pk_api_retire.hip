@@ -1,5 +1,5 @@
 // Retirement of stale readings and unconfirmed features behind the C ABI (pk_filter.hpp): switching it on and
-// off, the transfers of its clocks.  Host orchestration only; the kernels are in pk_k_grow_retire.hip, launched behind
+// off, the transfers of its clocks, the sensor's field of view (pk_grow_view).  Host orchestration only; the kernels are in pk_k_grow_retire.hip, launched behind
 // k_new_landmarks (pk_api_observe.hip) and ahead of k_grow_gather (pk_resample, pk_resample_adaptive).  What cannot carry the clocks
 // says so through refuse_retire (pk_api_shard.hip).
 #include "pk_filter.hpp"
@@ -15,6 +15,16 @@ void retire_release(pk_filter* f) {
     dev_free(f, &r.cnt[i]);
   }
   r = RetireState();
+  dev_free(f, &f->view.stats);  // (pk_grow_view: the view goes with the clocks)
+  f->view = RetireView();
+}
+
+// pk_grow_view / _state / _stats: a handle with retirement on
+int view_handle(const pk_filter* f, const char* who) {
+  if (!f) return fail(PK_ERR_INVALID, "%s: NULL handle", who);
+  if (!f->grow_on) return fail(PK_ERR_STATE, "%s: pk_grow_enable was not called on this filter", who);
+  if (!f->retire.on()) return fail(PK_ERR_STATE, "%s: nothing is being retired on this filter (pk_grow_retire)", who);
+  return PK_OK;
 }
 
 // pk_grow_clocks_download / _upload: a handle with retirement on and a range of its particles
@@ -71,6 +81,61 @@ int pk_grow_retire(pk_filter* f, int32_t reading_max_age, int32_t potential_max_
   }
   r.A = reading_max_age;
   r.M = potential_max_idle;
+  return PK_OK;
+}
+
+int pk_grow_view(pk_filter* f, double half_fov, double range_min, double range_max, int32_t confirmed_max_misses) {
+  int rc;
+  if ((rc = view_handle(f, "pk_grow_view"))) return rc;
+  constexpr double kPi = 3.14159265358979323846;
+  if (!(half_fov >= 0.0 && half_fov <= kPi)) return fail(PK_ERR_INVALID, "pk_grow_view: half_fov %g outside [0, pi]", half_fov);
+  RetireView& v = f->view;
+  if (half_fov == 0.0) {  // off: the counters stay allocated until the clocks go, and start again with the next view
+    v.on = false;
+    v.C = 0;
+    return PK_OK;
+  }
+  if (!(range_min >= 0.0) || std::isinf(range_min)) return fail(PK_ERR_INVALID, "pk_grow_view: range_min %g is not a finite distance >= 0", range_min);
+  if (!(range_max > range_min)) return fail(PK_ERR_INVALID, "pk_grow_view: range_max %g is not above range_min %g", range_max, range_min);
+  if (confirmed_max_misses < 0 || confirmed_max_misses > (1 << 30))
+    return fail(PK_ERR_INVALID, "pk_grow_view: confirmed_max_misses %d outside 0..2^30", (int)confirmed_max_misses);
+  if ((rc = use_device(f))) return rc;
+  if (!v.stats && (rc = dev_alloc(f, &v.stats, (size_t)kRetireViewWords))) return rc;
+  static_assert(PK_GROW_VIEW_STATS_BYTES == kRetireViewWords * sizeof(unsigned long long), "parakeet_slam.h");
+  if (!v.on) PK_HIP(hipMemsetAsync(v.stats, 0, kRetireViewWords * sizeof(unsigned long long), f->stream));  // switched on: the counters start
+  v.on = true;
+  v.C = confirmed_max_misses;
+  v.half_fov = half_fov;
+  v.r_min = range_min;
+  v.r_max = range_max;
+  v.rmin2 = range_min * range_min;
+  v.rmax2 = range_max * range_max;
+  return PK_OK;
+}
+
+int pk_grow_view_state(const pk_filter* f, int32_t* on, double view[3], int32_t* confirmed_max_misses) {
+  if (!f) return fail(PK_ERR_INVALID, "pk_grow_view_state: NULL handle");
+  const RetireView& v = f->view;
+  if (on) *on = v.on ? 1 : 0;
+  if (view) {
+    view[0] = v.on ? v.half_fov : 0.0;
+    view[1] = v.on ? v.r_min : 0.0;
+    view[2] = v.on ? v.r_max : 0.0;
+  }
+  if (confirmed_max_misses) *confirmed_max_misses = v.C;
+  return PK_OK;
+}
+
+int pk_grow_view_stats(pk_filter* f, int64_t out[4]) {
+  int rc;
+  if ((rc = view_handle(f, "pk_grow_view_stats"))) return rc;
+  if (!out) return fail(PK_ERR_INVALID, "pk_grow_view_stats: NULL argument");
+  if (!f->view.on) return fail(PK_ERR_STATE, "pk_grow_view_stats: this filter retires without a field of view (pk_grow_view)");
+  if ((rc = use_device(f))) return rc;
+  unsigned long long w[kRetireViewWords];
+  PK_HIP(hipMemcpyAsync(w, f->view.stats, sizeof(w), hipMemcpyDeviceToHost, f->stream));
+  PK_HIP(hipStreamSynchronize(f->stream));
+  for (int i = 0; i < kRetireViewWords; ++i) out[i] = (int64_t)w[i];
   return PK_OK;
 }
 

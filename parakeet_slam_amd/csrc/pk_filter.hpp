@@ -385,6 +385,7 @@ struct pk_filter {
   bool grow_on = false;
   bool grow_ranges = false;         // pk_grow_ranges: a ranged scan is taken, and one ranged sighting places a new feature (no per-particle state)
   RetireState retire{};            // pk_grow_retire (pk_api_retire.hip): the clocks of the retirement rule -- nothing until it is switched on
+  RetireView view{};               // pk_grow_view (pk_api_retire.hip): the field of view of that rule -- off, and 32 bytes of counters once asked for
   // the measurement-informed proposal (pk_propose / pk_propose_odom; pk_api_propose.hip): nothing until the first call, then
   // 84 P bytes -- ten rows of P doubles and one of P int32
   struct Proposal {

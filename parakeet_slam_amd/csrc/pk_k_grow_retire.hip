@@ -9,7 +9,13 @@
 // (tests/grow_retire_reference.py is the same in plain Python.)  The reference has no counterpart: its hypothesis_set only grows.
 //
 // Hand-written gfx950 (CDNA4, wave64), one wave per particle and four waves per workgroup as in k_new_landmarks: lane j is spare slot
-// j (S beyond 64: turns of 64, ascending).  Nothing here does float arithmetic.
+// j (S beyond 64: turns of 64, ascending).  Nothing in k_grow_retire does float arithmetic.
+//
+// A field of view (pk_grow_view; DESIGN.md section 9, "A field of view for retirement"): k_grow_retire_view is the same body with
+// steps 1 and 4 replaced by
+//   1'. ... else idle += 1 (saturating) ONLY where the slot's position mean lies in the sensor's field at the particle's live pose
+//   4'. M > 0: potential and idle >= M; C > 0: promoted (no potential bit in the seen word) and idle >= C
+// and four int64 counters written with integer atomics, once per wave from ballots.  retire_in_view is its only float arithmetic.
 #include "pk_device.hpp"
 
 namespace pk {
@@ -21,8 +27,33 @@ namespace pk {
 // the compiler from moving memory operations across it.
 __device__ __forceinline__ void retire_loads_before_stores() { __builtin_amdgcn_wave_barrier(); }
 
-__global__ void __launch_bounds__(256) k_grow_retire(GrowState g, RetireState r, unsigned char* map, size_t slot_bytes, size_t count_off,
-                                                     int Lp, int64_t P) {
+// Is the point (mx, my) inside the field v of a sensor at (px, py) heading along (ch, sn)?  Float64, operation by operation (no
+// contraction into fused multiply-adds: tests/grow_view_reference.py evaluates the same expressions in the same order; sincos and
+// pk_atan2 are within an ulp or two of the host's).  A NaN anywhere fails a comparison: not in view.
+#pragma clang fp contract(off)
+__device__ __forceinline__ bool retire_in_view(const RetireView& v, double px, double py, double sn, double ch, double mx, double my) {
+  const double dx = mx - px, dy = my - py;
+  const double q = dx * dx + dy * dy;
+  const double a = dx * ch + dy * sn;
+  const double c = dy * ch - dx * sn;
+  return q > 0.0 && q >= v.rmin2 && q <= v.rmax2 && fabs(pk_atan2(c, a)) <= v.half_fov;
+}
+#pragma clang fp contract(on)
+
+// step 4 / 4': does a slot with this seen word and idle count go
+template <bool kView>
+__device__ __forceinline__ bool retire_goes(int32_t sn, int32_t id, int M, int C) {
+  if constexpr (kView) {
+    return (sn & kPotentialBit) ? (M > 0 && id >= M) : (C > 0 && id >= C);
+  } else {
+    return M > 0 && (sn & kPotentialBit) && id >= M;
+  }
+}
+
+template <bool kView>
+__device__ __forceinline__ void grow_retire_body(const GrowState& g, const RetireState& r, const RetireView& v, const double* __restrict__ x,
+                                                 const double* __restrict__ y, const double* __restrict__ h, unsigned char* map,
+                                                 size_t slot_bytes, size_t count_off, int Lp, int64_t P) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t p = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
   if (p >= P) return;  // wave-uniform
@@ -44,27 +75,52 @@ __global__ void __launch_bounds__(256) k_grow_retire(GrowState g, RetireState r,
   cr = cr < 0 ? 0 : cr > n ? n : cr;
   cs = cs < 0 ? 0 : cs > used ? used : cs;
   const uint32_t t = r.t, A = (uint32_t)r.A;
-  const int M = r.M;
+  const int M = r.M, C = kView ? v.C : 0;
+  double px = 0.0, py = 0.0, psn = 0.0, pch = 1.0;  // the particle's live pose, read once per wave
+  if constexpr (kView) {
+    px = x[p];
+    py = y[p];
+    sincos(h[p], &psn, &pch);
+  }
 
-  // 1, 2 (slots): three words per slot in use
-  int m = 0;  // slots to retire
+  // 1, 2 (slots): three words per slot in use (1': and the two mean rows of an unchanged slot the pass knew)
+  int m = 0;                                     // slots to retire
+  int n_same = 0, n_view = 0, n_pot = 0;         // kView: unchanged slots the pass knew, those in view, potential ones among m
   for (int j0 = 0; j0 < used; j0 += kWave) {
     const int j = j0 + lane;
-    bool gone = false;
+    bool gone = false, same = false, view = false, pot = false;
     if (j < used) {
       const int32_t w = fc[j];
       int32_t sn = seen[j], id = idle[j];
       if (j >= cs || w != sn) {
         sn = w;
         id = 0;
+      } else if constexpr (kView) {
+        same = true;
+        view = retire_in_view(v, px, py, psn, pch, f[(size_t)F_MX * Lp + j], f[(size_t)F_MY * Lp + j]);
+        if (view && id != INT_MAX) ++id;
       } else if (id != INT_MAX) {
         ++id;
       }
       seen[j] = sn;
       idle[j] = id;
-      gone = M > 0 && (sn & kPotentialBit) && id >= M;
+      gone = retire_goes<kView>(sn, id, M, C);
+      pot = gone && (sn & kPotentialBit);
     }
     m += __popcll(__ballot(gone));
+    if constexpr (kView) {
+      n_same += __popcll(__ballot(same));
+      n_view += __popcll(__ballot(view));
+      n_pot += __popcll(__ballot(pot));
+    }
+  }
+  if constexpr (kView) {  // (integer atomics, one lane per wave; a zero is not sent)
+    if (lane == 0) {
+      if (n_same) atomicAdd(v.stats + 0, (unsigned long long)n_same);
+      if (n_view) atomicAdd(v.stats + 1, (unsigned long long)n_view);
+      if (n_pot) atomicAdd(v.stats + 2, (unsigned long long)n_pot);
+      if (m - n_pot) atomicAdd(v.stats + 3, (unsigned long long)(m - n_pot));
+    }
   }
   // 3: the stale prefix.  Readings from cr on are this scan's (stamp t, age 0): never stale
   int k = 0;
@@ -125,7 +181,7 @@ __global__ void __launch_bounds__(256) k_grow_retire(GrowState g, RetireState r,
         sn = seen[j];
         id = idle[j];
       }
-      const bool keep = j < used && !((sn & kPotentialBit) && id >= M);
+      const bool keep = j < used && !retire_goes<kView>(sn, id, M, C);
       const unsigned long long vote = __ballot(keep);
       const int dst = base + __popcll(vote & ((1ull << lane) - 1ull));
       const bool move = keep && dst != j;
@@ -178,10 +234,25 @@ __global__ void __launch_bounds__(256) k_grow_retire(GrowState g, RetireState r,
   }
 }
 
-void launch_grow_retire(hipStream_t s, DeviceState& d, const GrowState& g, const RetireState& r) {
+__global__ void __launch_bounds__(256) k_grow_retire(GrowState g, RetireState r, unsigned char* map, size_t slot_bytes, size_t count_off,
+                                                     int Lp, int64_t P) {
+  grow_retire_body<false>(g, r, RetireView(), nullptr, nullptr, nullptr, map, slot_bytes, count_off, Lp, P);
+}
+// pk_grow_view: rules 1' and 4' at the particles' live poses
+__global__ void __launch_bounds__(256) k_grow_retire_view(GrowState g, RetireState r, RetireView v, const double* __restrict__ x,
+                                                          const double* __restrict__ y, const double* __restrict__ h, unsigned char* map,
+                                                          size_t slot_bytes, size_t count_off, int Lp, int64_t P) {
+  grow_retire_body<true>(g, r, v, x, y, h, map, slot_bytes, count_off, Lp, P);
+}
+
+void launch_grow_retire(hipStream_t s, DeviceState& d, const GrowState& g, const RetireState& r, const RetireView& v) {
   if (d.P == 0) return;
-  hipLaunchKernelGGL(k_grow_retire, dim3((unsigned)((d.P + 3) / 4)), dim3(256), 0, s, g, r, d.map[d.mcur], d.lay.slot_bytes, d.lay.count_off,
-                     d.lay.Lp, d.P);
+  const dim3 grid((unsigned)((d.P + 3) / 4)), block(256);
+  if (v.on)
+    hipLaunchKernelGGL(k_grow_retire_view, grid, block, 0, s, g, r, v, d.x[d.cur], d.y[d.cur], d.h[d.cur], d.map[d.mcur], d.lay.slot_bytes,
+                       d.lay.count_off, d.lay.Lp, d.P);
+  else
+    hipLaunchKernelGGL(k_grow_retire, grid, block, 0, s, g, r, d.map[d.mcur], d.lay.slot_bytes, d.lay.count_off, d.lay.Lp, d.P);
 }
 
 // the clocks follow the particles wherever k_grow_gather takes the bookkeeping (launched before g.cur flips): slot k takes ancestor

@@ -72,6 +72,16 @@ struct RetireState {
   int A = 0, M = 0;                        // reading_max_age, potential_max_idle (0: never)
   bool on() const { return cnt[0] != nullptr; }
 };
+// the sensor's perceptual field for the retirement pass (pk_grow_view; DESIGN.md section 9, "A field of view for retirement"): kept
+// beside RetireState, not in it -- it holds nothing per particle, and the kernels that take RetireState by value keep their arguments
+constexpr int kRetireViewWords = 4;  // unchanged slots of the last pass | those in view | potential retired | confirmed retired
+struct RetireView {
+  bool on = false;
+  int C = 0;                                     // confirmed_max_misses (0: a promoted feature is never retired)
+  double half_fov = 0.0, r_min = 0.0, r_max = 0.0;  // as pk_grow_view received them
+  double rmin2 = 0.0, rmax2 = 0.0;               // r_min^2, r_max^2, formed once on the host
+  unsigned long long* stats = nullptr;           // [kRetireViewWords] on the device, from the first pk_grow_view until the clocks go
+};
 
 // Where the landmark slot of a particle lives: its own map buffer or the adoption buffer.
 struct SlotSource {
@@ -707,7 +717,8 @@ void launch_new_landmarks(hipStream_t s, DeviceState& d, GrowState& g, const Gro
 void launch_grow_gather(hipStream_t s, GrowState& g, const int32_t* anc_dev, int64_t P, const unsigned char* buf_dev = nullptr,
                         size_t stride = 0, size_t tail_off = 0);
 // behind launch_new_landmarks while retirement is on (r.t already counts this scan): every particle's slot is its own
-void launch_grow_retire(hipStream_t s, DeviceState& d, const GrowState& g, const RetireState& r);
+// (v.on: k_grow_retire_view at the live poses d.x / d.y / d.h [d.cur], its counters in v.stats; otherwise k_grow_retire as ever)
+void launch_grow_retire(hipStream_t s, DeviceState& d, const GrowState& g, const RetireState& r, const RetireView& v);
 // the clocks by the same ancestors, into the buffers launch_grow_gather makes current: BEFORE it (it flips g.cur)
 void launch_retire_gather(hipStream_t s, const GrowState& g, const RetireState& r, const int32_t* anc_dev, int64_t P);
 // scan block: pinned (device-mapped) host memory -> HBM by a kernel, in stream order
